@@ -17,6 +17,14 @@ call of data_util.py:242-281), and the figure the >= 10x target is quoted on.
 through `model`, fused clip + Adam, on G1 (small.bin is not obtainable offline); --batch-size 32 is the reference's
 README setting, 256 the default here.  Single GPU (the reference has no data-parallel E2E mode).
 
+A plain run sets up, warms up, times --steps steps and prints the headline line (`metric`, `value`, `unit`,
+`higher_is_better`, `dtype`, `ms_per_step`, the workload and the pipeline's own counters).  --full adds what takes runs
+of its own: the extra timing windows, the in-step stage intervals, the isolated sampler / positional-embedding probes
+and their rooflines, the CPU baseline and the parity legs against oracle/ (--no-cpu-baseline / --no-parity drop those
+two from a --full run).  --dump-outputs DIR writes what the last timed step computed as DIR/<name>.npy (float32 /
+float64, at most 64 MB, a fixed sample of larger arrays); the inputs depend on the flags only, so two builds can be
+compared output for output.
+
 Prints ONE JSON line on rank 0.  Multi-GPU: one process per GPU; when WORLD_SIZE is not set and --gpus N > 1 this
 script re-launches itself under torch.distributed.run (rendezvous on 127.0.0.1).  The seed batch is sharded by rank
 (rank r owns samples [step*N*bsz + r*bsz, +bsz)), the graph is replicated in every GPU's HBM, weak scaling.
@@ -101,6 +109,11 @@ def parse_args(argv=None):
                          "else needs the GPU; 0 in the training modes, where the in-order stream is the throttle the step needs)")
     ap.add_argument("--allow-posemb-flags", action="store_true",
                     help="do not fail when an eigen-iteration hit its restart cap (status bit 8); the count is reported either way")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the diagnostics: two more timing windows, eager steps for the stage intervals, "
+                         "the isolated sampler / positional-embedding probes and rooflines, the CPU baseline and the parity legs")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/<name>.npy (float32 / float64, at most 64 MB in all)")
     args = ap.parse_args(argv)
     if args.nodes is None:
         args.nodes = 10_000_000 if args.mode == "sampler" else 1_000_000
@@ -711,6 +724,43 @@ def stage_rooflines(args, acc, kern_iso, stage_ms, shape, pe_probe):
     return out
 
 
+# ------------------------------------------------------------------ --dump-outputs ----
+DUMP_BUDGET = 64 << 20          # bytes written in all
+DUMP_SAMPLE = 1 << 20           # elements kept of a larger array: a fixed, seeded sample
+
+
+def batch_arrays(prefix, g):
+    """One sampled view as its consumer reads it: the batched CSR (int32, exact in float64) and its positional embedding."""
+    out = {f"{prefix}_{k}": v for k, v in g.csr_numpy().items()}
+    if getattr(g, "pos_undirected", None) is not None:
+        out[f"{prefix}_pos_undirected"] = g.pos_undirected[: g.number_of_nodes()]
+    return out
+
+
+def dump_outputs(dirname, arrays):
+    """DIR/<name>.npy for every array: float32 stays float32, everything else becomes float64.  An array of more than
+    DUMP_SAMPLE elements is written as DIR/<name>.sample.npy: the elements at DUMP_SAMPLE flat indices drawn with a fixed
+    seed from its size, in ascending order."""
+    import torch
+
+    os.makedirs(dirname, exist_ok=True)
+    total = 0
+    for name, a in arrays.items():
+        if a is None:
+            continue
+        if isinstance(a, torch.Tensor):
+            a = a.detach().cpu().numpy()
+        a = np.asarray(a)
+        a = a.astype(np.float32 if a.dtype == np.float32 else np.float64)
+        if a.size > DUMP_SAMPLE:
+            idx = np.sort(np.random.default_rng(a.size).choice(a.size, DUMP_SAMPLE, replace=False))
+            a, name = a.reshape(-1)[idx], name + ".sample"
+        total += a.nbytes
+        if total > DUMP_BUDGET:
+            raise SystemExit(f"--dump-outputs: more than {DUMP_BUDGET >> 20} MB at {name}")
+        np.save(os.path.join(dirname, name + ".npy"), a)
+
+
 def main():
     args = parse_args()
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -778,18 +828,21 @@ def main():
         samplers = [sampler]
 
         def run_steps(first_step, count):            # `count` steps, S (or fewer) per call
-            at = 0
+            at, pairs = 0, None
             while at < count:
                 n = min(S, count - at)
-                sampler.sample_multi(first_id(first_step + at), n, world * B)
+                pairs = sampler.sample_multi(first_id(first_step + at), n, world * B)
                 at += n
+            return pairs
 
         run_steps(0, args.warmup)
         barrier()
         t0 = time.perf_counter()
-        run_steps(args.warmup, args.steps)
+        pairs = run_steps(args.warmup, args.steps)
         barrier()
         dt = time.perf_counter() - t0
+        if args.dump_outputs and rank == 0:          # the last step's two views
+            dump_outputs(args.dump_outputs, dict(**batch_arrays("q", pairs[-1][0]), **batch_arrays("k", pairs[-1][1])))
         extra["sampler_steps_per_call"] = S
         stages = ["seed-draw", "rwr-walk", "induce", "batch-pack"]
         produced = consumed = args.steps
@@ -818,18 +871,22 @@ def main():
         lane_streams = [torch.cuda.Stream(dev) for _ in range(args.lanes)]
 
         def run_steps(first_step, count):
+            pairs = None
             for cidx in range(first_step // chunk, (first_step + count) // chunk):
                 lane = cidx % args.lanes
                 with torch.cuda.stream(lane_streams[lane]):
                     pairs = samplers[lane].sample_multi(first_id(cidx * chunk), chunk, world * B)
                     posembs[lane].multi([g for pair in pairs for g in pair])
+            return pairs
 
         run_steps(0, args.warmup)
         barrier()
         t0 = time.perf_counter()
-        run_steps(args.warmup, args.steps)
+        pairs = run_steps(args.warmup, args.steps)
         barrier()
         dt = time.perf_counter() - t0
+        if args.dump_outputs and rank == 0:          # the last step's two views with their positional embeddings
+            dump_outputs(args.dump_outputs, dict(**batch_arrays("q", pairs[-1][0]), **batch_arrays("k", pairs[-1][1])))
         first_timed = args.warmup
         produced = consumed = args.steps
         stages = ["seed-draw", "rwr-walk", "induce", "batch-pack", "pos-emb:" + posemb.kind]
@@ -924,6 +981,16 @@ def main():
             last = trainer.step(first_timed + i, lr_at(first_timed + i), prof=profs[i])
         barrier()
         dt = time.perf_counter() - t0
+        if args.dump_outputs and rank == 0:
+            # what the last timed step handed its caller (loss, prob, gradient norm, the two views it trained on) and what
+            # it updated: the weights (and the key encoder's, the MoCo queue)
+            dump = {k: v for k, v in last.items() if k not in ("graph_q", "graph_k")}
+            dump.update(batch_arrays("q", last["graph_q"]), **batch_arrays("k", last["graph_k"]))
+            dump.update({"model." + k: v for k, v in model.state_dict().items()})
+            if args.mode == "train":
+                dump.update({"model_ema." + k: v for k, v in model_ema.state_dict().items()})
+                dump["contrast.memory"] = contrast.memory
+            dump_outputs(args.dump_outputs, dump)
         produced = (trainer.producer.launched - launched0) * chunk
         consumed = args.steps
         extra["producer_late"] = dict(chunks=trainer.producer.late_chunks - late0[0], chunks_consumed=args.steps // chunk,
@@ -937,7 +1004,7 @@ def main():
         # 20-step window is 16 ms, and the line should say how much such a window moves from one to the next
         windows = [dt / args.steps * 1e3]
         nxt_step = first_timed + args.steps
-        if world == 1 and args.steps <= 64:
+        if args.full and world == 1 and args.steps <= 64:
             for _w in range(2):
                 torch.cuda.synchronize()
                 tw0 = time.perf_counter()
@@ -946,8 +1013,9 @@ def main():
                 torch.cuda.synchronize()
                 windows.append((time.perf_counter() - tw0) / args.steps * 1e3)
                 nxt_step += args.steps
-        extra["ms_per_step_windows"] = windows
-        extra["ms_per_step_windows_note"] = "the timed window (= ms_per_step) and two more windows of --steps steps run right after it"
+        if args.full:
+            extra["ms_per_step_windows"] = windows
+            extra["ms_per_step_windows_note"] = "the timed window (= ms_per_step) and two more windows of --steps steps run right after it"
         first_after = nxt_step
         extra["final_loss"] = float(last["loss"].item())
         extra["step_launch"] = ("hipGraph replay (one captured graph per ring slot)" if graph_on else "eager (launch by launch)") + \
@@ -956,6 +1024,7 @@ def main():
         if graph_on:
             extra["graph_capture_failures"] = int(getattr(trainer, "graph_capture_failures", 0))
             extra["graph_replays_in_timed_region"] = int(trainer.graph_replays - (trainer.graph_replays_at_clock if hasattr(trainer, "graph_replays_at_clock") else 0))
+        if graph_on and args.full:
             trainer.use_graph = False                                     # stage intervals: eager steps right after the clock
             stage_profs = [{n: Prof(2) for n in names} for _ in range(chunk)]
             for i in range(chunk):
@@ -983,7 +1052,47 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
 
-    if rank == 0:
+    def headline():
+        """The fields of the line a plain run prints (--full adds its diagnostics to them)."""
+        line = {
+            "metric": "sampled-subgraphs/sec", "value": 2 * B * world * args.steps / dt, "unit": "subgraphs/s",
+            "n_gpus": world, "steps": args.steps, "warmup": first_timed, "warmup_requested": args.warmup,
+            "untimed_steps": first_timed,
+            "untimed_steps_note": "exactly the requested warm-up%s; the data pipeline is primed (first chunks sampled and embedded, no "
+                                  "training step) before the warm-up steps" % (" extended by --steady-steps %d" % args.steady_steps if getattr(args, "steady_steps", 0) > args.warmup else ""),
+            "ms_per_step": dt / args.steps * 1e3,
+            "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+            "dtype": "int32" if args.mode == "sampler" else "f32", "data": "synthetic",
+            "steps_per_sec": args.steps / dt,
+            "produced_steps": produced, "consumed_steps": consumed,
+            "config": {"workload": workload_name(args, world, V, E), "mode": args.mode,
+                       "graph_nodes": V, "graph_edges": E,
+                       "batch_size_per_gpu": B, "global_batch": B * world,
+                       "nce_k": args.nce_k if args.mode == "train" else (B - 1 if args.mode == "e2e" else None),
+                       "rw_hops": args.rw_hops, "restart_prob": args.restart_prob, "stages": stages,
+                       "parallelism": f"dp{world} (seed batch sharded, graph replicated)" + ("; OVERSUBSCRIBED: %d ranks on %d device(s), gloo, correctness only" % (world, ndev) if oversubscribed else "")
+                                      + ("; collectives forced on a 1-rank RCCL group (--collectives)" if args.collectives and world == 1 else "")},
+        }
+        if args.mode in ("train", "e2e"):
+            line["config"].update(producer_lanes=args.lanes, producer_depth=args.depth, producer_chunk=chunk,
+                                  producer_ahead=trainer.producer.ahead, reserved_cus=args.reserved_cus, hidden_size=args.hidden_size)
+        return line
+
+    def print_line(out):
+        try:                                     # (RCCL's version banner sits in the C library's stdout buffer until exit: out first,
+            import ctypes                        #  so that the JSON line is the LAST line of stdout)
+            ctypes.CDLL(None).fflush(None)
+        except Exception:
+            pass
+        sys.stdout.flush()
+        print(json.dumps(out), flush=True)
+
+    if rank == 0 and not args.full:
+        out = headline()
+        out.update(extra)
+        print_line(out)
+
+    if rank == 0 and args.full:
         from oracle import sampler as O   # checker side only: L table for the byte count (after the clock)
         lt = O.max_nodes_table(int(np.diff(rp).max()), args.rw_hops, args.restart_prob)
         # roofline of the HBM-bound sampler kernel: durations AND byte counts from an ISOLATED probe loop (same
@@ -1031,30 +1140,14 @@ def main():
                                               "time in the rocprofv3 --stats of this command: profiles/r5_kernel_stats_default.csv")
         else:
             roof = dict(samp_roofs[sampler_dom], dominant_by="largest isolated interval of a sampler call")
-        out = {
-            "metric": "sampled-subgraphs/sec", "value": 2 * B * world * args.steps / dt, "unit": "subgraphs/s",
-            "n_gpus": world, "steps": args.steps, "warmup": first_timed, "warmup_requested": args.warmup,
-            "untimed_steps": first_timed,
-            "untimed_steps_note": "exactly the requested warm-up%s; the data pipeline is primed (first chunks sampled and embedded, no "
-                                  "training step) before the warm-up steps" % (" extended by --steady-steps %d" % args.steady_steps if getattr(args, "steady_steps", 0) > args.warmup else ""),
-            "ms_per_step": ms_per_step,
-            "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-            "dtype": "int32" if args.mode == "sampler" else "f32", "data": "synthetic",
-            "steps_per_sec": args.steps / dt,
-            "produced_steps": produced, "consumed_steps": consumed,
-            "config": {"workload": workload_name(args, world, V, E), "mode": args.mode,
-                       "graph_nodes": V, "graph_edges": E,
-                       "batch_size_per_gpu": B, "global_batch": B * world,
-                       "nce_k": args.nce_k if args.mode == "train" else (B - 1 if args.mode == "e2e" else None),
-                       "rw_hops": args.rw_hops, "restart_prob": args.restart_prob, "stages": stages,
-                       "parallelism": f"dp{world} (seed batch sharded, graph replicated)" + ("; OVERSUBSCRIBED: %d ranks on %d device(s), gloo, correctness only" % (world, ndev) if oversubscribed else "")
-                                      + ("; collectives forced on a 1-rank RCCL group (--collectives)" if args.collectives and world == 1 else "")},
+        out = headline()
+        out.update({
             "kernel_ms_isolated": kern_iso, "kernel_ms_isolated_steps_per_launch": spc,
             "roofline": roof,
             "dominant_kernel": {"kernel": roof["kernel"], "bound": roof["bound"], "frac": roof["frac"], "by": roof["dominant_by"]},
             "sampler_rooflines": samp_roofs, "sampler_dominant_interval": sampler_dom,
             "algorithmic_bytes_per_step": acc,
-        }
+        })
         if args.mode == "sampler":
             # the whole sampler (five kernels per call, `sampler_steps_per_call` steps per call) against the HBM roof
             e2e = acc["total"] / (ms_per_step * 1e-3) / 1e9
@@ -1068,8 +1161,6 @@ def main():
             out["stage_rooflines"] = {"positional_embedding": dict(bound="f32 vector/MFMA rate of the CUs a solver workgroup occupies",
                                                                    peak_per_cu=F32_PER_CU_GFLOPS, unit="GFLOP/s per CU", **pe_probe)}
         if args.mode in ("train", "e2e"):
-            out["config"].update(producer_lanes=args.lanes, producer_depth=args.depth, producer_chunk=chunk,
-                                 producer_ahead=trainer.producer.ahead, reserved_cus=args.reserved_cus)
             used = [p for p in profs if p.get("used")]
             stage_ms = {n: float(np.mean([p[n].elapsed_ms(0, 1) for p in stage_profs])) for n in names}
             if used:
@@ -1079,7 +1170,6 @@ def main():
                     stage_ms["posemb_chunk_of_%d_views" % min(2 * chunk, 32)] = float(
                         np.mean([p["posemb"].elapsed_ms(0, 1) for p in used]))
             out["stage_ms"] = stage_ms
-            out["config"]["hidden_size"] = args.hidden_size
             if args.hidden_size > 64:
                 # the any-width step: no per-stage marks; the line's roofline is the GEMM every Linear runs on (csrc/ginx.hip),
                 # priced from an isolated replay of the step's training-stream launches on the last timed batch
@@ -1132,13 +1222,7 @@ def main():
             out["parity"] = par
             if "cpu_baseline" in out:            # (where rounds 3-5 published them)
                 out["cpu_baseline"].update(par)
-        try:                                     # (RCCL's version banner sits in the C library's stdout buffer until exit: out first,
-            import ctypes                        #  so that the JSON line is the LAST line of stdout)
-            ctypes.CDLL(None).fflush(None)
-        except Exception:
-            pass
-        sys.stdout.flush()
-        print(json.dumps(out), flush=True)
+        print_line(out)
     if world > 1:
         dist.barrier()
         dist.destroy_process_group()

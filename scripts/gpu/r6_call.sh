@@ -37,7 +37,7 @@ for part in "$@"; do
       echo "[$v]"; cut -c1-250 $O/posemb_phases_$v.txt ;;
     bench|driver)
       if [ $part = bench ]; then flags="--steps 192 --warmup 64"; f=bench_192; else flags="--steps 20 --warmup 5"; f=bench_driver; fi
-      (timeout 400 python bench.py $flags --no-cpu-baseline --no-parity 2>>$O/bench_$v.err | tail -1) > $O/${f}_$v.json
+      (timeout 400 python bench.py --full $flags --no-cpu-baseline --no-parity 2>>$O/bench_$v.err | tail -1) > $O/${f}_$v.json
       python -c "
 import json; d=json.loads(open('$O/${f}_$v.json').read()); s=d['stage_rooflines']; print('[$v] $f', round(d['ms_per_step'],4), 'ms/step', round(d['value']), 'subgraphs/s flags', (d.get('posemb_status') or {}).get('flags'), 'encoder fwd/bwd in step', round(s['gin_encoder_fwd']['ms_in_step'],3), round(s['gin_encoder_bwd']['ms_in_step'],3))" ;;
     pmc)  # sampler counters (separate --pmc passes, as MI355X_MICROARCH.md prescribes) + kernel stats of the sampler alone -> profiles/pmc_sampler.json

@@ -2,6 +2,7 @@
 MI355X: HIP kernels (through the C ABI) vs the reference-generated golden
 vectors and the CPU oracle.  Tolerance: north_star asks 1e-3 rel-fp32 for
 embeddings / NCE loss; the f32-MFMA path is held to 1e-4."""
+import copy
 import os
 
 import pytest
@@ -175,22 +176,27 @@ def test_long_rows_full_size_batch_vs_oracle():
     pos = torch.randn(q.parent_nid.numel(), 32, device="cuda") * 0.2
     q.pos_undirected = pos
     oracle = E.OracleGraphEncoder()
+    o64 = copy.deepcopy(oracle).double()
     model = reference_encoder().cuda()
     model.load_state_dict(oracle.state_dict())
     model.train()
     oracle.train()
+    o64.train()
     keep = (torch.rand(5, 32, 64) > 0.5).float()
     c = q.csr_numpy()
-    ref = oracle(c["node_off"].astype(np.int64), c["row_ptr"].astype(np.int64), c["col_idx"].astype(np.int64),
-                 pos[:n].cpu(), dropout_masks=keep)
+    args = (c["node_off"].astype(np.int64), c["row_ptr"].astype(np.int64), c["col_idx"].astype(np.int64))
+    ref = oracle(*args, pos[:n].cpu(), dropout_masks=keep)
     eng = model.engine()
     p, buf = eng.make_pass(model, q, training=True, keep=keep.cuda())
     eng.forward([p])
     torch.testing.assert_close(buf["feat"].cpu(), ref.detach(), rtol=1e-3, atol=1e-4)
     dfeat = torch.randn(32, 64)
-    ref.backward(dfeat)
     eng.backward(model, p, buf, dfeat.cuda())
-    _check_grads(model, {n: p_.grad for n, p_ in oracle.named_parameters() if p_.grad is not None})
+    # gradients against the oracle run in float64, at the same bar: the hub rows of this batch leave the GIN layers' output
+    # BatchNorm weights with gradients near zero (~4e-4 where the other tensors are O(1..100)), and there a float32 oracle's
+    # own rounding -- which moves with the host's thread count -- is several times the device's error
+    o64(*args, pos[:n].cpu().double(), dropout_masks=keep.double()).backward(dfeat.double())
+    _check_grads(model, {n: p_.grad.float() for n, p_ in o64.named_parameters() if p_.grad is not None})
 
 
 def test_tile_grid_smaller_than_the_batch_walks_on():
