@@ -2701,10 +2701,21 @@ constexpr int kChPWide = 64, kChPNarrow = 32;   // the two block widths of the s
 #endif
 constexpr int kChNarrowWant = GCC_POSEMB_CH_NARROW_WANT;   // items whose quotient must deliver at most this many pairs (k - zp) start with the narrow block (0: never)
 constexpr int kChNarrowGuards = 8;   // ... and move to the wide one when the first Ritz values show more than 32 - 8 wanted pairs
+// Workgroup size of the block class.  1024 threads hold the whole register file of their CU (4 waves per SIMD at 128
+// VGPRs).  512 threads are capped at 168 VGPRs (GCC_CHEB_REG_CAP), so that one 168-VGPR training wave per SIMD fits
+// beside them; measured in the pipeline that is no faster while the class still takes ~150 KB of the CU's 160 KB of LDS
+// (DESIGN.md section 6): it pays only together with a smaller LDS footprint.
 #ifndef GCC_POSEMB_CH_THREADS
 #define GCC_POSEMB_CH_THREADS 1024
 #endif
 constexpr int kChThreads = GCC_POSEMB_CH_THREADS;
+static_assert(kChThreads % 64 == 0 && kNodeMax % kChThreads == 0 && kChThreads >= 256 && kChThreads <= 1024, "block-class workgroup size");
+constexpr int kChRowsPerThread = kNodeMax / kChThreads;   // rows of the deflated matrix per thread in the row-wise scans
+#if defined(GCC_AMD_HIPEMU) || GCC_POSEMB_CH_THREADS > 512
+#define GCC_CHEB_REG_CAP
+#else
+#define GCC_CHEB_REG_CAP __attribute__((amdgpu_waves_per_eu(GCC_POSEMB_CH_THREADS / 256 + 1)))   // its waves per SIMD + one: <= 168 VGPRs at 512
+#endif
 constexpr int kChCsrCap = 12288;     // directed edges of the deflated subgraph (uint16 column ids in LDS)
 #ifndef GCC_POSEMB_CH_LONGDEG
 #define GCC_POSEMB_CH_LONGDEG 32
@@ -2750,7 +2761,7 @@ __host__ __device__ constexpr int cheb_lds_bytes()
     return 2 * (kNodeMax + 8) + 2 * kChCsrCap + 4 * kNodeMax + 4 * kChSlabFloats + cheb_region_bytes();
 }
 
-__global__ __launch_bounds__(kChThreads) void posemb_cheb_kernel(ChebArgs ca)
+__global__ __launch_bounds__(kChThreads) GCC_CHEB_REG_CAP void posemb_cheb_kernel(ChebArgs ca)
 {
     DYN_SMEM(smem);
     __shared__ EigShared es;
@@ -2766,7 +2777,6 @@ __global__ __launch_bounds__(kChThreads) void posemb_cheb_kernel(ChebArgs ca)
     constexpr int kCls = kClsCheb;
     const PosMulti &m = ca.m;
     const PosHead &hd = ca.hd;
-    const int tid = (int)threadIdx.x, lane = tid & 63, wv = tid >> 6;
     constexpr int kNW = kChThreads / 64;
     uint16_t *crow = (uint16_t *)smem;                       // [kNodeMax + 1] row offsets of the deflated CSR
     uint16_t *ccol = crow + (kNodeMax + 8);                  // [kChCsrCap]
@@ -2775,9 +2785,15 @@ __global__ __launch_bounds__(kChThreads) void posemb_cheb_kernel(ChebArgs ca)
     unsigned char *region = (unsigned char *)(slab + kChSlabFloats);
     for (;;) {                                               // items of this class
     __syncthreads();
-    if (tid == 0) sh_item = atomicAdd(hd.next + kCls, 1);
+    if (threadIdx.x == 0) sh_item = atomicAdd(hd.next + kCls, 1);
     __syncthreads();
     if (sh_item >= hd.count[kCls]) return;
+    // the thread index is opaque to the compiler once per item: what it derives from it (row / column assignments,
+    // LDS addresses of every phase) is recomputed per item instead of being hoisted out of the item loop and held in
+    // registers -- or scratch -- across all phases
+    uint32_t tid_ = threadIdx.x;
+    opaque_u32(tid_);
+    const int tid = (int)tid_, lane = tid & 63, wv = tid >> 6;
     const int gb = hd.list[(int64_t)kCls * hd.T + sh_item];
     PosArgs a;
     int b;
@@ -2822,7 +2838,7 @@ __global__ __launch_bounds__(kChThreads) void posemb_cheb_kernel(ChebArgs ca)
         }
         scale[d.ridx[i]] = sc;
     }
-    if (tid <= nr) crow[tid] = 0;                            // nr <= kNodeMax = kChThreads
+    for (int r = tid; r <= nr; r += kChThreads) crow[r] = 0;
     __syncthreads();
     for (int i = wv; i < n; i += kNW) {                      // kept neighbours per kept row
         if (d.ridx[i] == kNone) continue;                    // wave-uniform
@@ -2835,18 +2851,25 @@ __global__ __launch_bounds__(kChThreads) void posemb_cheb_kernel(ChebArgs ca)
         if (lane == 0) crow[d.ridx[i] + 1] = (uint16_t)(c > 65535 ? 65535 : c);
     }
     __syncthreads();
-    {                                                        // exclusive prefix: one row per thread
-        const int c = tid < nr ? (int)crow[tid + 1] : 0;
-        int incl = wave_scan_incl(c);
+    {                                                        // prefix over the rows: kChRowsPerThread consecutive rows per thread
+        const int r0 = kChRowsPerThread * tid;
+        int c[kChRowsPerThread], own = 0;
+#pragma unroll
+        for (int u = 0; u < kChRowsPerThread; ++u) { c[u] = r0 + u < nr ? (int)crow[r0 + u + 1] : 0; own += c[u]; }
+        int incl = wave_scan_incl(own);
         if (lane == 63) wsum[wv] = incl;
         __syncthreads();
         int base = 0;
         for (int q = 0; q < wv; ++q) base += wsum[q];
-        incl += base;
+        incl += base - own;
         __syncthreads();
-        if (tid < nr) {
-            if (incl > kChCsrCap) sh_fail = 1;               // does not fit: dense classes
-            crow[tid + 1] = (uint16_t)(incl > 65535 ? 65535 : incl);
+#pragma unroll
+        for (int u = 0; u < kChRowsPerThread; ++u) {
+            incl += c[u];
+            if (r0 + u < nr) {
+                if (incl > kChCsrCap) sh_fail = 1;           // does not fit: dense classes
+                crow[r0 + u + 1] = (uint16_t)(incl > 65535 ? 65535 : incl);
+            }
         }
     }
     __syncthreads();
@@ -2870,9 +2893,14 @@ __global__ __launch_bounds__(kChThreads) void posemb_cheb_kernel(ChebArgs ca)
     __syncthreads();
     PHASE_TICK(0);                                           // deflation + sparse matrix
     bool failed = sh_fail != 0;
-    // Long rows -> chunk tables for `slots` chunk slots (all threads; ends with a barrier).  Row r = thread r.
+    // Long rows -> chunk tables for `slots` chunk slots (all threads; ends with a barrier).  Thread t owns the
+    // kChRowsPerThread consecutive rows from kChRowsPerThread * t on, so the scans number rows in row order.
     auto build_chunks = [&](int slots) {
-        const int len = (tid < nr && !failed) ? (int)crow[tid + 1] - (int)crow[tid] : 0;
+        constexpr int R = kChRowsPerThread;
+        const int r0 = R * tid;
+        int len[R];
+#pragma unroll
+        for (int u = 0; u < R; ++u) len[u] = (r0 + u < nr && !failed) ? (int)crow[r0 + u + 1] - (int)crow[r0 + u] : 0;
         auto block_scan = [&](int v, int &total) -> int {                // exclusive prefix of v over the workgroup
             int incl = wave_scan_incl(v);
             if (lane == 63) wsum[wv] = incl;
@@ -2885,23 +2913,37 @@ __global__ __launch_bounds__(kChThreads) void posemb_cheb_kernel(ChebArgs ca)
         };
         int T = kChLongDeg, nl = 0, x = 0;
         for (;;) {                                                       // block-uniform: at most half of the slots are rows
-            x = block_scan(len > T ? 1 : 0, nl);
+            int own = 0;
+#pragma unroll
+            for (int u = 0; u < R; ++u) own += len[u] > T ? 1 : 0;
+            x = block_scan(own, nl);
             if (nl <= slots / 2) break;
             T *= 2;
         }
-        const bool lg = len > T;
-        int total = 0;
-        (void)block_scan(lg ? len : 0, total);
+        int own = 0, total = 0;
+#pragma unroll
+        for (int u = 0; u < R; ++u) own += len[u] > T ? len[u] : 0;
+        (void)block_scan(own, total);
         int clen = nl ? (total + (slots - nl) - 1) / (slots - nl) : 8;
         clen = clen < 8 ? 8 : (clen + 3) & ~3;
-        const int nch = lg ? (len + clen - 1) / clen : 0;
+        own = 0;
+#pragma unroll
+        for (int u = 0; u < R; ++u) own += len[u] > T ? (len[u] + clen - 1) / clen : 0;
         int nc = 0;
-        const int fx = block_scan(nch, nc);                              // nc <= total / clen + nl <= slots
-        if (tid < nr) rowx[tid] = lg ? (uint8_t)x : (uint8_t)0xFF;
-        if (lg) {
-            longrow[x] = tid;
-            longfirst[x] = fx;
-            for (int j = 0; j < nch; ++j) { chunk_beg[fx + j] = (int)crow[tid] + j * clen; chunk_row[fx + j] = (uint8_t)x; }
+        int fx = block_scan(own, nc);                                    // nc <= total / clen + nl <= slots
+#pragma unroll
+        for (int u = 0; u < R; ++u) {
+            const int r = r0 + u;
+            const bool lg = len[u] > T;
+            if (r < nr) rowx[r] = lg ? (uint8_t)x : (uint8_t)0xFF;
+            if (lg) {
+                const int nch = (len[u] + clen - 1) / clen;
+                longrow[x] = r;
+                longfirst[x] = fx;
+                for (int j = 0; j < nch; ++j) { chunk_beg[fx + j] = (int)crow[r] + j * clen; chunk_row[fx + j] = (uint8_t)x; }
+                ++x;
+                fx += nch;
+            }
         }
         if (tid == 0) { longfirst[nl] = nc; sh_nlong = nl; sh_nchunk = nc; sh_clen = clen; sh_long_t = T; }
         __syncthreads();
@@ -2917,9 +2959,8 @@ __global__ __launch_bounds__(kChThreads) void posemb_cheb_kernel(ChebArgs ca)
     auto solve = [&](auto pc) -> int {
     constexpr int P = decltype(pc)::value;
     constexpr int Ldy = P + 1;
-    constexpr int E = P * P / kChThreads;                    // entries of a P x P matrix per thread: 4 (P = 64) / 1 (P = 32)
+    constexpr int E = P * P / kChThreads;                    // entries of a P x P matrix per thread: 4 (P = 64) / 1 (P = 32) at 1024 threads
     constexpr int TPM = P / E;                               // threads per matrix row: 16 / 32
-    const int mi = tid / TPM, mj = E * (tid % TPM);          // this thread's strip of a P x P matrix: row mi, columns mj .. mj + E - 1
     constexpr int TPR = P / 8;                               // threads per block row in the products (8 columns each)
     constexpr int TPQ = P / 4;                               // ... in the rotation / tile loads (4 columns each)
     bool failed = build_failed;
@@ -2967,7 +3008,9 @@ __global__ __launch_bounds__(kChThreads) void posemb_cheb_kernel(ChebArgs ca)
     };
     auto spmm_body = [&](auto in_lds, const float *src, float *dst, float alpha, float center, float gamma) {
         const float *base = decltype(in_lds)::value ? (const float *)region : src;
-        const int q8 = 8 * (tid % TPR), g8 = tid / TPR;
+        uint32_t pt_ = (uint32_t)tid;                        // opaque per product (see the item loop)
+        opaque_u32(pt_);
+        const int q8 = 8 * ((int)pt_ % TPR), g8 = (int)pt_ / TPR;
         auto finish = [&](int r, const float *acc) {
             const float sr = scale[r];
             const float4 oa = *(const float4 *)(base + (int64_t)r * P + q8), ob = *(const float4 *)(base + (int64_t)r * P + q8 + 4);
@@ -3017,12 +3060,14 @@ __global__ __launch_bounds__(kChThreads) void posemb_cheb_kernel(ChebArgs ca)
     // workspace), read and overwritten by its owner only.  What a product still moves through L2 is off its chain: the
     // per-product copy of the block into LDS, the read-modify-write of the target block and the wait for its stores
     // (a third of a product's time at n' ~ 300) are gone.
-    constexpr int RPP = kChThreads / TPR;                    // rows per pass of the workgroup: 128 (P = 64) / 256 (P = 32)
-    constexpr int kPasses = 3;
+    constexpr int RPP = kChThreads / TPR;                    // rows per pass of the workgroup: 128 (P = 64) / 256 (P = 32) at 1024 threads
+    constexpr int kPasses = kChLdsRows / RPP;                // 3 at 1024 threads, 6 at 512 (8 registers of new rows per pass)
     static_assert(kChLdsRows == kPasses * RPP, "an LDS-resident block is covered in kPasses passes");
     auto filter_step_lds = [&](float *prev, float alpha, float center, float gamma) {
         float *xs = (float *)region;
-        const int q8 = 8 * (tid % TPR), g8 = tid / TPR;
+        uint32_t pt_ = (uint32_t)tid;                        // opaque per product (see the item loop)
+        opaque_u32(pt_);
+        const int q8 = 8 * ((int)pt_ % TPR), g8 = (int)pt_ / TPR;
         float nw[kPasses][8];
         auto finish = [&](int ps, int r, const float *acc) {             // -> nw[ps]; Y_{i-1}'s row becomes the next step's Y_{i-2}
             float4 da = make_float4(0.f, 0.f, 0.f, 0.f), db = da;
@@ -3111,6 +3156,10 @@ __global__ __launch_bounds__(kChThreads) void posemb_cheb_kernel(ChebArgs ca)
     // A round = filter of degree `deg`, then either a cheap re-orthonormalisation (X <- X R^-1) or, when the degrees
     // planned after the last Ritz step are spent, a Rayleigh-Ritz step with the convergence test.
     for (; round < kChRounds && !failed; ++round) {
+        uint32_t rt_ = (uint32_t)tid;                        // opaque once per round as well (see the item loop)
+        opaque_u32(rt_);
+        const int tid = (int)rt_, lane = tid & 63, wv = tid >> 6;
+        const int mi = tid / TPM, mj = E * (tid % TPM);      // this thread's strip of a P x P matrix: row mi, columns mj .. mj + E - 1
         remaining -= deg;
 #ifdef GCC_AMD_HIPEMU
         if (getenv("GCC_POSEMB_RR_ALWAYS")) remaining = 0;
@@ -3165,8 +3214,8 @@ __global__ __launch_bounds__(kChThreads) void posemb_cheb_kernel(ChebArgs ca)
         {
             constexpr int NB = P / 16;                            // blocks per side: 4 (P = 64) / 2 (P = 32)
             constexpr int kUn = 4;                                // steps (of four rows) requested together
-            if (wv < NB * NB) {                                   // (P = 32: four of the sixteen waves)
-                const int bi = wv / NB, bj = wv % NB, j = lane & 15, q = lane >> 4;
+            for (int blk = wv; blk < NB * NB; blk += kNW) {       // (a block per wave at 1024 threads, two at 512; P = 32: four blocks)
+                const int bi = blk / NB, bj = blk % NB, j = lane & 15, q = lane >> 4;
                 const f64x4 z4 = {0.0, 0.0, 0.0, 0.0};
                 f64x4 ga[2] = {z4, z4}, ka[2] = {z4, z4};         // two accumulators per product: consecutive steps do not wait for each other
                 const float *xa_ = XA + 16 * bi + j, *xb_ = XA + 16 * bj + j, *wb_ = XB + 16 * bj + j;
@@ -3197,7 +3246,7 @@ __global__ __launch_bounds__(kChThreads) void posemb_cheb_kernel(ChebArgs ca)
         }
         __syncthreads();
         PHASE_TICK(5);                                           // Gram matrices
-        // ---- small dense algebra, all 16 waves, fp64 in LDS: Jacobi scaling G^ = D G D; shifted Cholesky G^ = L L^T
+        // ---- small dense algebra, all waves, fp64 in LDS: Jacobi scaling G^ = D G D; shifted Cholesky G^ = L L^T
         //      (right-looking, two barriers per column); Linv = L^-1 by recursive doubling over the diagonal blocks
         //      (inv [A 0; B C] = [A^-1 0; -C^-1 B A^-1  C^-1]: 6 levels); with a Ritz step H = Linv K^ Linv^T
         double *Li = K + P * P;                                  // [P][P] L^-1 (lower); upper triangle = scratch
@@ -3323,9 +3372,10 @@ __global__ __launch_bounds__(kChThreads) void posemb_cheb_kernel(ChebArgs ca)
                 // holds scratch of the doubling levels: entries above the diagonal are read as zero, blocks above it are skipped.
                 // (Per thread E entries with a dot product of up to P terms each before: ~10 us per product.)
                 constexpr int NB = P / 16;
-                const int bi = wv / NB, bj = wv % NB, jl = lane & 15, ql = lane >> 4;
+                const int jl = lane & 15, ql = lane >> 4;
                 const f64x4 z4 = {0.0, 0.0, 0.0, 0.0};
-                if (wv < NB * NB) {
+                for (int blk = wv; blk < NB * NB; blk += kNW) {
+                    const int bi = blk / NB, bj = blk % NB;
                     f64x4 acc = z4;
                     for (int k0 = 0; k0 < 16 * (bi + 1); k0 += 4) {      // T1[i][j] = sum_{q <= i} Linv[i][q] K[q][j]
                         const int ii = 16 * bi + jl, kk = k0 + ql;
@@ -3336,7 +3386,8 @@ __global__ __launch_bounds__(kChThreads) void posemb_cheb_kernel(ChebArgs ca)
                     for (int r = 0; r < 4; ++r) G[(16 * bi + ql + 4 * r) * P + 16 * bj + jl] = acc[r];
                 }
                 __syncthreads();
-                if (wv < NB * NB) {
+                for (int blk = wv; blk < NB * NB; blk += kNW) {
+                    const int bi = blk / NB, bj = blk % NB;
                     f64x4 acc = z4;
                     for (int k0 = 0; k0 < 16 * (bj + 1); k0 += 4) {      // H[i][j] = sum_{q <= j} T1[i][q] Linv[j][q]
                         const int jj = 16 * bj + jl, kk = k0 + ql;
@@ -3423,12 +3474,17 @@ __global__ __launch_bounds__(kChThreads) void posemb_cheb_kernel(ChebArgs ca)
         __syncthreads();
         PHASE_TICK(8);                                           // C matrix
         // ---- X <- X C into the free buffer (W C stays in registers); residuals ||W_i - theta_i X_i||^2 accumulated per
-        //      thread, then over the 64 row groups
+        //      row group (rows g, g + kRG, ...), then over the kRG groups in order.  kRG is fixed by the slab, not by the
+        //      workgroup: a thread carries kRG / (kChThreads / TPQ) groups, so the sums do not depend on kChThreads.
         {
+            constexpr int kRG = kChSlabFloats / P, kG = kChThreads / TPQ, kS = kRG / kG;
+            static_assert(kS * kG == kRG, "residual row groups per thread");
             const int q4 = 4 * (tid % TPQ), g16 = tid / TPQ;
-            float r0 = 0.f, r1 = 0.f, r2 = 0.f, r3 = 0.f;
+            float rs[kS][4];
+#pragma unroll
+            for (int s = 0; s < kS; ++s) rs[s][0] = rs[s][1] = rs[s][2] = rs[s][3] = 0.f;
             const float t0 = theta[q4], t1 = theta[q4 + 1], t2 = theta[q4 + 2], t3 = theta[q4 + 3];
-            for (int r = g16; r < nr; r += kChThreads / TPQ) {
+            for (int r = g16, s = 0; r < nr; r += kG, s = s + 1 == kS ? 0 : s + 1) {
                 float xn[4] = {0.f, 0.f, 0.f, 0.f}, wn[4] = {0.f, 0.f, 0.f, 0.f};
                 for (int which = 0; which < (fullrr ? 2 : 1); ++which) {
                     const float *src = (which ? XB : XA) + (int64_t)r * P;
@@ -3461,16 +3517,23 @@ __global__ __launch_bounds__(kChThreads) void posemb_cheb_kernel(ChebArgs ca)
                     }
                 }
                 const float d0 = wn[0] - t0 * xn[0], d1 = wn[1] - t1 * xn[1], d2 = wn[2] - t2 * xn[2], d3 = wn[3] - t3 * xn[3];
-                r0 = fmaf(d0, d0, r0); r1 = fmaf(d1, d1, r1); r2 = fmaf(d2, d2, r2); r3 = fmaf(d3, d3, r3);
+#pragma unroll
+                for (int u = 0; u < kS; ++u) {
+                    if (u != s) continue;
+                    rs[u][0] = fmaf(d0, d0, rs[u][0]); rs[u][1] = fmaf(d1, d1, rs[u][1]);
+                    rs[u][2] = fmaf(d2, d2, rs[u][2]); rs[u][3] = fmaf(d3, d3, rs[u][3]);
+                }
             }
             __syncthreads();
             { float *t = XA; XA = XC; XC = t; }                          // block-uniform: the rotated block is X now
             if (fullrr) {
-                *(float4 *)(slab + g16 * P + q4) = make_float4(r0, r1, r2, r3);     // (1024 / TPQ) groups x P columns = 4096 floats
+#pragma unroll
+                for (int u = 0; u < kS; ++u)
+                    *(float4 *)(slab + (g16 + u * kG) * P + q4) = make_float4(rs[u][0], rs[u][1], rs[u][2], rs[u][3]);
                 __syncthreads();
                 if (tid < P) {
                     float sres = 0.f;
-                    for (int g = 0; g < kChThreads / TPQ; ++g) sres += slab[g * P + tid];
+                    for (int g = 0; g < kRG; ++g) sres += slab[g * P + tid];
                     resid[tid] = sqrtf(sres);
                 }
                 __syncthreads();
