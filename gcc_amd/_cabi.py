@@ -171,6 +171,20 @@ class GccGinwArgs(ctypes.Structure):
     ]
 
 
+class GccClsHeadArgs(ctypes.Structure):      # gcc_cls_head_args: the fine-tuning head (csrc/cls_head.hip)
+    _fields_ = [
+        ("feat", _VP), ("W", _VP), ("b", _VP), ("labels", _VP),
+        ("B", ctypes.c_int32), ("D", ctypes.c_int32), ("C", ctypes.c_int32), ("ld_feat", ctypes.c_int32),
+        ("ld_dfeat", ctypes.c_int32),
+        ("logits", _VP), ("dlogits", _VP), ("dW", _VP), ("db", _VP), ("dfeat", _VP), ("loss", _VP), ("correct", _VP),
+        ("meter_acc", _VP), ("meter_max", _VP), ("node_off", _VP), ("edge_off", _VP),
+        ("eval_loss_sum", _VP), ("eval_counts", _VP),
+    ]
+
+
+CLS_HEAD_MAX_CLASSES = 64
+CLS_HEAD_MAX_DIM = 256
+
 ABI_VERSION = 3          # GCC_AMD_ABI_VERSION of the include/gcc_amd.h these structs mirror (checked in load())
 GRAPH_CONTRACT_CHECKED = 1   # gcc_graph.flags
 
@@ -261,6 +275,11 @@ SIGNATURES = {
     "gcc_step_meters": (ctypes.c_int32, [ctypes.c_void_p] * 8 + [ctypes.c_int32, ctypes.c_void_p]),
     "gcc_ema_update": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_float,
                                         ctypes.c_void_p]),
+    "gcc_cls_head_train": (ctypes.c_int32, [ctypes.POINTER(GccClsHeadArgs), ctypes.c_void_p]),
+    "gcc_cls_head_eval": (ctypes.c_int32, [ctypes.POINTER(GccClsHeadArgs), ctypes.c_void_p]),
+    "gcc_adam_clipvalue_step": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                                 ctypes.c_int64, ctypes.c_float, ctypes.c_float, ctypes.c_float, ctypes.c_float,
+                                                 ctypes.c_float, ctypes.c_int32, ctypes.c_float, ctypes.c_float, ctypes.c_void_p]),
 }
 # symbols declared in the header but not built yet are listed here while the build is in progress
 PENDING = set()

@@ -587,6 +587,42 @@ int32_t gcc_adam_ema_step_scalars(float *param, float *grad, float *exp_avg, flo
 int32_t gcc_queue_enqueue_scalars(float *mem, int32_t K, const float *keys, int32_t nkeys,
                                   const gcc_step_scalars *scalars, void *stream);
 
+/* ------------------------------------------------------- fine-tuning head ---
+ * train.py --finetune (train_finetune / test_finetune of the reference, train.py:175-337): output_layer = nn.Linear(D, C),
+ * CrossEntropyLoss (mean over the batch) and out.argmax(1), as ONE single-workgroup launch.  Rows whose label is < 0 are
+ * padding (a partial last batch filled with empty subgraphs): they add nothing to the loss, the gradients or the counts.
+ * Limits: 1 <= C <= 64, 1 <= D <= 256; anything else is refused (rc < 0, gcc_last_error()).  Every sum over rows runs in a
+ * fixed order (no float atomics): two runs give bit-identical results. */
+typedef struct gcc_cls_head_args {
+    const float *feat;           /* device [B][ld_feat]: the encoder's embeddings, columns [0, D) used */
+    const float *W;              /* device [C][D] (torch layout of nn.Linear.weight) */
+    const float *b;              /* device [C] */
+    const int32_t *labels;       /* device [B]: class index, < 0 = padding row */
+    int32_t B, D, C, ld_feat, ld_dfeat;
+    float *logits;               /* device [B][C] out, or NULL */
+    float *dlogits;              /* train: device [B][C] out, (softmax - onehot) / valid rows, 0 on padding rows */
+    float *dW, *db;              /* train: device [C][D], [C] out (may point into a flat gradient buffer) */
+    float *dfeat;                /* train: device [B][ld_dfeat] out = dlogits W (columns past D written as 0) */
+    float *loss;                 /* train: device [1] out, mean over the valid rows */
+    int32_t *correct;            /* train: device [2] out {correct predictions, valid rows}, or NULL */
+    double *meter_acc;           /* train, optional: device double[5] += {loss * valid, correct, valid, nodes, 1} */
+    int32_t *meter_max;          /* train, optional: device int32[2] = max with {node_off[B], edge_off[B]} */
+    const int32_t *node_off, *edge_off;   /* device [B + 1] of the batch (for the meters), or NULL */
+    double *eval_loss_sum;       /* eval: device double[1] += sum over valid rows of the row's CE */
+    int32_t *eval_counts;        /* eval: device int32[2] += {correct predictions, valid rows} */
+} gcc_cls_head_args;
+/* logits, loss, dlogits, dW, db, dfeat, correct count (+ meters) of one training batch */
+int32_t gcc_cls_head_train(const gcc_cls_head_args *args, void *stream);
+/* forward only (held-out fold): accumulates eval_loss_sum / eval_counts, so the eval loop reads them once at the end */
+int32_t gcc_cls_head_eval(const gcc_cls_head_args *args, void *stream);
+
+/* clip_grad_value_(params, clip_value) + Adam.step() over one flat buffer: g <- clamp(g * grad_scale, -clip_value, clip_value)
+ * (stored back, as torch leaves the clipped gradient), then gcc_adam_step's update (L2 weight decay added to the clipped
+ * gradient, bias correction with step >= 1, eps outside the sqrt).  clip_value <= 0 disables the clamp.  One launch. */
+int32_t gcc_adam_clipvalue_step(float *param, float *grad, float *exp_avg, float *exp_avg_sq, int64_t n, float lr,
+                                float beta1, float beta2, float eps, float weight_decay, int32_t step, float clip_value,
+                                float grad_scale, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

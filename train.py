@@ -5,12 +5,15 @@ Same flag surface (all 49 flags of train.py:45-120, same names/types/defaults),
 same model_name / folder layout (train.py:133-166), same checkpoint dictionary
 ({opt, model, contrast, optimizer, epoch[, model_ema]}, train.py:748-786) and the
 same per-step semantics (train.py:378-434), executed by the MI355X-native hot
-path of gcc_amd.  Out of scope: --finetune / --cv (downstream
-supervised loops) and the non-"dgl" evaluation datasets.
+path of gcc_amd.  --finetune [--cv] (train_finetune / test_finetune, train.py:175-337,
+516-545, 800-815) fine-tunes a pre-trained encoder and a linear head on a labelled
+dataset (gcc_amd/finetune.py); without --finetune only the "dgl" corpus is served.
 
 The pre-training corpus ./data/small.bin (a DGL graph file, train.py:552) is read
 without DGL (gcc_amd/ingest.py).  Extra flags (not in the reference): --dgl-file,
---graph-npz / --synthetic choose another pre-training graph.
+--graph-npz / --synthetic choose another pre-training graph; --edgelist / --nodelabel,
+--tudataset, --graphs-npz and --edge-multiplicity name the labelled data of --finetune
+(as generate.py's flags do; the dataset files are not bundled).
 Multi-GPU: launch with torch.distributed.run; the seed batch is sharded by rank,
 keys are all-gathered before the enqueue, gradients are all-reduced (RCCL).
 """
@@ -122,6 +125,12 @@ def parse_option(argv=None):
     parser.add_argument("--max-steps", type=int, default=0, help="stop after this many steps (0 = full schedule)")
     parser.add_argument("--producer-lanes", type=int, default=2, help="data-pipeline streams (the GPU's command processor serves few queues well)")
     parser.add_argument("--producer-chunk", type=int, default=4, help="steps a lane prepares per turn (2x as many views per eigensolver call, <= 32)")
+    parser.add_argument("--edgelist", type=str, default=None, help="--finetune, node classification: <name>.edgelist of the reference's data folder")
+    parser.add_argument("--nodelabel", type=str, default=None, help="--finetune, node classification: <name>.nodelabel")
+    parser.add_argument("--tudataset", type=str, default=None, help="--finetune, graph classification: folder with the raw TU files of --dataset")
+    parser.add_argument("--graphs-npz", type=str, default=None, help="--finetune, graph classification: npz with node_off/row_ptr/col_idx/graph_labels")
+    parser.add_argument("--edge-multiplicity", type=int, default=0, help="copies of every edge in the reference's DGL graph (edge lists: detected)")
+    parser.add_argument("--no-prefetch", action="store_true", help="--finetune: make each batch on the step's stream")
     # fmt: on
 
     opt = parser.parse_args(argv)
@@ -279,9 +288,13 @@ def main(args):
     np.random.seed(args.seed)                             # train.py:483-486
     torch.manual_seed(args.seed)
     torch.cuda.manual_seed(args.seed)
-    if args.finetune or args.cv or args.dataset != "dgl":
-        raise NotImplementedError("--finetune/--cv and the evaluation datasets are outside the accelerated "
-                                  "pre-training path (SURVEY.md §2.1 #5, #7)")
+    if args.finetune:
+        from gcc_amd.finetune_main import main_finetune
+
+        return main_finetune(args, option_update)
+    if args.cv or args.dataset != "dgl":
+        raise NotImplementedError("--cv and the evaluation datasets need --finetune; pre-training reads the \"dgl\" corpus "
+                                  "(SURVEY.md §2.1 #5, #7)")
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
     if world > 1 and not args.moco:
@@ -437,5 +450,18 @@ if __name__ == "__main__":
     if args.gpu is None:
         args.gpu = [int(os.environ.get("LOCAL_RANK", "0"))]
     assert args.gpu is not None and torch.cuda.is_available()
-    args.gpu = args.gpu[0]                                 # train.py:817
-    main(args)
+    if args.cv:                                            # train.py:800-815: ten folds, each a fresh main() from the checkpoint
+        import copy
+
+        gpus = args.gpu
+        f1 = []
+        for fold_idx in range(10):
+            args.fold_idx = fold_idx
+            args.num_workers = 0
+            args.gpu = gpus[fold_idx % len(gpus)]
+            f1.append(main(copy.deepcopy(args)))
+        print(f1)
+        print(f"Mean = {np.mean(f1)}; Std = {np.std(f1)}")
+    else:
+        args.gpu = args.gpu[0]                             # train.py:817
+        main(args)
