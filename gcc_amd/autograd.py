@@ -7,7 +7,7 @@ from __future__ import annotations
 
 import torch
 
-from .encoder import H, grad_params
+from .encoder import STALE_SLOT_MSG, H, grad_params
 
 
 def _stream(t):
@@ -16,12 +16,10 @@ def _stream(t):
 
 class _GinFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, enc, g, keep, nparams, *params):
+    def forward(ctx, enc, g, keep, needs_backward, *params):
         eng = enc.engine()
         bn_training = enc.bn_training()
-        enc._calls += 1
-        slot = (enc._slot, enc._calls % 2)          # two passes may be in flight (E2E: model(q), model(k))
-        p, buf = eng.make_pass(enc, g, training=bn_training, keep=keep, slot=slot)
+        p, buf = eng.make_pass(enc, g, training=bn_training, keep=keep, slot=enc.pass_slot(needs_backward))
         if not bn_training and getattr(enc, "fused_eval", True):
             eng.eval_fused([p], stream=_stream(g.node_off))     # eval mode: one launch, one workgroup per subgraph
         else:
@@ -37,6 +35,8 @@ class _GinFn(torch.autograd.Function):
         enc = ctx.enc
         if not ctx.p.training:
             raise RuntimeError("backward through an eval-mode (running statistics) pass is not supported")
+        if not enc.engine().slot_is_current(ctx.buf):
+            raise RuntimeError(STALE_SLOT_MSG)
         targets = [enc.padded_zeros_like(param) for _, _, param in grad_params(enc)]
         enc.engine().backward(enc, ctx.p, ctx.buf, dfeat, targets=targets, stream=_stream(dfeat))
         return (None, None, None, None, *targets)
@@ -49,7 +49,7 @@ def gin_apply(enc, g, return_all_outputs=False):
         L = len(enc.gnn.ginlayers)
         keep = (torch.rand(L + 1, g.batch_size, H, device=g.node_off.device) >= enc.gnn.drop.p).float()
     params = [param for _, _, param in grad_params(enc)]
-    outs = _GinFn.apply(enc, g, keep, len(params), *params)
+    outs = _GinFn.apply(enc, g, keep, enc.needs_backward(params), *params)
     x = outs[0]
     if return_all_outputs:
         return x, list(outs[1:])

@@ -17,6 +17,9 @@ from . import _cabi
 
 H = _cabi.GIN_HIDDEN
 STATS_REPLICAS = 16        # kRep of gcc_amd/csrc/encoder_common.h (GCC_GIN_STAT_REPLICAS)
+STALE_SLOT_MSG = ("backward of a GraphEncoder forward whose activations were overwritten: at most two forward passes that need "
+                  "a backward (grad enabled, training mode) may be pending per encoder -- run backward before a third one; passes "
+                  "under torch.no_grad() or in eval mode keep a workspace of their own and may run at any time")
 
 
 # ---------------------------------------------------------------------------
@@ -123,6 +126,7 @@ class GinEngine:
         self.lib = lib if lib is not None else _cabi.load()
         self.ptr = ptr if ptr is not None else _cabi.dev_ptr
         self._bufs = {}
+        self._gen = {}              # buffer key -> generation: a forward stamps its slot, the API path's backward checks the stamp
         self.rows_hint = None       # gcc_gin_pass.rows_hint of every pass made from here on (None: launch for the capacity)
 
     def hint_rows(self, n, margin=1.10):
@@ -185,9 +189,17 @@ class GinEngine:
         if self.rows_hint is None:               # API path / tests: the first batch this engine sees sizes the grids (one host read, once;
             self.hint_rows(int(g.node_off[g.batch_size].item()))      # the fused steps set it before their first pass, outside any capture)
         p.rows_hint = int(self.rows_hint or 0)   # grid of the tile kernels: an upper estimate of the live rows (0: the capacity)
+        key = (slot, node_cap, g.batch_size, L, str(g.node_off.device))
+        self._gen[key] = self._gen.get(key, 0) + 1
         buf = dict(buf)
         buf["_keepalive"] = (g, keep, enc)      # the struct holds raw pointers into these
+        buf["_slot"] = (key, self._gen[key])    # which buffers this pass's activations live in, and its generation
         return p, buf
+
+    def slot_is_current(self, buf):
+        """False once a later pass has reused the buffers this pass's activations were stored in."""
+        key, gen = buf["_slot"]
+        return self._gen.get(key) == gen
 
     def forward(self, passes, stream=None, prof=None):
         arr = (_cabi.GccGinPass * len(passes))(*passes)
@@ -366,6 +378,20 @@ class GraphEncoder(nn.Module):
 
             self._wide_engine = WideGinEngine()
         return self._wide_engine
+
+    def needs_backward(self, params) -> bool:
+        """An API-path forward can be backpropagated: grad enabled, some parameter requires it, batch statistics."""
+        return torch.is_grad_enabled() and self.bn_training() and any(p.requires_grad for p in params)
+
+    def pass_slot(self, needs_backward):
+        """Workspace slot of an API-path forward.  Passes that may be backpropagated alternate between two slots (model(q),
+        model(k) of an E2E step are both pending); the backward checks that its slot was not reused since.  A pass nobody
+        can backpropagate (grad disabled, or eval-mode statistics) takes a slot of its own: it must never overwrite the
+        activations of a pending backward (its outputs are copies, so a later pass may reuse that slot)."""
+        if not needs_backward:
+            return (self._slot, "nograd")
+        self._calls += 1
+        return (self._slot, self._calls % 2)
 
     def bn_training(self) -> bool:
         """train.py:357-365: model_ema is in eval() but its BatchNorm layers are switched back to train()."""

@@ -94,12 +94,10 @@ def _stream(t):
 
 class _GinxFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, enc, g, keep, want_pooled, *params):
+    def forward(ctx, enc, g, keep, want_pooled, needs_backward, *params):
         eng = enc.wide_engine()
         training = enc.bn_training()
-        enc._calls += 1
-        slot = (enc._slot, enc._calls % 2)          # two passes may be in flight (E2E: model(q), model(k))
-        p, buf = eng.make_pass(enc, g, training=training, keep=keep, slot=slot, want_pooled=want_pooled)
+        p, buf = eng.make_pass(enc, g, training=training, keep=keep, slot=enc.pass_slot(needs_backward), want_pooled=want_pooled)
         eng.forward(p, stream=_stream(g.node_off))
         ctx.enc, ctx.p, ctx.buf = enc, p, buf
         L = len(enc.gnn.ginlayers)
@@ -109,20 +107,16 @@ class _GinxFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dfeat, *_unused):
-        from .encoder import grad_params
+        from .encoder import STALE_SLOT_MSG, grad_params
 
         enc = ctx.enc
         if not ctx.p.training:
             raise RuntimeError("backward through an eval-mode (running statistics) pass is not supported")
         if not enc.wide_engine().slot_is_current(ctx.buf):
-            # the activations of a pending backward live in one of two workspace slots per encoder (model(q), model(k) of an
-            # E2E step); a third forward before this backward has overwritten them -- gradients from the wrong activations
-            # would be silent
-            raise RuntimeError("backward of a GraphEncoder forward whose activations were overwritten: at most two forward passes "
-                               "of one wide encoder may be pending a backward (run backward, or wrap the extra passes in torch.no_grad())")
+            raise RuntimeError(STALE_SLOT_MSG)
         targets = [torch.zeros_like(param) for _, _, param in grad_params(enc)]
         enc.wide_engine().backward(enc, ctx.p, dfeat, targets, stream=_stream(dfeat))
-        return (None, None, None, None, *targets)
+        return (None, None, None, None, None, *targets)
 
 
 def ginx_apply(enc, g, return_all_outputs=False):
@@ -134,7 +128,7 @@ def ginx_apply(enc, g, return_all_outputs=False):
         L = len(enc.gnn.ginlayers)
         keep = (torch.rand(L + 1, g.batch_size, enc.output_dim, device=g.node_off.device) >= enc.gnn.drop.p).float()
     params = [param for _, _, param in grad_params(enc)]
-    outs = _GinxFn.apply(enc, g, keep, bool(return_all_outputs), *params)
+    outs = _GinxFn.apply(enc, g, keep, bool(return_all_outputs), enc.needs_backward(params), *params)
     if return_all_outputs:
         return outs[0], list(outs[1:])
     return outs[0]

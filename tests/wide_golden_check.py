@@ -3,7 +3,9 @@ the reference's GraphEncoder + MemoryMoCo + NCESoftmaxLoss + clip + Adam + momen
 float64 for the exact gradients).  One MoCo step through the any-width API path (GraphEncoder.forward -> csrc/ginx.hip,
 MemoryMoCo -> gcc_ncex_forward, torch.optim.Adam as train.py's wide path uses it); shared by the emulator tier
 (tests/test_wide_golden_emu.py) and the device tier (tests/test_wide_golden_gpu.py).  The bar is north_star's: 1e-3 of the
-tensor's largest entry for gradients (against the float64 run), 1e-3 relative for embeddings / logits / loss."""
+tensor's largest entry for gradients (against the float64 run), 1e-3 relative for embeddings / logits / loss.
+``run_fused_step`` is the same step through the fused MoCoTrainStep (MoCoTrainStep._body_wide) against the reference's post-step
+state."""
 import os
 
 import torch
@@ -99,3 +101,50 @@ def run_moco_step(hidden, device, to_batch, monkeypatch, gin_engine=None, nce_en
     torch.testing.assert_close(cpu(contrast.memory), c["after"]["memory"], rtol=1e-3, atol=2e-5)
     assert contrast.index == c["after"]["index"]
     return worst
+
+
+class _FixtureSampler:
+    def __init__(self, views, batch_size):
+        self.views, self.batch_size = views, batch_size
+
+    def sample(self, first_id, prof=None):
+        return self.views
+
+
+def run_fused_step(hidden, device, to_batch, gin_engine=None, nce_engine=None, flat_engine=None, sync=lambda: None):
+    """MoCoTrainStep at --hidden-size 128 / 256 (flat buffers, clip + Adam + EMA + meters as two launches, the any-width encoder
+    and head underneath) against what the reference's train.py step left behind: loss, prob, grad norm, weights, EMA, queue."""
+    from gcc_amd.contrast import MemoryMoCo
+    from gcc_amd.train_step import MoCoTrainStep
+    from tests.test_wide_encoder_emu import wide_encoder
+
+    G = gold()
+    c = G["cases"][hidden]
+    model, ema = wide_init.fill_(wide_encoder(hidden, hidden), 0).to(device), wide_init.fill_(wide_encoder(hidden, hidden), 1).to(device)
+    if gin_engine is not None:
+        model._wide_engine = ema._wide_engine = gin_engine()
+    contrast = MemoryMoCo(hidden, None, c["K"], c["T"], use_softmax=True)
+    with torch.no_grad():
+        contrast.memory.copy_(wide_init.tensor_for("contrast.memory", contrast.memory) * c["memory0_scale"])
+    contrast = contrast.to(device)
+    if nce_engine is not None:
+        contrast._engine = nce_engine()
+    views = (to_batch(G["views"][0]), to_batch(G["views"][1]))
+    step = MoCoTrainStep(model, ema, contrast, _FixtureSampler(views, views[0].batch_size), posemb=lambda gr: gr, prefetch=False,
+                         flat_engine=flat_engine() if flat_engine is not None else None)
+    assert step.wide and not step.use_graph
+    masks = c["masks"].to(device).contiguous()
+    step.mask_fn = lambda: masks
+    out = step.step(0, c["lr"])
+    sync()
+    cpu = lambda t: t.detach().cpu()
+    torch.testing.assert_close(cpu(out["loss"]).reshape(()), c["loss"], rtol=1e-4, atol=1e-5)
+    torch.testing.assert_close(cpu(out["prob"]).reshape(()), c["prob"], rtol=1e-3, atol=1e-4)
+    torch.testing.assert_close(cpu(torch.as_tensor(out["grad_norm"])).reshape(()).float(), c["grad_norm"].float(), rtol=1e-3, atol=1e-5)
+    torch.testing.assert_close(cpu(contrast.memory), c["after"]["memory"], rtol=1e-3, atol=2e-5)
+    assert contrast.index == c["after"]["index"]
+    for sd_name, mod in (("model", model), ("model_ema", ema)):
+        sd = mod.state_dict()
+        for key, ref in c["after"][sd_name].items():
+            if ref.dtype.is_floating_point:
+                torch.testing.assert_close(cpu(sd[key]), ref, rtol=1e-4, atol=2e-6, msg=lambda m, key=key, n=sd_name: f"{n}.{key}: {m}")
