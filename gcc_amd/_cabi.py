@@ -188,6 +188,43 @@ CLS_HEAD_MAX_DIM = 256
 ABI_VERSION = 3          # GCC_AMD_ABI_VERSION of the include/gcc_amd.h these structs mirror (checked in load())
 GRAPH_CONTRACT_CHECKED = 1   # gcc_graph.flags
 
+GAT_MAX_LAYERS = 8
+GAT_MAX_S2S_LAYERS = 8
+
+
+class GccGatWeights(ctypes.Structure):       # gcc_gat_weights: GraphEncoder(gnn_model="gat") (csrc/gat.hip)
+    _fields_ = [
+        ("num_layers", ctypes.c_int32), ("hidden", ctypes.c_int32), ("heads", ctypes.c_int32), ("out_dim", ctypes.c_int32),
+        ("pos_dim", ctypes.c_int32), ("deg_emb_dim", ctypes.c_int32), ("max_degree", ctypes.c_int32),
+        ("s2s_iters", ctypes.c_int32), ("s2s_layers", ctypes.c_int32), ("normalize", ctypes.c_int32),
+        ("norm_eps", ctypes.c_float),
+        ("degree_embedding", _VP),
+        ("fc", _VP * GAT_MAX_LAYERS), ("attn_l", _VP * GAT_MAX_LAYERS), ("attn_r", _VP * GAT_MAX_LAYERS),
+        ("w_ih", _VP * GAT_MAX_S2S_LAYERS), ("w_hh", _VP * GAT_MAX_S2S_LAYERS),
+        ("b_ih", _VP * GAT_MAX_S2S_LAYERS), ("b_hh", _VP * GAT_MAX_S2S_LAYERS),
+        ("ro0_w", _VP), ("ro0_b", _VP), ("ro2_w", _VP), ("ro2_b", _VP),
+    ]
+
+
+class GccGatGrads(ctypes.Structure):
+    _fields_ = [
+        ("degree_embedding", _VP),
+        ("fc", _VP * GAT_MAX_LAYERS), ("attn_l", _VP * GAT_MAX_LAYERS), ("attn_r", _VP * GAT_MAX_LAYERS),
+        ("w_ih", _VP * GAT_MAX_S2S_LAYERS), ("w_hh", _VP * GAT_MAX_S2S_LAYERS),
+        ("b_ih", _VP * GAT_MAX_S2S_LAYERS), ("b_hh", _VP * GAT_MAX_S2S_LAYERS),
+        ("ro0_w", _VP), ("ro0_b", _VP), ("ro2_w", _VP), ("ro2_b", _VP),
+    ]
+
+
+class GccGatPass(ctypes.Structure):
+    _fields_ = [
+        ("node_off", _VP), ("row_ptr", _VP), ("col_idx", _VP), ("seed_local", _VP), ("pos", _VP),
+        ("batch_size", ctypes.c_int32), ("node_cap", ctypes.c_int32), ("edge_multiplicity", ctypes.c_int32),
+        ("reserved_", ctypes.c_int32),
+        ("saved", _VP), ("out", _VP),
+    ]
+
+
 # name -> (restype, argtypes); the single source of truth for the symbol test
 SIGNATURES = {
     "gcc_abi_version": (ctypes.c_int32, []),
@@ -275,6 +312,12 @@ SIGNATURES = {
     "gcc_step_meters": (ctypes.c_int32, [ctypes.c_void_p] * 8 + [ctypes.c_int32, ctypes.c_void_p]),
     "gcc_ema_update": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_float,
                                         ctypes.c_void_p]),
+    "gcc_gat_saved_floats": (ctypes.c_int64, [ctypes.POINTER(GccGatWeights), ctypes.c_int32, ctypes.c_int32]),
+    "gcc_gat_forward": (ctypes.c_int32, [ctypes.POINTER(GccGatPass), ctypes.POINTER(GccGatWeights), ctypes.c_void_p]),
+    "gcc_gat_backward_workspace_bytes": (ctypes.c_int64, [ctypes.POINTER(GccGatWeights), ctypes.c_int32, ctypes.c_int32]),
+    "gcc_gat_backward": (ctypes.c_int32, [ctypes.POINTER(GccGatPass), ctypes.POINTER(GccGatWeights), ctypes.c_void_p,
+                                          ctypes.POINTER(GccGatGrads), ctypes.c_int32, ctypes.c_void_p, ctypes.c_int64,
+                                          ctypes.c_void_p]),
     "gcc_cls_head_train": (ctypes.c_int32, [ctypes.POINTER(GccClsHeadArgs), ctypes.c_void_p]),
     "gcc_cls_head_eval": (ctypes.c_int32, [ctypes.POINTER(GccClsHeadArgs), ctypes.c_void_p]),
     "gcc_adam_clipvalue_step": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,

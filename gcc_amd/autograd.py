@@ -7,7 +7,7 @@ from __future__ import annotations
 
 import torch
 
-from .encoder import STALE_SLOT_MSG, H, grad_params
+from .encoder import STALE_SLOT_MSG, H, gat_params, grad_params
 
 
 def _stream(t):
@@ -54,3 +54,38 @@ def gin_apply(enc, g, return_all_outputs=False):
     if return_all_outputs:
         return x, list(outs[1:])
     return x
+
+
+class _GatFn(torch.autograd.Function):
+    """GAT encoder + Set2Set + lin_readout + normalize (csrc/gat.hip).  The forward's activations are a tensor owned by
+    this node (``ctx``), not an engine slot: any number of passes may be pending.  The parameters go through
+    save_for_backward, so an in-place update between forward and backward (an optimizer step) raises, as in torch, instead
+    of differentiating with the new weights the pass structs point at."""
+
+    @staticmethod
+    def forward(ctx, enc, g, *params):
+        out, saved, p, w = enc.engine().forward(enc, g, stream=_stream(g.node_off))
+        ctx.enc, ctx.g, ctx.p, ctx.w = enc, g, p, w
+        ctx.saved_gat = saved          # p / w hold raw pointers into `saved` and the parameters of this pass
+        ctx.save_for_backward(*params)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        enc = ctx.enc
+        params = ctx.saved_tensors     # (raises if a parameter was modified in place since the forward)
+        targets = [torch.zeros_like(t) for t in params]
+        enc.engine().backward(enc, ctx.p, ctx.w, dout, targets, stream=_stream(dout))
+        return (None, None, *targets)
+
+
+def gat_apply(enc, g):
+    """GraphEncoder.forward for gnn_model="gat" (graph_encoder.py:132-196) on a BatchedCSR.  A pass nobody can
+    differentiate (grad disabled, or no parameter requires grad) builds no autograd node; its `saved` buffer is released
+    when the call returns."""
+    params = [t for _, _, t in gat_params(enc)]
+    if not (torch.is_grad_enabled() and any(t.requires_grad for t in params)):
+        with torch.no_grad():
+            out, _saved, _p, _w = enc.engine().forward(enc, g, stream=_stream(g.node_off))
+        return out
+    return _GatFn.apply(enc, g, *params)

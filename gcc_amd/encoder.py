@@ -66,6 +66,32 @@ class _Set2Set(nn.Module):                   # allocated by the reference, never
         self.lstm = nn.LSTM(2 * d, d, n_layers)
 
 
+class _GATConv(nn.Module):                   # DGL 0.4.3 GATConv(in, F, H, feat_drop=0, attn_drop=0, 0.2, residual=False)
+    def __init__(self, in_feats, out_feats, num_heads):
+        super().__init__()
+        self._num_heads, self._out_feats = num_heads, out_feats
+        self.fc = nn.Linear(in_feats, out_feats * num_heads, bias=False)
+        self.attn_l = nn.Parameter(torch.FloatTensor(1, num_heads, out_feats))
+        self.attn_r = nn.Parameter(torch.FloatTensor(1, num_heads, out_feats))
+        gain = nn.init.calculate_gain("relu")               # GATConv.reset_parameters
+        nn.init.xavier_normal_(self.fc.weight, gain=gain)
+        nn.init.xavier_normal_(self.attn_l, gain=gain)
+        nn.init.xavier_normal_(self.attn_r, gain=gain)
+
+
+class _GATLayer(nn.Module):                  # dgl.model_zoo.chem.gnn.GATLayer (agg_mode="flatten")
+    def __init__(self, in_feats, out_feats, num_heads):
+        super().__init__()
+        self.gnn = _GATConv(in_feats, out_feats, num_heads)
+
+
+class _UnsupervisedGAT(nn.Module):           # gat.py:16-34
+    def __init__(self, node_input_dim, node_hidden_dim, num_layers, num_heads):
+        super().__init__()
+        self.layers = nn.ModuleList([_GATLayer(node_input_dim if i == 0 else node_hidden_dim, node_hidden_dim // num_heads,
+                                               num_heads) for i in range(num_layers)])
+
+
 # ---------------------------------------------------------------------------
 def fill_weights(enc: "GraphEncoder", ptr) -> _cabi.GccGinWeights:
     """state tensors -> gcc_gin_weights.  ``ptr`` maps a tensor to its address
@@ -102,7 +128,9 @@ def fill_weights(enc: "GraphEncoder", ptr) -> _cabi.GccGinWeights:
 
 
 def grad_params(enc: "GraphEncoder"):
-    """Parameters that receive gradients, in gcc_gin_grads field order."""
+    """Parameters that receive gradients, in gcc_gin_grads (GAT: gcc_gat_grads) field order."""
+    if enc.gnn_model == "gat":
+        return gat_params(enc)
     g = enc.gnn
     out = [("degree_embedding", None, enc.degree_embedding.weight)]
     for i, layer in enumerate(g.ginlayers):
@@ -115,6 +143,97 @@ def grad_params(enc: "GraphEncoder"):
     for i, lin in enumerate(g.linears_prediction):
         out += [("pred_w", i, lin.weight), ("pred_b", i, lin.bias)]
     return out
+
+
+def gat_params(enc: "GraphEncoder"):
+    """Every parameter of a GAT encoder (all of them are live: set2set.* and lin_readout.* included), in gcc_gat_grads
+    field order: (field, index, parameter)."""
+    out = [("degree_embedding", None, enc.degree_embedding.weight)]
+    for i, layer in enumerate(enc.gnn.layers):
+        out += [("fc", i, layer.gnn.fc.weight), ("attn_l", i, layer.gnn.attn_l), ("attn_r", i, layer.gnn.attn_r)]
+    lstm = enc.set2set.lstm
+    for k in range(lstm.num_layers):
+        out += [("w_ih", k, getattr(lstm, f"weight_ih_l{k}")), ("w_hh", k, getattr(lstm, f"weight_hh_l{k}")),
+                ("b_ih", k, getattr(lstm, f"bias_ih_l{k}")), ("b_hh", k, getattr(lstm, f"bias_hh_l{k}"))]
+    ro = enc.lin_readout
+    out += [("ro0_w", None, ro[0].weight), ("ro0_b", None, ro[0].bias), ("ro2_w", None, ro[2].weight),
+            ("ro2_b", None, ro[2].bias)]
+    return out
+
+
+def _fill_struct(st, named, ptr):
+    for name, idx, t in named:
+        if idx is None:
+            setattr(st, name, ptr(t))
+        else:
+            getattr(st, name)[idx] = ptr(t)
+    return st
+
+
+class GatEngine:
+    """C-ABI calls of the GAT backbone (csrc/gat.hip).  Stateless between passes: a forward's activations live in the
+    ``saved`` tensor it returns, which the caller (the autograd node) owns -- so any number of passes may be pending.
+    ``lib``/``ptr`` are injectable so that tests can run the same host code against the emulator build."""
+
+    def __init__(self, lib=None, ptr=None):
+        self.lib = lib if lib is not None else _cabi.load()
+        self.ptr = ptr if ptr is not None else _cabi.dev_ptr
+
+    def weights(self, enc):
+        w = _cabi.GccGatWeights()
+        w.num_layers, w.hidden, w.heads, w.out_dim = len(enc.gnn.layers), enc.hidden, enc.num_heads, enc.output_dim
+        w.pos_dim, w.deg_emb_dim, w.max_degree = enc.positional_embedding_size, enc.degree_embedding_size, enc.max_degree
+        w.s2s_iters, w.s2s_layers = enc.num_step_set2set, enc.set2set.lstm.num_layers
+        w.normalize, w.norm_eps = int(enc.norm), 1e-5                     # graph_encoder.py:196
+        return _fill_struct(w, [(n, i, t.detach()) for n, i, t in gat_params(enc)], self.ptr)
+
+    @staticmethod
+    def _stream(t, stream):
+        if stream is None and t.is_cuda:
+            return torch.cuda.current_stream(t.device).cuda_stream
+        return stream
+
+    def forward(self, enc, g, stream=None):
+        """-> (out [B, out_dim], saved, pass struct, weights struct)"""
+        stream = self._stream(g.node_off, stream)
+        if g.pos_undirected is None:
+            raise RuntimeError("the batch has no pos_undirected (run the positional embedding first)")
+        w = self.weights(enc)
+        node_cap = g.parent_nid.numel() if hasattr(g, "parent_nid") else g.graph_id.numel()
+        n = self.lib.gcc_gat_saved_floats(ctypes.byref(w), node_cap, g.batch_size)
+        if n < 0:
+            raise RuntimeError(f"gcc_gat_saved_floats failed ({n}): {self.lib.gcc_last_error().decode()}")
+        dev = g.node_off.device
+        saved = torch.empty(n, dtype=torch.float32, device=dev)
+        out = torch.empty(g.batch_size, enc.output_dim, dtype=torch.float32, device=dev)
+        p = _cabi.GccGatPass()
+        ptr = self.ptr
+        p.node_off, p.row_ptr, p.col_idx = ptr(g.node_off), ptr(g.row_ptr), ptr(g.col_idx)
+        seed_local = getattr(g, "seed_local", None)
+        p.seed_local = ptr(seed_local) if seed_local is not None else None
+        p.pos = ptr(g.pos_undirected)
+        p.batch_size, p.node_cap = g.batch_size, node_cap
+        p.edge_multiplicity = int(getattr(g, "edge_multiplicity", 1))
+        p.saved, p.out = ptr(saved), ptr(out)
+        rc = self.lib.gcc_gat_forward(ctypes.byref(p), ctypes.byref(w), stream)
+        if rc != 0:
+            raise RuntimeError(f"gcc_gat_forward failed ({rc}): {self.lib.gcc_last_error().decode()}")
+        return out, saved, p, w
+
+    def backward(self, enc, p, w, dout, targets, accumulate=False, stream=None):
+        """gradients into ``targets`` (tensors in :func:`gat_params` order)."""
+        stream = self._stream(dout, stream)
+        nbytes = self.lib.gcc_gat_backward_workspace_bytes(ctypes.byref(w), p.node_cap, p.batch_size)
+        if nbytes < 0:
+            raise RuntimeError(f"gcc_gat_backward_workspace_bytes failed ({nbytes}): {self.lib.gcc_last_error().decode()}")
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=dout.device)
+        grads = _fill_struct(_cabi.GccGatGrads(), [(n, i, t) for (n, i, _), t in zip(gat_params(enc), targets)], self.ptr)
+        dout = dout.contiguous()
+        rc = self.lib.gcc_gat_backward(ctypes.byref(p), ctypes.byref(w), self.ptr(dout), ctypes.byref(grads), int(accumulate),
+                                       self.ptr(ws), nbytes, stream)
+        if rc != 0:
+            raise RuntimeError(f"gcc_gat_backward failed ({rc}): {self.lib.gcc_last_error().decode()}")
+        return targets
 
 
 class GinEngine:
@@ -250,21 +369,27 @@ class GinEngine:
 
 
 class GraphEncoder(nn.Module):
-    """graph_encoder.py:44-63 signature; only gnn_model="gin" with degree_input=True
-    (train.py:601-618) is implemented -- the other backbones are out of scope (SURVEY.md §2.1 #8)."""
+    """graph_encoder.py:44-63 signature; gnn_model="gin" and "gat" with degree_input=True (train.py:601-618) are
+    implemented -- "mpnn" does not run in the reference (graph_encoder.py:188 passes e_feat=None to NNConv)."""
 
     def __init__(self, positional_embedding_size=32, max_node_freq=8, max_edge_freq=8, max_degree=128,
                  freq_embedding_size=32, degree_embedding_size=32, output_dim=32, node_hidden_dim=32,
                  edge_hidden_dim=32, num_layers=6, num_heads=4, num_step_set2set=6, num_layer_set2set=3,
                  norm=False, gnn_model="mpnn", degree_input=False, lstm_as_gate=False):
         super().__init__()
-        if gnn_model != "gin":
-            raise NotImplementedError("gcc_amd accelerates the GIN path only (train.py:77 default)")
+        if gnn_model not in ("gin", "gat"):
+            raise NotImplementedError(f"gnn_model={gnn_model!r}: gcc_amd runs the \"gin\" (train.py:77 default) and \"gat\" "
+                                      "backbones (\"mpnn\" does not run in the reference: graph_encoder.py:188 feeds "
+                                      "e_feat=None to NNConv)")
         if not degree_input:
             raise NotImplementedError("train.py:617 always passes degree_input=True")
         if node_hidden_dim < 1 or output_dim < 1:
             raise ValueError(f"hidden / output size must be positive (got {node_hidden_dim} / {output_dim})")
         node_input_dim = positional_embedding_size + degree_embedding_size + 1      # graph_encoder.py:66-67
+        if gnn_model == "gat":
+            self._init_gat(positional_embedding_size, max_node_freq, max_edge_freq, max_degree, degree_embedding_size,
+                           output_dim, node_hidden_dim, num_layers, num_heads, num_step_set2set, num_layer_set2set, norm)
+            return
         # --hidden-size up to 64 runs on the fused 64-channel kernels, zero-padded and exact (ensure_padded); anything wider
         # (or a wider input) on the any-width kernels of csrc/ginx.hip (gcc_amd/encoder_wide.py): same arithmetic, unfused
         self.wide = node_hidden_dim > H or output_dim > H or node_input_dim > H
@@ -290,6 +415,42 @@ class GraphEncoder(nn.Module):
         self._slot = id(self)
         self._calls = 0
 
+    def _init_gat(self, pos, max_node_freq, max_edge_freq, max_degree, deg_emb, output_dim, hidden, num_layers, num_heads,
+                  num_step_set2set, num_layer_set2set, norm):
+        """gnn_model="gat": gat.py + Set2Set + lin_readout (graph_encoder.py:84-91, 124-129) on csrc/gat.hip."""
+        node_input_dim = pos + deg_emb + 1
+        if hidden > H or output_dim > H or hidden % num_heads != 0:
+            raise NotImplementedError(f"the GAT kernels serve hidden and output sizes up to {H} with hidden % num_heads == 0 "
+                                      f"(got hidden {hidden}, output {output_dim}, {num_heads} heads)")
+        if node_input_dim > H:
+            raise NotImplementedError(f"the GAT kernels take input features up to {H} columns (positional + degree "
+                                      f"embedding + 1 = {node_input_dim})")
+        if not 1 <= num_layers <= _cabi.GAT_MAX_LAYERS or not 1 <= num_layer_set2set <= _cabi.GAT_MAX_S2S_LAYERS \
+                or num_step_set2set < 1:
+            raise NotImplementedError(f"the GAT kernels serve 1..{_cabi.GAT_MAX_LAYERS} GAT layers, 1.."
+                                      f"{_cabi.GAT_MAX_S2S_LAYERS} LSTM layers and at least one Set2Set step")
+        self.wide = False
+        self.gnn = _UnsupervisedGAT(node_input_dim, hidden, num_layers, num_heads)
+        self.gnn_model = "gat"
+        self.max_node_freq, self.max_edge_freq = max_node_freq, max_edge_freq
+        self.max_degree = max_degree
+        self.degree_input = True
+        self.positional_embedding_size = pos
+        self.degree_embedding_size = deg_emb
+        self.degree_embedding = nn.Embedding(max_degree + 1, deg_emb)                  # :116-118
+        self.set2set = _Set2Set(hidden, num_layer_set2set)                             # :124
+        self.set2set.lstm.reset_parameters()          # DGL's Set2Set.__init__ calls reset_parameters(): a second draw
+        self.lin_readout = nn.Sequential(nn.Linear(2 * hidden, hidden), nn.ReLU(), nn.Linear(hidden, output_dim))
+        self.norm = norm
+        self.hidden, self.output_dim = int(hidden), int(output_dim)
+        self.num_heads, self.num_step_set2set = int(num_heads), int(num_step_set2set)
+        self._pad_ptrs = {}
+        self.fused_eval = False      # generate.py: model(q), model(k) and their mean (embed_views)
+        self._engine = None
+        self._wide_engine = None
+        self._slot = id(self)
+        self._calls = 0
+
     # ---- hidden / output sizes below 64: the kernels always compute 64 channels.  Every tensor they index by channel
     # (Linear rows and biases, BatchNorm weight / bias / running statistics, prediction layers) lives as the PREFIX of a
     # zero-padded block: a [h, k] weight is the first h rows of a [64, k] block, a [h] vector the first h entries of a [64]
@@ -297,7 +458,7 @@ class GraphEncoder(nn.Module):
     # their backward, and Adam never moves a weight whose gradient and value are zero -- so the padded model IS the narrow
     # model, and state_dict() / load_state_dict() see tensors of the reference's shapes (graph_encoder.py:44-63).
     def is_padded(self) -> bool:
-        return not self.wide and (self.hidden != H or self.output_dim != H)
+        return self.gnn_model == "gin" and not self.wide and (self.hidden != H or self.output_dim != H)
 
     def _channel_tensors(self):
         """(name, tensor holder, attribute, is_parameter) of every tensor whose leading dimension is a channel count."""
@@ -364,7 +525,11 @@ class GraphEncoder(nn.Module):
                 m._buffers[a] = home
             self._pad_ptrs[name] = home.data_ptr()
 
-    def engine(self) -> GinEngine:
+    def engine(self):
+        if self.gnn_model == "gat":
+            if self._engine is None:
+                self._engine = GatEngine()
+            return self._engine
         if self.wide:
             raise NotImplementedError(f"the fused 64-channel kernels serve hidden / output sizes up to {H}; this model "
                                       f"({self.hidden} / {self.output_dim}) runs through GraphEncoder.forward (csrc/ginx.hip)")
@@ -395,6 +560,8 @@ class GraphEncoder(nn.Module):
 
     def bn_training(self) -> bool:
         """train.py:357-365: model_ema is in eval() but its BatchNorm layers are switched back to train()."""
+        if self.gnn_model == "gat":      # no BatchNorm (and no dropout): train and eval mode compute the same thing
+            return self.training
         return self.gnn.batch_norms[0].training
 
     def embed_views(self, graph_q, graph_k):
@@ -402,7 +569,7 @@ class GraphEncoder(nn.Module):
         as workgroups of the same gcc_gin_eval_fused call, the mean taken on the device).  -> [B, output_dim]"""
         if self.bn_training():
             raise RuntimeError("embed_views is the eval-mode path (generate.py:38 calls model.eval())")
-        if self.wide:                                   # two eval passes and their mean (generate.py:48-52 as written)
+        if self.wide or self.gnn_model == "gat":                                   # two eval passes and their mean (generate.py:48-52 as written)
             with torch.no_grad():
                 fq = self(graph_q)
                 return fq.clone() if graph_k is graph_q else (fq + self(graph_k)) / 2
@@ -419,6 +586,11 @@ class GraphEncoder(nn.Module):
         return mean[:, : self.output_dim].clone()
 
     def forward(self, g, return_all_outputs=False):
+        if self.gnn_model == "gat":
+            from .autograd import gat_apply
+
+            x = gat_apply(self, g)
+            return (x, None) if return_all_outputs else x          # graph_encoder.py:192
         if self.wide:
             from .encoder_wide import ginx_apply
 

@@ -273,8 +273,8 @@ def evaluate(model, head, dataset, order, engine=None, stream=None):
 
 def embed_eval(model, graph_q, st=None):
     """model(graph_q) in eval mode: one gcc_gin_eval_fused launch (fused 64-channel kernels) -> [B, 64] device tensor
-    (columns past output_dim zero); wide models through GraphEncoder.forward"""
-    if model.wide:
+    (columns past output_dim zero); wide and GAT models through GraphEncoder.forward"""
+    if model.wide or model.gnn_model == "gat":
         with torch.no_grad():
             return model(graph_q).contiguous()
     eng = model.engine()

@@ -123,7 +123,7 @@ def main_finetune(args, option_update):
 
     contrast = MemoryMoCo(args.hidden_size, None, args.nce_k, args.nce_t, use_softmax=True).to(dev)   # (checkpointed only)
     output_layer = nn.Linear(in_features=args.hidden_size, out_features=dataset.num_classes).to(dev)  # train.py:637-646
-    fused = args.optimizer == "adam" and not model.wide
+    fused = args.optimizer == "adam" and not model.wide and model.gnn_model == "gin"
     if fused:
         flatten_parameters(model)
     clear_bn(model)                                                 # train.py:651-655 (before the resume, as there)
@@ -138,7 +138,7 @@ def main_finetune(args, option_update):
         trainer = FinetuneTrainStep(model, output_layer, learning_rate=args.learning_rate, betas=(args.beta1, args.beta2),
                                     weight_decay=args.weight_decay, clip_value=1.0)
         optimizer, head_optimizer = trainer.optimizer, trainer.head_optimizer
-    else:                                                           # API path: SGD / Adagrad, wide models (train.py:658-679)
+    else:                                                           # API path: SGD / Adagrad, wide and GAT models (train.py:658-679)
         trainer = None
         head_optimizer = torch.optim.Adam(output_layer.parameters(), lr=args.learning_rate, betas=(args.beta1, args.beta2),
                                           weight_decay=args.weight_decay)

@@ -623,6 +623,65 @@ int32_t gcc_adam_clipvalue_step(float *param, float *grad, float *exp_avg, float
                                 float beta1, float beta2, float eps, float weight_decay, int32_t step, float clip_value,
                                 float grad_scale, void *stream);
 
+/* ------------------------------------------------------------ GAT backbone ---
+ * GraphEncoder(gnn_model="gat") (gat.py + graph_encoder.py:152-196 of the reference): input features
+ * [pos | degree_embedding(clamp(in_degree)) | seed], L GATLayers (fc without bias, per-head attention logits el / er,
+ * leaky_relu(0.2) edge scores, softmax over each node's incoming edges, head-major flatten, F.leaky_relu between layers),
+ * Set2Set(D, T, Lr) with PyTorch's LSTM gate order (i, f, g, o), lin_readout (Linear, ReLU, Linear) and F.normalize.
+ * One workgroup per subgraph for the whole forward pass (one launch) and for the per-node / per-graph part of the
+ * backward; weight gradients are per-chunk partials summed in a fixed order (no float atomics: two backward calls
+ * give bit-identical gradients).  Limits: D = hidden <= 64 with D % heads == 0, out_dim <= 64,
+ * pos_dim + deg_emb_dim + 1 <= 64, L <= GCC_GAT_MAX_LAYERS, Lr <= GCC_GAT_MAX_S2S_LAYERS, T >= 1.
+ * The batch contract is symmetric (every CSR entry u in row v has an entry v in row u), as for the GIN kernels. */
+#define GCC_GAT_MAX_LAYERS 8
+#define GCC_GAT_MAX_S2S_LAYERS 8
+
+typedef struct gcc_gat_weights {
+    int32_t num_layers, hidden, heads, out_dim;       /* L, D, H, lin_readout output                     */
+    int32_t pos_dim, deg_emb_dim, max_degree;
+    int32_t s2s_iters, s2s_layers;                    /* T (--set2set-iter), Lr (--set2set-lstm-layer)    */
+    int32_t normalize;                                /* F.normalize(p=2, dim=-1, eps=norm_eps) at the end */
+    float norm_eps;
+    const float *degree_embedding;                    /* [max_degree + 1][deg_emb_dim]                   */
+    const float *fc[GCC_GAT_MAX_LAYERS];              /* gnn.layers.i.gnn.fc.weight [D][in]               */
+    const float *attn_l[GCC_GAT_MAX_LAYERS];          /* gnn.layers.i.gnn.attn_l [1][H][D/H]              */
+    const float *attn_r[GCC_GAT_MAX_LAYERS];
+    const float *w_ih[GCC_GAT_MAX_S2S_LAYERS];        /* set2set.lstm.weight_ih_lk [4D][2D | D]           */
+    const float *w_hh[GCC_GAT_MAX_S2S_LAYERS];        /* set2set.lstm.weight_hh_lk [4D][D]                */
+    const float *b_ih[GCC_GAT_MAX_S2S_LAYERS];
+    const float *b_hh[GCC_GAT_MAX_S2S_LAYERS];
+    const float *ro0_w, *ro0_b;                       /* lin_readout.0 [D][2D], [D]                       */
+    const float *ro2_w, *ro2_b;                       /* lin_readout.2 [out][D], [out]                    */
+} gcc_gat_weights;
+
+typedef struct gcc_gat_grads {                        /* device gradients, same shapes as the weights     */
+    float *degree_embedding;
+    float *fc[GCC_GAT_MAX_LAYERS], *attn_l[GCC_GAT_MAX_LAYERS], *attn_r[GCC_GAT_MAX_LAYERS];
+    float *w_ih[GCC_GAT_MAX_S2S_LAYERS], *w_hh[GCC_GAT_MAX_S2S_LAYERS];
+    float *b_ih[GCC_GAT_MAX_S2S_LAYERS], *b_hh[GCC_GAT_MAX_S2S_LAYERS];
+    float *ro0_w, *ro0_b, *ro2_w, *ro2_b;
+} gcc_gat_grads;
+
+typedef struct gcc_gat_pass {
+    const int32_t *node_off, *row_ptr, *col_idx;      /* the batch (gcc_gin_pass)                         */
+    const int32_t *seed_local;                        /* device [B] or NULL (seed = first node)           */
+    const float *pos;                                 /* device [node_cap][pos_dim]                       */
+    int32_t batch_size, node_cap, edge_multiplicity, reserved_;
+    float *saved;                                     /* device, gcc_gat_saved_floats() floats: activations the
+                                                         backward reads (written by gcc_gat_forward)       */
+    float *out;                                       /* device [B][out_dim]                              */
+} gcc_gat_pass;
+
+/* floats of gcc_gat_pass.saved for this model and batch capacity (< 0: refused, gcc_last_error()) */
+int64_t gcc_gat_saved_floats(const gcc_gat_weights *w, int32_t node_cap, int32_t batch_size);
+/* the forward pass: one launch, one workgroup per subgraph */
+int32_t gcc_gat_forward(const gcc_gat_pass *p, const gcc_gat_weights *w, void *stream);
+int64_t gcc_gat_backward_workspace_bytes(const gcc_gat_weights *w, int32_t node_cap, int32_t batch_size);
+/* backward of a gcc_gat_forward pass (same p, w, unchanged saved): dout [B][out_dim] -> every parameter gradient,
+ * written (accumulate = 0) or added (accumulate = 1).  Three launches. */
+int32_t gcc_gat_backward(const gcc_gat_pass *p, const gcc_gat_weights *w, const float *dout, const gcc_gat_grads *g,
+                         int32_t accumulate, void *workspace, int64_t workspace_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -297,6 +297,9 @@ def main(args):
                                   "(SURVEY.md §2.1 #5, #7)")
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
+    if world > 1 and args.model == "gat":
+        raise NotImplementedError("--model gat runs the single-GPU API path (autograd + torch.optim); the data-parallel "
+                                  "step is GIN's: run --model gat with WORLD_SIZE=1")
     if world > 1 and not args.moco:
         raise NotImplementedError("only the MoCo step is data parallel (seed batch sharded by rank, key all-gather, gradient "
                                   "all-reduce); the E2E / --nce-k 0 path would train N identical replicas: run it on one GPU")
@@ -352,12 +355,13 @@ def main(args):
     posemb = None                                         # API path only; the fused steps embed in their producer lanes
     trainer, optimizer = None, None
     wide = model.wide or contrast.wide    # above 64 channels (or a wider input): the any-width kernels (csrc/ginx.hip)
+    gat = model.gnn_model == "gat"        # GAT (csrc/gat.hip): the API path below for every optimizer, MoCo and E2E
     # --moco with Adam: the fused step at every width (MoCoTrainStep: producer lanes, flat buffers, clip + Adam + EMA as two launches,
     # data parallel; above 64 channels on the any-width kernels, launch by launch).  E2E above 64 channels and SGD / Adagrad: the API
     # path below (single GPU)
     if wide and world > 1 and not (args.moco and args.optimizer == "adam"):
         raise NotImplementedError("--hidden-size above 64 on several GPUs needs --moco with --optimizer adam (the data-parallel step)")
-    if args.optimizer == "adam" and (not wide or args.moco):
+    if args.optimizer == "adam" and (not wide or args.moco) and not gat:
         # data pipeline: `producer_lanes` streams, each preparing `producer_chunk` steps per turn (sampler calls + one
         # multi-view eigensolver call) -- the role of the reference's --num-workers DataLoader processes
         lanes, depth = [], 2
@@ -387,7 +391,7 @@ def main(args):
             raise NotImplementedError("--optimizer sgd/adagrad runs the single-GPU API path; the data-parallel step is fused Adam")
         posemb = DevicePosEmb(args.batch_size, train_dataset.node_cap, args.positional_embedding_size,
                               device=dev, seed=args.seed)
-        if args.optimizer == "adam":                      # (--hidden-size above 64) train.py:667-672
+        if args.optimizer == "adam":                      # (--hidden-size above 64, --model gat) train.py:667-672
             optimizer = torch.optim.Adam(model.parameters(), lr=args.learning_rate, betas=(args.beta1, args.beta2),
                                          weight_decay=args.weight_decay)
         elif args.optimizer == "sgd":
