@@ -78,6 +78,32 @@ class NceEngine:
             raise RuntimeError(f"gcc_nce_backward failed ({rc}): {self.lib.gcc_last_error().decode()}")
         return dq
 
+    def one_pass(self):
+        """whether :meth:`forward_backward` takes the one-pass kernels (f32); bf16 stays on the four launches"""
+        return self.dtype == "f32"
+
+    def forward_backward(self, q, k, mem, T, dloss, patch=None, patch_index=0, stream=None, prof_fwd=None, prof_bwd=None):
+        """MoCo head (pos_mode 0), loss and d loss / d q together -> (outs, dq).  f32: gcc_nce_forward_backward, two launches
+        and one pass over the queue; bf16: :meth:`forward` + :meth:`backward` (four launches)."""
+        if not self.one_pass():
+            outs = self.forward(q, k, mem, T, 0, patch=patch, patch_index=patch_index, stream=stream, prof=prof_fwd)
+            return outs, self.backward(q, k, mem, T, 0, outs, dloss, patch=patch, patch_index=patch_index, stream=stream,
+                                       prof=prof_bwd)
+        B, K = q.shape[0], mem.shape[0]
+        f32 = dict(dtype=torch.float32, device=q.device)
+        outs = dict(lse=torch.empty(B, **f32), pos=torch.empty(B, **f32), loss=torch.empty(1, **f32), prob=torch.empty(1, **f32),
+                    out=None)
+        dq = torch.empty_like(q)
+        ws, nbytes = self._workspace(B, K, q.device)
+        a = self._args(q, k, mem, 1.0 / T, 0, patch, patch_index, outs, None)
+        dloss = dloss.reshape(1).to(torch.float32).contiguous()
+        rc = self.lib.gcc_nce_forward_backward(ctypes.byref(a), self.ptr(dloss), self.ptr(dq), self.ptr(ws), nbytes,
+                                               prof_fwd.handle if prof_fwd else None, prof_bwd.handle if prof_bwd else None,
+                                               stream)
+        if rc != 0:
+            raise RuntimeError(f"gcc_nce_forward_backward failed ({rc}): {self.lib.gcc_last_error().decode()}")
+        return outs, dq
+
     def set_scalars(self, scalars, lr, betas, adam_step, enqueue_index, dropout_seed, stream=None):
         """gcc_step_scalars_set: the per-step scalars of a replayed step into their device struct (uint8[24] tensor)."""
         rc = self.lib.gcc_step_scalars_set(self.ptr(scalars), float(lr), float(betas[0]), float(betas[1]), int(adam_step),
@@ -120,9 +146,13 @@ class NceEngine:
             raise RuntimeError(f"gcc_adam_step failed ({rc}): {self.lib.gcc_last_error().decode()}")
 
     def adam_ema(self, param, grad, exp_avg, exp_avg_sq, lr, betas, eps, weight_decay, step, max_norm, grad_norm,
-                 scratch, stream=None, grad_scale=1.0, ema=None, ema_src=None, ema_m=0.0, meters=None, scalars=None):
+                 scratch, stream=None, grad_scale=1.0, ema=None, ema_src=None, ema_m=0.0, meters=None, scalars=None,
+                 sumsq_parts=None, enqueue=None):
         """gcc_adam_ema_step: clip + Adam over ``param`` (the live prefix of the flat buffer ``ema_src``), the EMA copy
-        ``ema`` of all of ``ema_src`` and one step of the meters ``(acc, mx, loss, prob, q, k)`` in the Adam launch."""
+        ``ema`` of all of ``ema_src`` and one step of the meters ``(acc, mx, loss, prob, q, k)`` in the Adam launch.
+        With ``scalars``: ``sumsq_parts`` = (float64 tensor, count) of :meth:`GinEngine.backward`'s ``sumsq`` replaces the
+        sum-of-squares launch, ``enqueue`` = (queue, keys) puts the queue's enqueue into the Adam launch
+        (gcc_adam_ema_enqueue_step_scalars)."""
         ma = None
         if meters is not None:
             acc, mx, loss, prob, q, k = meters
@@ -130,6 +160,22 @@ class NceEngine:
                                          self.ptr(q.edge_off), self.ptr(k.node_off), int(q.batch_size))
         if ema is not None and (ema_src is None or ema_src.data_ptr() != param.data_ptr() or ema.numel() != ema_src.numel()):
             raise ValueError("adam_ema: param must be a prefix of ema_src, and ema the same size as ema_src")
+        if (sumsq_parts is not None or enqueue is not None) and scalars is None:
+            raise ValueError("adam_ema: sumsq_parts / enqueue are the device-resident-scalars step's")
+        if sumsq_parts is not None or enqueue is not None:
+            parts, nparts = sumsq_parts if sumsq_parts is not None else (None, 0)
+            queue, keys = enqueue if enqueue is not None else (None, None)
+            rc = self.lib.gcc_adam_ema_enqueue_step_scalars(
+                self.ptr(param), self.ptr(grad), self.ptr(exp_avg), self.ptr(exp_avg_sq), param.numel(), float(betas[0]),
+                float(betas[1]), float(eps), float(weight_decay), float(max_norm), float(grad_scale), self.ptr(grad_norm),
+                self.ptr(scratch), self.ptr(ema) if ema is not None else None, ema.numel() if ema is not None else 0,
+                float(ema_m), ctypes.byref(ma) if ma is not None else None, self.ptr(scalars),
+                self.ptr(parts) if parts is not None else None, int(nparts),
+                self.ptr(queue) if queue is not None else None, queue.shape[0] if queue is not None else 0,
+                self.ptr(keys) if keys is not None else None, keys.shape[0] if keys is not None else 0, stream)
+            if rc != 0:
+                raise RuntimeError(f"gcc_adam_ema_enqueue_step_scalars failed ({rc}): {self.lib.gcc_last_error().decode()}")
+            return
         if scalars is not None:                      # lr / bias corrections from the device struct (replayed step)
             rc = self.lib.gcc_adam_ema_step_scalars(
                 self.ptr(param), self.ptr(grad), self.ptr(exp_avg), self.ptr(exp_avg_sq), param.numel(), float(betas[0]),

@@ -42,7 +42,9 @@ struct FeatArgs {
     int32_t B, pos_dim, emb_dim, max_degree, mult;
     int32_t cap;                 // gcc_gin_pass.node_cap
 };
-struct FeatLaunch { FeatArgs p[kMaxPass]; };
+// the step's scalars fetch riding in this launch (gcc_gin_forward_fetch): ring == NULL = none
+struct FeatFetch { gcc_step_scalars *dev; const gcc_step_scalars *ring; unsigned long long *counter; int32_t ring_len; };
+struct FeatLaunch { FeatArgs p[kMaxPass]; FeatFetch f; };
 
 __global__ __launch_bounds__(kThreads) void gin_feat_kernel(FeatLaunch L)
 {
@@ -70,6 +72,21 @@ __global__ __launch_bounds__(kThreads) void gin_feat_kernel(FeatLaunch L)
     const int tf = first_tile();
     request(tf * kTile);
     const int N = a.node_off[a.B];
+    // gcc_step_scalars_fetch inside this launch, the first of a replayed step: ONE thread copies ring entry (*counter mod
+    // ring_len) of the host-pinned ring into the device struct and counts the step.  The entry's words are requested here as
+    // one batch, behind the thread's own tile requests (system-scope loads: the ring's lines are reused every ring_len
+    // steps), and stored at the end of the kernel, so the trip to host memory runs beside the thread's tile work.  Nothing
+    // in THIS launch reads the struct; its readers (readout, Adam, enqueue) are launches of their own further down the stream.
+    constexpr int kScWords = (int)(sizeof(gcc_step_scalars) / 4);
+    const bool fetch = L.f.ring && blockIdx.x == 0 && blockIdx.y == 0 && tid == 0;
+    uint32_t scw[kScWords];
+    unsigned long long step_n = 0;
+    if (fetch) {
+        step_n = *L.f.counter;
+        const uint32_t *src = (const uint32_t *)(L.f.ring + (step_n % (unsigned long long)L.f.ring_len));
+#pragma unroll
+        for (int i = 0; i < kScWords; ++i) scw[i] = load_system_u32(src + i);
+    }
     SCHED_FENCE();
     {
         const float4 z4 = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -109,6 +126,12 @@ __global__ __launch_bounds__(kThreads) void gin_feat_kernel(FeatLaunch L)
             }
             st4(a.x0 + (int64_t)vv[i] * H + 4 * t, x);
         }
+    }
+    if (fetch) {
+        uint32_t *dst = (uint32_t *)L.f.dev;
+#pragma unroll
+        for (int i = 0; i < kScWords; ++i) dst[i] = scw[i];
+        *L.f.counter = step_n + 1;
     }
 }
 
@@ -607,7 +630,7 @@ __global__ __launch_bounds__(kThreads) void gin_readout_kernel(ReadLaunch L)
 
 extern "C" void gcc_gin_debug_ticks(long long *device_ticks64) { g_gin_ticks = device_ticks64; }   /* diagnostics only */
 
-extern "C" int32_t gcc_gin_forward(const gcc_gin_pass *passes, int32_t npass, gcc_prof *prof, void *stream)
+static int32_t gin_forward_launches(const gcc_gin_pass *passes, int32_t npass, const FeatFetch &fetch, gcc_prof *prof, void *stream)
 {
     if (!passes || npass < 1 || npass > kMaxPass) {
         snprintf(g_err, kErrLen, "gcc_gin_forward: npass must be 1..%d", kMaxPass);
@@ -649,6 +672,7 @@ extern "C" int32_t gcc_gin_forward(const gcc_gin_pass *passes, int32_t npass, gc
                       p.batch_size, p.w.pos_dim, p.w.deg_emb_dim, p.w.max_degree, p.edge_multiplicity > 1 ? p.edge_multiplicity : 1,
                       (int32_t)p.node_cap};
         }
+        L.f = fetch;
         hipLaunchKernelGGL(gin_feat_kernel, grid, block, 0, s, L);
     }
     for (int l = 0; l < Lg; ++l) {
@@ -736,4 +760,20 @@ extern "C" int32_t gcc_gin_forward(const gcc_gin_pass *passes, int32_t npass, gc
         return -10;
     }
     return 0;
+}
+
+extern "C" int32_t gcc_gin_forward(const gcc_gin_pass *passes, int32_t npass, gcc_prof *prof, void *stream)
+{
+    return gin_forward_launches(passes, npass, FeatFetch{nullptr, nullptr, nullptr, 0}, prof, stream);
+}
+
+extern "C" int32_t gcc_gin_forward_fetch(const gcc_gin_pass *passes, int32_t npass, gcc_step_scalars *dev,
+                                         const gcc_step_scalars *ring, int32_t ring_len, unsigned long long *counter,
+                                         gcc_prof *prof, void *stream)
+{
+    if (!dev || !ring || !counter || ring_len < 1) {
+        snprintf(g_err, kErrLen, "gcc_gin_forward_fetch: bad argument");
+        return -1;
+    }
+    return gin_forward_launches(passes, npass, FeatFetch{dev, ring, counter, ring_len}, prof, stream);
 }

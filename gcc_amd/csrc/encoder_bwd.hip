@@ -831,11 +831,16 @@ struct FinalArgs {
     const float *demb_parts;  // [kEmbBlocks][emb_rows * emb_dim]
     gcc_gin_grads g;
     int32_t B, L, kdim0, emb_rows, emb_dim, accumulate, hid;
+    double *sumsq_parts;      // [gridDim.x] or NULL: every workgroup's sum of squares of what it wrote (gcc_gin_backward_sumsq)
 };
 
-__device__ __forceinline__ void put(float *dst, float v, int acc)
+// -> the value stored (what the gradient's norm is taken over); 0 without a destination
+__device__ __forceinline__ float put(float *dst, float v, int acc)
 {
-    if (dst) *dst = acc ? *dst + v : v;
+    if (!dst) return 0.f;
+    const float w = acc ? *dst + v : v;
+    *dst = w;
+    return w;
 }
 
 __global__ __launch_bounds__(kThreads) void gin_grad_final_kernel(FinalArgs a)
@@ -843,10 +848,18 @@ __global__ __launch_bounds__(kThreads) void gin_grad_final_kernel(FinalArgs a)
     TRAIN_STEP_WAVE_PRIORITY();
     const int64_t gid = (int64_t)blockIdx.x * kThreads + threadIdx.x;
     const int L = a.L;
-    int64_t base = 0;
+    float wrote = 0.f;        // every thread stores at most ONE gradient element
     // (1) weight gradients from the slabs: jobs [0, 2L) = linears.{0,1} of every layer, [2L, 3L+1) = linears_prediction
     const int njobs = 3 * L + 1;
     const int64_t n1 = (int64_t)njobs * H * H;
+    // (3) linears_prediction.i.bias = column sums of G_i
+    const int64_t n3 = (int64_t)(L + 1) * H;
+    // (4) BatchNorm weight/bias and Linear bias gradients from the backward sums
+    const int64_t n4 = (int64_t)L * 3 * 3 * H;
+    // (5) degree embedding: 8 threads per element, each adding kEmbBlocks / 8 of the partial tables (8 loads in flight),
+    // combined by a fixed shuffle tree.  The section starts on a wave boundary and is padded to whole waves (the shuffles
+    // need every lane); one thread per element walked all 448 partials in 56 dependent rounds (17 of this kernel's 20 us).
+    const int64_t base5 = (n1 + n3 + n4 + 63) & ~(int64_t)63;
     if (gid < n1) {
         const int y = (int)(gid / (H * H)), idx = (int)(gid % (H * H));
         const int o = idx / H, k = idx % H;
@@ -863,25 +876,15 @@ __global__ __launch_bounds__(kThreads) void gin_grad_final_kernel(FinalArgs a)
             kd = i == 0 ? a.kdim0 : a.hid;
             dst = a.g.pred_w[i];
         }
-        if (k < kd && dst) put(dst + (int64_t)o * kd + k, s, a.accumulate);
-        return;
-    }
-    base += n1;
-    // (3) linears_prediction.i.bias = column sums of G_i
-    const int64_t n3 = (int64_t)(L + 1) * H;
-    if (gid < base + n3) {
-        const int64_t r = gid - base;
+        if (k < kd && dst) wrote = put(dst + (int64_t)o * kd + k, s, a.accumulate);
+    } else if (gid < n1 + n3) {
+        const int64_t r = gid - n1;
         const int i = (int)(r / H), o = (int)(r % H);
         float s = 0.f;
         for (int c = 0; c < kWgChunks; ++c) s += a.bias_slabs[((int64_t)(2 * L + i) * kWgChunks + c) * H + o];
-        if (a.g.pred_b[i]) put(a.g.pred_b[i] + o, s, a.accumulate);
-        return;
-    }
-    base += n3;
-    // (4) BatchNorm weight/bias and Linear bias gradients from the backward sums
-    const int64_t n4 = (int64_t)L * 3 * 3 * H;
-    if (gid < base + n4) {
-        const int64_t r = gid - base;
+        if (a.g.pred_b[i]) wrote = put(a.g.pred_b[i] + o, s, a.accumulate);
+    } else if (gid < n1 + n3 + n4) {
+        const int64_t r = gid - (n1 + n3);
         const int c = (int)(r % H), slot = (int)((r / H) % 3), which = (int)((r / (3 * H)) % 3), l = (int)(r / (9 * H));
         double acc = 0.0;
         const double *src = a.bst + ((int64_t)l * 3 + which) * kRep * 3 * H + slot * H + c;
@@ -897,18 +900,11 @@ __global__ __launch_bounds__(kThreads) void gin_grad_final_kernel(FinalArgs a)
         if (which == 0) dst = slot == 0 ? a.g.bn_a_b[l] : slot == 1 ? a.g.bn_a_w[l] : a.g.lin0_b[l];
         else if (which == 1) dst = slot == 0 ? a.g.bn_b_b[l] : slot == 1 ? a.g.bn_b_w[l] : a.g.lin1_b[l];
         else dst = slot == 0 ? a.g.bn_c_b[l] : slot == 1 ? a.g.bn_c_w[l] : nullptr;
-        if (dst) put(dst + c, v, a.accumulate);
-        return;
-    }
-    base += n4;
-    // (5) degree embedding: 8 threads per element, each adding kEmbBlocks / 8 of the partial tables (8 loads in flight),
-    // combined by a fixed shuffle tree.  The section starts on a wave boundary and is padded to whole waves (the shuffles
-    // need every lane); one thread per element walked all 448 partials in 56 dependent rounds (17 of this kernel's 20 us).
-    base = (base + 63) & ~(int64_t)63;
-    const int64_t n5 = (int64_t)a.emb_rows * a.emb_dim;
-    if (gid >= base) {                                   // wave-uniform
+        if (dst) wrote = put(dst + c, v, a.accumulate);
+    } else if (gid >= base5) {                               // wave-uniform
+        const int64_t n5 = (int64_t)a.emb_rows * a.emb_dim;
         static_assert(kEmbBlocks % 64 == 0, "8 threads x batches of 8 partials");
-        const int64_t q = gid - base, r = q >> 3;
+        const int64_t q = gid - base5, r = q >> 3;
         const int part = (int)(q & 7);
         float s = 0.f;
         if (r < n5) {
@@ -923,7 +919,19 @@ __global__ __launch_bounds__(kThreads) void gin_grad_final_kernel(FinalArgs a)
         s += wave_shfl_xor(s, 1);
         s += wave_shfl_xor(s, 2);
         s += wave_shfl_xor(s, 4);
-        if (part == 0 && r < n5 && a.g.degree_embedding) put(a.g.degree_embedding + r, s, a.accumulate);
+        if (part == 0 && r < n5 && a.g.degree_embedding) wrote = put(a.g.degree_embedding + r, s, a.accumulate);
+    }
+    // The clip's sum of squares, taken where the values are: ONE fp64 partial per workgroup, in a slot of its own (fixed tree; no
+    // ticket -- the Adam launch adds the partials up).  It equals the sum over the caller's flat gradient buffer when every
+    // element of that buffer is either stored here -- each by exactly one thread above: the 64 x kd elements of a weight block
+    // (the rows past a hidden width below 64 included, as the zeros their slabs add up to), the 64 of a bias / BatchNorm vector,
+    // the embedding table -- or exactly zero (the trainer allocates the buffer zeroed and Adam's g * coef keeps a zero).
+    if (a.sumsq_parts) {                                     // (uniform)
+        __shared__ double red[kThreads / 64];
+        const double sq = wave_sum((double)wrote * (double)wrote);
+        if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = sq;
+        __syncthreads();
+        if (threadIdx.x == 0) a.sumsq_parts[blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
     }
 }
 
@@ -971,9 +979,10 @@ extern "C" int64_t gcc_gin_backward_workspace_bytes(int64_t node_cap, int32_t ba
     return bwd_layout(nullptr, node_cap, batch_size, num_gin_layers, kEmbMaxElems).total;
 }
 
-extern "C" int32_t gcc_gin_backward(const gcc_gin_pass *pass, const float *dfeat, const gcc_gin_grads *grads,
-                                    int32_t accumulate, void *workspace, int64_t workspace_bytes,
-                                    int64_t node_cap, gcc_prof *prof, void *stream)
+static int32_t gin_backward_launches(const gcc_gin_pass *pass, const float *dfeat, const gcc_gin_grads *grads,
+                                     int32_t accumulate, void *workspace, int64_t workspace_bytes,
+                                     int64_t node_cap, double *sumsq_parts, int32_t parts_cap, int32_t *nparts,
+                                     gcc_prof *prof, void *stream)
 {
     if (!pass || !dfeat || !grads || !workspace) {
         snprintf(g_err, kErrLen, "gcc_gin_backward: null argument");
@@ -1067,7 +1076,16 @@ extern "C" int32_t gcc_gin_backward(const gcc_gin_pass *pass, const float *dfeat
         a.accumulate = accumulate;
         const int64_t upto4 = (int64_t)(3 * L + 1) * H * H + (int64_t)(L + 1) * H + (int64_t)L * 9 * H;
         const int64_t total = ((upto4 + 63) & ~(int64_t)63) + (((int64_t)a.emb_rows * a.emb_dim * 8 + 63) & ~(int64_t)63);
-        hipLaunchKernelGGL(gin_grad_final_kernel, dim3((unsigned)((total + kThreads - 1) / kThreads)), block, 0, s, a);
+        const int64_t blocks = (total + kThreads - 1) / kThreads;
+        a.sumsq_parts = sumsq_parts;
+        if (sumsq_parts) {
+            if (blocks > parts_cap) {
+                snprintf(g_err, kErrLen, "gcc_gin_backward_sumsq: %lld partials, room for %d", (long long)blocks, parts_cap);
+                return -3;
+            }
+            *nparts = (int32_t)blocks;
+        }
+        hipLaunchKernelGGL(gin_grad_final_kernel, dim3((unsigned)blocks), block, 0, s, a);
     }
     prof_mark(prof, 1, s);
     hipError_t e = hipGetLastError();
@@ -1076,4 +1094,24 @@ extern "C" int32_t gcc_gin_backward(const gcc_gin_pass *pass, const float *dfeat
         return -10;
     }
     return 0;
+}
+
+extern "C" int32_t gcc_gin_backward(const gcc_gin_pass *pass, const float *dfeat, const gcc_gin_grads *grads,
+                                    int32_t accumulate, void *workspace, int64_t workspace_bytes,
+                                    int64_t node_cap, gcc_prof *prof, void *stream)
+{
+    return gin_backward_launches(pass, dfeat, grads, accumulate, workspace, workspace_bytes, node_cap, nullptr, 0, nullptr, prof,
+                                 stream);
+}
+
+extern "C" int32_t gcc_gin_backward_sumsq(const gcc_gin_pass *pass, const float *dfeat, const gcc_gin_grads *grads,
+                                          void *workspace, int64_t workspace_bytes, int64_t node_cap, double *sumsq_parts,
+                                          int32_t parts_cap, int32_t *nparts, gcc_prof *prof, void *stream)
+{
+    if (!sumsq_parts || !nparts || parts_cap < 1) {
+        snprintf(g_err, kErrLen, "gcc_gin_backward_sumsq: bad argument");
+        return -1;
+    }
+    return gin_backward_launches(pass, dfeat, grads, 0, workspace, workspace_bytes, node_cap, sumsq_parts, parts_cap, nparts, prof,
+                                 stream);
 }

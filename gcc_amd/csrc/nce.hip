@@ -250,6 +250,200 @@ __global__ __launch_bounds__(kThreads) void nce_slice_kernel(NceDev a)
     }
 }
 
+// Forward AND backward of the MoCo head (pos_mode 0, f32) in ONE pass over the queue -- flash-attention's identity applied to
+// q . queue^T / T.  Per 16-row tile: logits on the MFMA as nce_slice_kernel<false>; the running maximum m of a query is made
+// COMMON to its four lane groups before the tile's exp (in the second MFMA the reduction index runs over those groups, so their
+// p~ = exp(l - m) must share one reference); p~ goes straight into the second MFMA (p~^T x queue rows, the operand identity of
+// nce_slice_kernel<true>) and the accumulators are rescaled by exp(m_old - m_new) whenever the maximum rises.  No assumption
+// about the size of the logits.  Per (slice, query): pm = m, ps = sum p~, slab = sum p~ row (unnormalised; nce_merge_kernel
+// weighs it with exp(pm - lse)).
+__global__ __launch_bounds__(kThreads) void nce_onepass_kernel(NceDev a)
+{
+    TRAIN_STEP_WAVE_PRIORITY();
+    __shared__ float Ms[kChunk * kLd];
+    const int tid = (int)threadIdx.x, lane = lane_id(), wv = tid >> 6, j = lane & 15, q = lane >> 4;
+    const int s = (int)blockIdx.x;
+    if (s == 0 && blockIdx.y == 0 && tid == 0) *a.ticket = 0;      // arrival counter of nce_merge_kernel
+    const int qj = (int)blockIdx.y * kQPerBlock + 16 * wv + j;
+    const bool qvalid = qj < a.B;
+    F4 qf[4];
+    const float *qrow = a.q + (int64_t)(qvalid ? qj : 0) * D;      // (unconditional loads, masked afterwards)
+#pragma unroll
+    for (int c = 0; c < 4; ++c) qf[c] = ld4(qrow + 16 * c + 4 * q);
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {                    // (per component: a select between two F4 objects is a select of addresses -- scratch)
+        qf[c].x = qvalid ? qf[c].x : 0.f; qf[c].y = qvalid ? qf[c].y : 0.f;
+        qf[c].z = qvalid ? qf[c].z : 0.f; qf[c].w = qvalid ? qf[c].w : 0.f;
+    }
+    const int row_beg = s * a.R, row_end = min(a.K, row_beg + a.R);
+    float m = -INFINITY, ssum = 0.f;                 // m: the same value in the four lane groups of a query
+    f32x4 acc2[4];
+#pragma unroll
+    for (int db = 0; db < 4; ++db) { f32x4 z = {0.f, 0.f, 0.f, 0.f}; acc2[db] = z; }
+    F4 nxt[4];
+    auto request = [&](int c0) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const int idx = tid + kThreads * i, row = idx >> 4, c4 = (idx & 15) * 4;
+            nxt[i] = ld4(mem_row_ptr(a, c0 + row) + c4);
+        }
+    };
+    if (row_beg < row_end) request(row_beg);
+    for (int c0 = row_beg; c0 < row_end; c0 += kChunk) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const int idx = tid + kThreads * i, row = idx >> 4, c4 = (idx & 15) * 4;
+            st4(&Ms[row * kLd + c4], finish_mem4(a, nxt[i], c0 + row));
+        }
+        __syncthreads();
+        if (c0 + kChunk < row_end) request(c0 + kChunk);
+        for (int t = 0; t < 4; ++t) {
+            if (c0 + 16 * t >= row_end) break;      // block-uniform
+            f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int c = 0; c < 4; ++c) {
+                const F4 mf = ld4(&Ms[(16 * t + j) * kLd + 16 * c + 4 * q]);
+                acc = mfma_16x16x4_f32(mf.x, qf[c].x, acc);
+                acc = mfma_16x16x4_f32(mf.y, qf[c].y, acc);
+                acc = mfma_16x16x4_f32(mf.z, qf[c].z, acc);
+                acc = mfma_16x16x4_f32(mf.w, qf[c].w, acc);
+            }
+            // acc[r] = mem[row0 + r] . q[qj], row0 = c0 + 16 t + 4 q
+            const int row0 = c0 + 16 * t + 4 * q;
+            float lv[4];
+#pragma unroll
+            for (int r = 0; r < 4; ++r) lv[r] = row0 + r < row_end ? acc[r] * a.inv_T : -INFINITY;
+            float tmax = fmaxf(fmaxf(lv[0], lv[1]), fmaxf(lv[2], lv[3]));
+            tmax = fmaxf(tmax, wave_shfl_xor(tmax, 16));           // the tile's maximum over all 16 rows of the query
+            tmax = fmaxf(tmax, wave_shfl_xor(tmax, 32));
+            const float mn = fmaxf(m, tmax);
+            const float sc = mn > -INFINITY ? expf(m - mn) : 1.f;  // (m = -inf before the first valid row: 0, and acc2 is 0)
+            float p[4];
+#pragma unroll
+            for (int r = 0; r < 4; ++r) p[r] = lv[r] > -INFINITY ? expf(lv[r] - mn) : 0.f;
+            ssum = ssum * sc + ((p[0] + p[1]) + (p[2] + p[3]));
+            m = mn;
+#pragma unroll
+            for (int db = 0; db < 4; ++db) acc2[db] *= sc;
+            // second GEMM: slab[query][d] += p~[row][query] * mem[row][d]; this lane's p~ is the B operand (k = q <-> row
+            // 4q + r, column j = query); the lane's accumulators all belong to query j, whose sc it holds
+#pragma unroll
+            for (int r = 0; r < 4; ++r)
+#pragma unroll
+                for (int db = 0; db < 4; ++db)
+                    acc2[db] = mfma_16x16x4_f32(Ms[(16 * t + 4 * q + r) * kLd + 16 * db + j], p[r], acc2[db]);
+        }
+        __syncthreads();
+    }
+    ssum += wave_shfl_xor(ssum, 16);                 // (one common m: the lane groups' sums simply add)
+    ssum += wave_shfl_xor(ssum, 32);
+    if (qvalid) {
+        if (q == 0) {
+            a.pm[(int64_t)s * a.B + qj] = m;
+            a.ps[(int64_t)s * a.B + qj] = ssum;
+        }
+#pragma unroll
+        for (int db = 0; db < 4; ++db) {
+            F4 o = {acc2[db][0], acc2[db][1], acc2[db][2], acc2[db][3]};
+            st4(a.slabs + ((int64_t)s * a.B + qj) * D + 16 * db + 4 * q, o);
+        }
+    }
+}
+
+// mean loss / mean positive logit by the workgroup that arrives last, in index order (deterministic); every workgroup has
+// written its lse / pos before it calls this
+__device__ __forceinline__ void nce_mean_by_last(const NceDev &a, double *red, int *last)
+{
+    const int tid = (int)threadIdx.x, lane = lane_id(), wv = tid >> 6;
+    device_fence();                                              // lse / pos of this workgroup are visible device wide
+    __syncthreads();
+    if (tid == 0) *last = atomicAdd(a.ticket, 1) == (int)gridDim.x - 1;
+    __syncthreads();
+    if (!*last) return;
+    device_fence();
+    double lsum = 0.0, psum = 0.0;
+    for (int i = tid; i < a.B; i += kThreads) {
+        const float lse = load_fresh(a.lse + i), pos = load_fresh(a.pos + i);
+        lsum += (double)(lse - pos);                             // CrossEntropyLoss row term
+        psum += (double)pos;
+    }
+    lsum = wave_sum(lsum);
+    psum = wave_sum(psum);
+    if (lane == 0) { red[wv] = lsum; red[4 + wv] = psum; }
+    __syncthreads();
+    if (tid == 0) {
+        a.loss[0] = (float)((red[0] + red[1] + red[2] + red[3]) / (double)a.B);    // reduction="mean"
+        a.prob[0] = (float)((red[4] + red[5] + red[6] + red[7]) / (double)a.B);    // out[:, 0].mean(), train.py:394
+        *a.ticket = 0;
+    }
+}
+
+#ifndef NCE_MERGE_BATCH
+#define NCE_MERGE_BATCH 32   // slabs requested per round
+#endif
+// nce_combine_kernel + nce_dq_kernel for nce_onepass_kernel's partials (pos_mode 0): one wave per query.  lse / pos exactly as
+// nce_combine_kernel forms them; then dq[b] = dloss / (B T) * (sum_s exp(pm_s - lse) slab_s[b] + (exp(pos - lse) - 1) k[b]),
+// slabs in slice order (lane = feature dim).  A slice without a valid row (pm = -inf) counts as zero, whatever its slab holds.
+__global__ __launch_bounds__(kThreads) void nce_merge_kernel(NceDev a)
+{
+    TRAIN_STEP_WAVE_PRIORITY();
+    __shared__ double red[8];
+    __shared__ int last;
+    const int tid = (int)threadIdx.x, lane = lane_id(), wv = tid >> 6;
+    const int b = (int)blockIdx.x * (kThreads >> 6) + wv;
+    if (b < a.B) {                                   // wave-uniform
+        // one round trip: the query, the key, the first 64 slices' maxima and sums, dloss and the first batch of slabs
+        const float qv = a.q[(int64_t)b * D + lane], kv = a.k[(int64_t)b * D + lane];
+        const int s0 = min(lane, a.S - 1);
+        const float pm0r = a.pm[(int64_t)s0 * a.B + b], ps0r = a.ps[(int64_t)s0 * a.B + b];
+        const float dl = a.dloss[0];
+        const float *sp = a.slabs + (int64_t)b * D + lane;
+        const int64_t st = (int64_t)a.B * D;
+        float v[NCE_MERGE_BATCH];
+#pragma unroll
+        for (int u = 0; u < NCE_MERGE_BATCH; ++u) v[u] = sp[(int64_t)min(u, a.S - 1) * st];
+        const float pm0 = lane < a.S ? pm0r : -INFINITY;
+        const float pos = wave_sum(qv * kv) * a.inv_T;
+        float m = pm0;
+        for (int s = lane + 64; s < a.S; s += 64) m = fmaxf(m, a.pm[(int64_t)s * a.B + b]);
+        m = fmaxf(wave_max(m), pos);
+        float sum = pm0 > -INFINITY ? ps0r * expf(pm0 - m) : 0.f;
+        for (int s = lane + 64; s < a.S; s += 64) {
+            const float pmv = a.pm[(int64_t)s * a.B + b], psv = a.ps[(int64_t)s * a.B + b];
+            if (pmv > -INFINITY) sum += psv * expf(pmv - m);
+        }
+        sum = wave_sum(sum) + expf(pos - m);
+        const float lse = m + logf(sum);
+        if (lane == 0) {
+            a.lse[b] = lse;
+            a.pos[b] = pos;
+        }
+        float acc = 0.f;
+        for (int base = 0; base < a.S; base += 64) {              // lane l holds the weight of slice base + l
+            float pmv = pm0;
+            if (base > 0) pmv = base + lane < a.S ? a.pm[(int64_t)(base + lane) * a.B + b] : -INFINITY;
+            const float w = pmv > -INFINITY ? expf(pmv - lse) : 0.f;
+            const int send = min(a.S, base + 64);
+            for (int sl = base; sl < send; sl += NCE_MERGE_BATCH) {
+                if (sl > 0) {
+#pragma unroll
+                    for (int u = 0; u < NCE_MERGE_BATCH; ++u) v[u] = sp[(int64_t)min(sl + u, a.S - 1) * st];
+                }
+#pragma unroll
+                for (int u = 0; u < NCE_MERGE_BATCH; ++u) {
+                    if (sl + u < send) {                           // wave-uniform
+                        const float ws = wave_readlane(w, sl + u - base);
+                        if (ws > 0.f) acc = fmaf(ws, v[u], acc);
+                    }
+                }
+            }
+        }
+        const float coef = dl * a.inv_T / (float)a.B;
+        a.dq[(int64_t)b * D + lane] = coef * (acc + (expf(pos - lse) - 1.f) * kv);
+    }
+    nce_mean_by_last(a, red, &last);
+}
+
 __global__ __launch_bounds__(kThreads) void nce_combine_kernel(NceDev a)
 {
     TRAIN_STEP_WAVE_PRIORITY();
@@ -418,6 +612,10 @@ struct AdamExtras {
     float *ema; int64_t n_ema; float ema_m;
     const gcc_step_scalars *sc;      // replayed step: lr and the bias corrections come from here
     double *acc; int32_t *mx; const float *loss, *prob; const int32_t *node_off_q, *edge_off_q, *node_off_k; int32_t B;
+    // gcc_adam_ema_enqueue_step_scalars: the sum of squares as per-workgroup partials of gin_grad_final_kernel (instead of
+    // sumsq[0] of a gradnorm_kernel launch), and the queue's enqueue as workgroups >= adam_blocks of this launch
+    const double *parts; int32_t nparts;
+    float *q_mem; const float *q_keys; int32_t q_K, q_nkeys, adam_blocks;
 };
 
 __global__ __launch_bounds__(kThreads) void adam_kernel(float *p, float *g, float *m, float *v, int64_t n, float lr,
@@ -426,14 +624,46 @@ __global__ __launch_bounds__(kThreads) void adam_kernel(float *p, float *g, floa
                                                         const double *sumsq, float *grad_norm, AdamExtras x)
 {
     TRAIN_STEP_WAVE_PRIORITY();
+    const int nblk = x.q_mem ? x.adam_blocks : (int)gridDim.x;
+    if ((int)blockIdx.x >= nblk) {                             // (block-uniform) queue_enqueue_kernel's rows, ring pointer from the device
+        const int gid = ((int)blockIdx.x - nblk) * kThreads + (int)threadIdx.x;
+        const int i = gid >> 4, c4 = (gid & 15) * 4;
+        if (i >= x.q_nkeys) return;
+        const int row = (x.sc->enqueue_index % x.q_K + i) % x.q_K;                 // torch.fmod(out_ids + index, queueSize)
+        st4(x.q_mem + (int64_t)row * D + c4, ld4(x.q_keys + (int64_t)i * D + c4));
+        return;
+    }
     // grad_scale: the 1 / world of a summed (all-reduced) gradient, folded in here instead of a launch of its own
-    const double ss = sumsq[0];
+    double ss = 0.0;
+    double pv[4] = {0.0, 0.0, 0.0, 0.0};
+    if (x.parts) {                                             // (uniform) the partials: one round trip, with the first element's
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const int idx = (int)threadIdx.x + kThreads * u;
+            pv[u] = x.parts[idx < x.nparts ? idx : x.nparts - 1];
+        }
+    } else {
+        ss = sumsq[0];
+    }
     if (x.sc) { lr = x.sc->lr; bc1 = x.sc->bias_corr1; bc2_sqrt = x.sc->bias_corr2_sqrt; }   // (uniform: one scalar load, in flight with the rest)
     // this thread's first element rides in the same round trip as the norm
-    const int64_t stride = (int64_t)gridDim.x * kThreads, i0 = (int64_t)blockIdx.x * kThreads + threadIdx.x;
+    const int64_t stride = (int64_t)nblk * kThreads, i0 = (int64_t)blockIdx.x * kThreads + threadIdx.x;
     const int64_t ic = i0 < n ? i0 : n - 1;
     float g0 = g[ic], p0 = p[ic], m0 = m[ic], v0 = v[ic];
     const float e0 = x.ema ? x.ema[i0 < x.n_ema ? i0 : x.n_ema - 1] : 0.f;      // (block-uniform branch)
+    if (x.parts) {
+        // every workgroup adds ALL partials up in the same fixed order (thread t: partials t, t + 256, ..; wave tree; waves 0..3):
+        // the same bits in every workgroup, no ticket and no last-arrival pass
+        __shared__ double red[kThreads / 64];
+        double t = 0.0;
+#pragma unroll
+        for (int u = 0; u < 4; ++u) if ((int)threadIdx.x + kThreads * u < x.nparts) t += pv[u];
+        for (int idx = (int)threadIdx.x + 4 * kThreads; idx < x.nparts; idx += kThreads) t += x.parts[idx];
+        t = wave_sum(t);
+        if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = t;
+        __syncthreads();
+        ss = (red[0] + red[1]) + (red[2] + red[3]);
+    }
     const float norm = grad_scale * (float)sqrt(ss);
     float coef = 1.f;
     if (max_norm > 0.f) {                                      // torch.nn.utils.clip_grad_norm_
@@ -575,6 +805,31 @@ int32_t gcc_nce_backward(const gcc_nce_args *a, const float *dloss, int32_t by_m
     return 0;
 }
 
+int32_t gcc_nce_forward_backward(const gcc_nce_args *a, const float *dloss, float *dq, void *workspace,
+                                 int64_t workspace_bytes, gcc_prof *prof_fwd, gcc_prof *prof_bwd, void *stream)
+{
+    NceDev d;
+    Plan pl;
+    int rc = fill_dev(a, workspace, workspace_bytes, d, pl);
+    if (rc) return rc;
+    if (!a->loss || !a->prob || !dloss || !dq) { snprintf(g_err, kErrLen, "gcc_nce_forward_backward: bad argument"); return -1; }
+    if (a->pos_mode != 0 || a->out_dense || d.bf16) {
+        snprintf(g_err, kErrLen, "gcc_nce_forward_backward: pos_mode 0, f32, no dense output (use gcc_nce_forward + gcc_nce_backward)");
+        return -2;
+    }
+    d.dloss = dloss; d.dq = dq;
+    hipStream_t s = (hipStream_t)stream;
+    prof_mark(prof_fwd, 0, s);
+    hipLaunchKernelGGL(nce_onepass_kernel, dim3(pl.S, pl.QB), dim3(kThreads), 0, s, d);
+    prof_mark(prof_fwd, 1, s);
+    prof_mark(prof_bwd, 0, s);
+    hipLaunchKernelGGL(nce_merge_kernel, dim3((d.B + (kThreads >> 6) - 1) / (kThreads >> 6)), dim3(kThreads), 0, s, d);
+    prof_mark(prof_bwd, 1, s);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) { snprintf(g_err, kErrLen, "gcc_nce_forward_backward: %s", hipGetErrorString(e)); return -10; }
+    return 0;
+}
+
 int32_t gcc_queue_enqueue(float *mem, int32_t K, const float *keys, int32_t nkeys, int32_t index, float *saved,
                           void *stream)
 {
@@ -678,10 +933,16 @@ int32_t gcc_adam_step(float *param, float *grad, float *exp_avg, float *exp_avg_
     return hipGetLastError() == hipSuccess ? 0 : -10;
 }
 
+struct AdamFold {            // gcc_adam_ema_enqueue_step_scalars
+    const double *parts; int32_t nparts;
+    float *q_mem; const float *q_keys; int32_t q_K, q_nkeys;
+};
+
 static int32_t adam_ema_launch(const char *who, float *param, float *grad, float *exp_avg, float *exp_avg_sq, int64_t n, float lr,
                                float beta1, float beta2, float eps, float weight_decay, int32_t step, float max_norm,
                                float grad_scale, float *grad_norm, double *scratch, float *ema, int64_t n_ema, float ema_m,
-                               const gcc_step_meters_args *meters, const gcc_step_scalars *scalars, void *stream)
+                               const gcc_step_meters_args *meters, const gcc_step_scalars *scalars, void *stream,
+                               const AdamFold *fold = nullptr)
 {
     if (!param || !grad || !exp_avg || !exp_avg_sq || !grad_norm || !scratch || n < 1 || (!scalars && step < 1) || !(grad_scale > 0.f) ||
         (ema && n_ema < n) ||
@@ -693,7 +954,8 @@ static int32_t adam_ema_launch(const char *who, float *param, float *grad, float
     hipStream_t s = (hipStream_t)stream;
     const float bc1 = scalars ? 1.f : 1.0f - powf(beta1, (float)step);
     const float bc2_sqrt = scalars ? 1.f : sqrtf(1.0f - powf(beta2, (float)step));
-    hipLaunchKernelGGL(gradnorm_kernel, dim3(kNormBlocks), dim3(kThreads), 0, s, (const float *)grad, n, scratch);
+    if (!fold || !fold->parts)
+        hipLaunchKernelGGL(gradnorm_kernel, dim3(kNormBlocks), dim3(kThreads), 0, s, (const float *)grad, n, scratch);
     AdamExtras x = {};
     x.sc = scalars;
     if (ema) { x.ema = ema; x.n_ema = n_ema; x.ema_m = ema_m; }
@@ -705,7 +967,15 @@ static int32_t adam_ema_launch(const char *who, float *param, float *grad, float
     const int64_t nmax = ema ? n_ema : n;
     int blocks = (int)((nmax + kThreads - 1) / kThreads);
     if (blocks > 512) blocks = 512;
-    hipLaunchKernelGGL(adam_kernel, dim3(blocks), dim3(kThreads), 0, s, param, grad, exp_avg, exp_avg_sq, n, lr, beta1,
+    int extra = 0;
+    if (fold) {
+        x.parts = fold->parts; x.nparts = fold->nparts;
+        if (fold->q_mem) {
+            x.q_mem = fold->q_mem; x.q_keys = fold->q_keys; x.q_K = fold->q_K; x.q_nkeys = fold->q_nkeys; x.adam_blocks = blocks;
+            extra = (fold->q_nkeys * 16 + kThreads - 1) / kThreads;
+        }
+    }
+    hipLaunchKernelGGL(adam_kernel, dim3(blocks + extra), dim3(kThreads), 0, s, param, grad, exp_avg, exp_avg_sq, n, lr, beta1,
                        beta2, eps, weight_decay, bc1, bc2_sqrt, max_norm, grad_scale, (const double *)scratch, grad_norm, x);
     return hipGetLastError() == hipSuccess ? 0 : -10;
 }
@@ -727,6 +997,25 @@ int32_t gcc_adam_ema_step_scalars(float *param, float *grad, float *exp_avg, flo
     if (!scalars) { snprintf(g_err, kErrLen, "gcc_adam_ema_step_scalars: scalars is NULL"); return -1; }
     return adam_ema_launch("gcc_adam_ema_step_scalars", param, grad, exp_avg, exp_avg_sq, n, 0.f, beta1, beta2, eps, weight_decay,
                            0, max_norm, grad_scale, grad_norm, scratch, ema, n_ema, ema_m, meters, scalars, stream);
+}
+
+int32_t gcc_adam_ema_enqueue_step_scalars(float *param, float *grad, float *exp_avg, float *exp_avg_sq, int64_t n,
+                                          float beta1, float beta2, float eps, float weight_decay, float max_norm,
+                                          float grad_scale, float *grad_norm, double *scratch, float *ema, int64_t n_ema, float ema_m,
+                                          const gcc_step_meters_args *meters, const gcc_step_scalars *scalars,
+                                          const double *sumsq_parts, int32_t nparts, float *queue, int32_t K, const float *keys,
+                                          int32_t nkeys, void *stream)
+{
+    const char *who = "gcc_adam_ema_enqueue_step_scalars";
+    if (!scalars) { snprintf(g_err, kErrLen, "%s: scalars is NULL", who); return -1; }
+    if ((sumsq_parts && nparts < 1) || (!sumsq_parts && nparts != 0) || (queue && (!keys || K < 1 || nkeys < 1 || nkeys > K)) ||
+        (!sumsq_parts && !queue)) {
+        snprintf(g_err, kErrLen, "%s: bad argument (nparts=%d K=%d n=%d)", who, nparts, K, nkeys);
+        return -1;
+    }
+    const AdamFold fold = {sumsq_parts, nparts, queue, keys, K, nkeys};
+    return adam_ema_launch(who, param, grad, exp_avg, exp_avg_sq, n, 0.f, beta1, beta2, eps, weight_decay, 0, max_norm, grad_scale,
+                           grad_norm, scratch, ema, n_ema, ema_m, meters, scalars, stream, &fold);
 }
 
 int32_t gcc_step_meters(double *acc, int32_t *mx, const float *loss, const float *prob, const float *grad_norm,

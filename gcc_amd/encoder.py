@@ -320,12 +320,20 @@ class GinEngine:
         key, gen = buf["_slot"]
         return self._gen.get(key) == gen
 
-    def forward(self, passes, stream=None, prof=None):
+    def forward(self, passes, stream=None, prof=None, fetch=None):
+        """``fetch`` = (scalars, ring, ring_len, counter): the step's scalars fetch inside the first kernel
+        (gcc_gin_forward_fetch) instead of a launch of its own in front of this call."""
         arr = (_cabi.GccGinPass * len(passes))(*passes)
+        if fetch is not None:
+            scalars, ring, ring_len, counter = fetch
+            rc = self.lib.gcc_gin_forward_fetch(arr, len(passes), self.ptr(scalars), ring.data_ptr(), int(ring_len),
+                                                self.ptr(counter), prof.handle if prof is not None else None, stream)
+            if rc != 0:
+                raise RuntimeError(f"gcc_gin_forward_fetch failed ({rc}): {self.lib.gcc_last_error().decode()}")
+            return
         rc = self.lib.gcc_gin_forward(arr, len(passes), prof.handle if prof is not None else None, stream)
         if rc != 0:
             raise RuntimeError(f"gcc_gin_forward failed ({rc}): {self.lib.gcc_last_error().decode()}")
-
 
     def eval_fused(self, passes, mean_out=None, stream=None):
         """gcc_gin_eval_fused: eval-mode passes (running statistics) as one launch, one workgroup per subgraph; with
@@ -335,9 +343,11 @@ class GinEngine:
         if rc != 0:
             raise RuntimeError(f"gcc_gin_eval_fused failed ({rc}): {self.lib.gcc_last_error().decode()}")
 
-    def backward(self, enc, p, buf, dfeat, targets=None, accumulate=False, stream=None, prof=None):
+    def backward(self, enc, p, buf, dfeat, targets=None, accumulate=False, stream=None, prof=None, sumsq=None):
         """Backward of a training-mode pass.  Gradients are written (or added, ``accumulate``) into
-        ``targets`` (tensors in :func:`grad_params` order); by default into each ``param.grad``."""
+        ``targets`` (tensors in :func:`grad_params` order); by default into each ``param.grad``.
+        ``sumsq``: a float64 device tensor that receives the per-workgroup partial sums of squares of the stored gradient
+        (gcc_gin_backward_sumsq; not with ``accumulate``) -- the call then returns (targets, number of partials)."""
         ptr = self.ptr
         L = len(enc.gnn.ginlayers)
         g = buf["_keepalive"][0]
@@ -361,6 +371,16 @@ class GinEngine:
             else:
                 getattr(grads, name)[idx] = ptr(tgt)
         dfeat = dfeat.contiguous()
+        if sumsq is not None:
+            if accumulate:
+                raise ValueError("sumsq: the partial sums are of what ONE backward pass stores (accumulate=False)")
+            nparts = ctypes.c_int32(0)
+            rc = self.lib.gcc_gin_backward_sumsq(ctypes.byref(p), ptr(dfeat), ctypes.byref(grads), ptr(ws), nbytes, node_cap,
+                                                 ptr(sumsq), sumsq.numel(), ctypes.byref(nparts),
+                                                 prof.handle if prof is not None else None, stream)
+            if rc != 0:
+                raise RuntimeError(f"gcc_gin_backward_sumsq failed ({rc}): {self.lib.gcc_last_error().decode()}")
+            return targets, nparts.value
         rc = self.lib.gcc_gin_backward(ctypes.byref(p), ptr(dfeat), ctypes.byref(grads), int(accumulate),
                                        ptr(ws), nbytes, node_cap, prof.handle if prof is not None else None, stream)
         if rc != 0:

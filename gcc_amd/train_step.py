@@ -328,9 +328,12 @@ class FlatAdam:
         self.steps = 0
         self.grad_norm = torch.zeros(1, dtype=torch.float32, device=param.device)
         self._scratch = torch.zeros(64, dtype=torch.float64, device=param.device)
+        self.sumsq_parts = torch.zeros(4096, dtype=torch.float64, device=param.device)     # gin_grad_final's partials (folded step)
 
-    def step(self, grad_scale=1.0, ema=None, ema_src=None, ema_m=0.0, meters=None, scalars=None):
-        """``grad_scale``: 1 / world when ``grad`` holds the SUM over ranks (folded into the two launches).
+    def step(self, grad_scale=1.0, ema=None, ema_src=None, ema_m=0.0, meters=None, scalars=None, sumsq_parts=None, enqueue=None):
+        """``sumsq_parts`` = (partials, count) left by the backward's last kernel instead of a sum-of-squares launch, ``enqueue`` =
+        (queue, keys) copied by extra workgroups of the Adam launch: both with ``scalars`` only (the single-GPU MoCo step).
+        ``grad_scale``: 1 / world when ``grad`` holds the SUM over ranks (folded into the two launches).
         ``ema`` / ``ema_src`` / ``ema_m``: moment_update of the flat EMA buffer from the flat parameter buffer
         (``param`` is its live prefix); ``meters`` = (acc, mx, loss, prob, graph_q, graph_k): one step of the
         device-side meters -- both inside the Adam launch (gcc_adam_ema_step) instead of launches of their own."""
@@ -344,7 +347,8 @@ class FlatAdam:
         else:
             self.engine.adam_ema(self.param, self.grad, self.exp_avg, self.exp_avg_sq, g["lr"], g["betas"], g["eps"],
                                  g["weight_decay"], self.steps, self.clip_norm, self.grad_norm, self._scratch, stream=st,
-                                 grad_scale=grad_scale, ema=ema, ema_src=ema_src, ema_m=ema_m, meters=meters, scalars=scalars)
+                                 grad_scale=grad_scale, ema=ema, ema_src=ema_src, ema_m=ema_m, meters=meters, scalars=scalars,
+                                 **(dict(sumsq_parts=sumsq_parts, enqueue=enqueue) if sumsq_parts is not None or enqueue is not None else {}))
         return self.grad_norm
 
     def zero_grad(self):
@@ -578,12 +582,22 @@ class MoCoTrainStep(_GraphedStep):
     def __init__(self, model: GraphEncoder, model_ema: GraphEncoder, contrast: MemoryMoCo, sampler, posemb,
                  learning_rate=0.005, betas=(0.9, 0.999), weight_decay=1e-5, clip_norm=1.0, alpha=0.999,
                  world_size=1, rank=0, prefetch=True, extra_lanes=(), depth=2, lanes=None, chunk=1, reserved_cus=0, cu_layout="interleaved",
-                 collectives=None, ahead=None, graph=None, flat_engine=None):
+                 collectives=None, ahead=None, graph=None, flat_engine=None, fold=None, onepass_head=None):
         """``sampler``/``posemb``: producer lane 0; ``extra_lanes``: more (sampler, posemb) pairs with their own
         workspaces for multi-stream prefetch (see :class:`BatchProducer`).
         ``graph``: replay the step's ~45 launches as ONE captured hipGraph per ring slot (default: on with prefetch on a
-        device, off with collectives -- see :meth:`_step`)."""
+        device, off with collectives -- see :meth:`_step`).
+        ``fold``: the folded launches of the 64-channel step that compute what the separate ones compute -- the scalars fetch
+        inside the step's first kernel, the clip's sum of squares inside the backward's last kernel, the enqueue inside the Adam
+        launch (default: on; ``GCC_STEP_FOLD=0`` or ``fold=False`` selects the separate launches: the A/B switch of
+        profiles/step_fold_bench_ab.txt).
+        ``onepass_head``: the head as one pass over the queue (gcc_nce_forward_backward, two launches instead of four).  OFF
+        unless asked for (``GCC_STEP_ONEPASS_HEAD=1``): it adds the same terms in another order, d loss / d q moves by ~1e-7
+        relative, and Adam turns that into visibly different weights within a few steps -- a training run is no
+        longer the run the four launches give."""
         self.model, self.ema, self.contrast = model, model_ema, contrast
+        self.fold = (os.environ.get("GCC_STEP_FOLD", "1") != "0") if fold is None else bool(fold)
+        self.onepass_head = (os.environ.get("GCC_STEP_ONEPASS_HEAD", "0") == "1") if onepass_head is None else bool(onepass_head)
         self.sampler, self.posemb = sampler, posemb
         self.clip_norm, self.alpha = clip_norm, alpha
         self.world, self.rank = world_size, rank
@@ -836,26 +850,41 @@ class MoCoTrainStep(_GraphedStep):
             return self._body_wide(q, k, keep, S, st)
 
         def fwd():
-            self._fetch_scalars(scalars, st)
+            fetch = None
+            if self.fold and scalars is not None:      # the fetch rides in the forward's first kernel
+                fetch = (scalars, self.ring, self.ring_len, self.ring_counter)
+            else:
+                self._fetch_scalars(scalars, st)
             # (with scalars the by-value seed is an addend to the device-resident one: 0 here)
             S["pq"], S["bufq"] = self.gin.make_pass(self.model, q, training=True, keep=keep, slot=("step", 0),
                                                     dropout_seed=(0 if seed is not None else None) if scalars is not None else seed,
                                                     scalars=scalars)
             S["pk"], S["bufk"] = self.gin.make_pass(self.ema, k, training=True, keep=None, slot=("step", 1), backward=False)
-            self.gin.forward([S["pq"], S["pk"]], stream=st, prof=pr.get("gin_fwd"))      # train.py:389-391
+            self.gin.forward([S["pq"], S["pk"]], stream=st, prof=pr.get("gin_fwd"), fetch=fetch)      # train.py:389-391
 
         def gather_begin():                    # RCCL, overlapped with everything up to the enqueue
             S["gathering"] = self._all_gather_begin(self.keys_all, S["bufk"]["feat"])
 
         def head_and_backward():
             feat_q, feat_k = S["bufq"]["feat"], S["bufk"]["feat"]
-            S["outs"] = self.nce.forward(feat_q, feat_k, c.kernel_memory(), c.T, 0, stream=st, prof=pr.get("nce_fwd"))   # train.py:393,407
+            mem = c.kernel_memory()
             # The enqueue (memory_moco.py:55-61) is the LAST thing the step does with the queue: logits and their backward
             # are taken against the queue before the update (the reference clones it, memory_moco.py:31), so deferring the
             # update is the same computation -- and it takes the key all-gather off the critical chain.
-            dq = self.nce.backward(feat_q, feat_k, c.kernel_memory(), c.T, 0, S["outs"], self.one, stream=st,
-                                   prof=pr.get("nce_bwd"))                    # loss.backward(), train.py:408
-            self.gin.backward(self.model, S["pq"], S["bufq"], dq, targets=self.grad_views, stream=st, prof=pr.get("gin_bwd"))
+            if self.onepass_head:            # loss and d loss / d q in one pass over the queue (two launches; bf16 keeps the four)
+                S["outs"], dq = self.nce.forward_backward(feat_q, feat_k, mem, c.T, self.one, stream=st,
+                                                          prof_fwd=pr.get("nce_fwd"), prof_bwd=pr.get("nce_bwd"))
+            else:
+                S["outs"] = self.nce.forward(feat_q, feat_k, mem, c.T, 0, stream=st, prof=pr.get("nce_fwd"))   # train.py:393,407
+                dq = self.nce.backward(feat_q, feat_k, mem, c.T, 0, S["outs"], self.one, stream=st,
+                                       prof=pr.get("nce_bwd"))                    # loss.backward(), train.py:408
+            if self.fold and scalars is not None and not self.collectives:
+                # nothing touches the gradient between the backward's last kernel and Adam: its sum of squares is taken there
+                _, n = self.gin.backward(self.model, S["pq"], S["bufq"], dq, targets=self.grad_views, stream=st,
+                                         prof=pr.get("gin_bwd"), sumsq=self.optimizer.sumsq_parts)
+                S["sumsq"] = (self.optimizer.sumsq_parts, n)
+            else:
+                self.gin.backward(self.model, S["pq"], S["bufq"], dq, targets=self.grad_views, stream=st, prof=pr.get("gin_bwd"))
 
         def reduce_and_join():
             self._all_reduce(self.flat_grad)                             # SUM of one flat bucket (248 KiB) over xGMI
@@ -866,6 +895,11 @@ class MoCoTrainStep(_GraphedStep):
             # ... moment_update (train.py:430-431) and train.py:418-428's meters ride in the Adam launch: the meters read
             # this batch's offsets BEFORE its ring slot is handed back
             outs = S["outs"]
+            if "sumsq" in S:                 # the folded single-GPU tail: norm from the partials, enqueue inside the Adam launch
+                S["gnorm"] = self.optimizer.step(ema=self.flat_ema, ema_src=self.flat, ema_m=self.alpha,
+                                                 meters=(self.meter_acc, self.meter_max, outs["loss"], outs["prob"], q, k),
+                                                 scalars=scalars, sumsq_parts=S["sumsq"], enqueue=(c.kernel_memory(), S["bufk"]["feat"]))
+                return
             S["gnorm"] = self.optimizer.step(grad_scale=1.0 / self.world if self.collectives else 1.0,
                                              ema=self.flat_ema, ema_src=self.flat, ema_m=self.alpha,
                                              meters=(self.meter_acc, self.meter_max, outs["loss"], outs["prob"], q, k),

@@ -359,6 +359,13 @@ typedef struct gcc_gin_pass {    /* one encoder invocation on one batched graph 
 /* Runs `npass` independent passes (e.g. query with model, key with model_ema)
  * in the same launches.  prof marks: 0 before, 1 after. */
 int32_t gcc_gin_forward(const gcc_gin_pass *passes, int32_t npass, gcc_prof *prof, void *stream);
+/* gcc_step_scalars_fetch + gcc_gin_forward without the fetch's launch: one thread of the forward's FIRST kernel copies ring
+ * entry (*counter mod ring_len) into `dev` and increments the counter -- the same loads, the same count, once per call.  No
+ * kernel of that first launch reads `dev`; the forward's readout (dropout key) and everything after it see the new entry.
+ * An E2E step uses it for the first of its two forward calls only. */
+int32_t gcc_gin_forward_fetch(const gcc_gin_pass *passes, int32_t npass, gcc_step_scalars *dev,
+                              const gcc_step_scalars *ring, int32_t ring_len, unsigned long long *counter,
+                              gcc_prof *prof, void *stream);
 
 /* The eval-mode forward as ONE call (generate.py:33-53: model.eval(); feat_q = model(graph_q); feat_k = model(graph_k);
  * emb = (feat_q + feat_k) / 2): a workgroup carries a subgraph -- or a run of up to four subgraphs of at most 64 nodes --
@@ -394,6 +401,15 @@ int64_t gcc_gin_backward_workspace_bytes(int64_t node_cap, int32_t batch_size, i
 int32_t gcc_gin_backward(const gcc_gin_pass *pass, const float *dfeat, const gcc_gin_grads *grads,
                          int32_t accumulate, void *workspace, int64_t workspace_bytes, int64_t node_cap,
                          gcc_prof *prof, void *stream);
+
+/* gcc_gin_backward (accumulate = 0) whose last kernel also leaves the sum of squares of every gradient element it stored, as
+ * `*nparts` fp64 partials (one per workgroup of that kernel, <= parts_cap or the call is refused with -3) in sumsq_parts --
+ * the input of gcc_adam_ema_enqueue_step_scalars, which then needs no pass of its own over the gradient for the clip's norm.
+ * The partials add up to the squared norm of the caller's flat gradient buffer if every element of that buffer is either a
+ * target of `grads` or zero (zero-padded blocks of a hidden width below 64 are stored in full). */
+int32_t gcc_gin_backward_sumsq(const gcc_gin_pass *pass, const float *dfeat, const gcc_gin_grads *grads, void *workspace,
+                               int64_t workspace_bytes, int64_t node_cap, double *sumsq_parts, int32_t parts_cap,
+                               int32_t *nparts, gcc_prof *prof, void *stream);
 
 /* ------------------------------------- GIN encoder at any width (training) ---
  * The same encoder -- GraphEncoder(gnn_model="gin").forward, graph_encoder.py:132-200 -> gin.py:213-232 -- for hidden /
@@ -535,6 +551,14 @@ int32_t gcc_nce_forward(const gcc_nce_args *a, void *workspace, int64_t workspac
  * call it with q/mem swapped; p is then normalised with lse[mem row] (args->lse has K entries). */
 int32_t gcc_nce_backward(const gcc_nce_args *a, const float *dloss, int32_t by_mem_row, float *dq,
                          void *workspace, int64_t workspace_bytes, gcc_prof *prof, void *stream);
+/* gcc_nce_forward + gcc_nce_backward of the MoCo head (pos_mode 0, GCC_NCE_F32, out_dense NULL; anything else is refused
+ * with -2) as TWO launches instead of four, with ONE pass over the queue: the slice kernel keeps a running maximum per
+ * query and feeds exp(logit - maximum) straight into the second product, rescaling its accumulators when the maximum
+ * rises; the merge kernel forms lse / pos / loss / prob as gcc_nce_forward does and
+ * dq[b] = dloss / (B T) * (sum_s exp(pm_s - lse) slab_s[b] + (p_b,pos - 1) k_b), slabs in slice order.  Same workspace;
+ * same results up to summation order.  prof_fwd marks 0 / 1 bracket the slice launch, prof_bwd's the merge launch. */
+int32_t gcc_nce_forward_backward(const gcc_nce_args *a, const float *dloss, float *dq, void *workspace,
+                                 int64_t workspace_bytes, gcc_prof *prof_fwd, gcc_prof *prof_bwd, void *stream);
 
 /* memory.index_copy_(0, (arange(n) + index) % K, keys) of memory_moco.py:55-61; when saved != NULL
  * the overwritten rows are first copied there (the `patch` of gcc_nce_args). */
@@ -586,6 +610,18 @@ int32_t gcc_adam_ema_step_scalars(float *param, float *grad, float *exp_avg, flo
                                   const gcc_step_meters_args *meters, const gcc_step_scalars *scalars, void *stream);
 int32_t gcc_queue_enqueue_scalars(float *mem, int32_t K, const float *keys, int32_t nkeys,
                                   const gcc_step_scalars *scalars, void *stream);
+/* The tail of a single-GPU MoCo step as ONE launch: gcc_adam_ema_step_scalars with
+ *  - sumsq_parts / nparts (NULL / 0: the separate sum-of-squares launch stays): the partials of gcc_gin_backward_sumsq, valid
+ *    when nothing touched the gradient since (no all-reduce, no accumulation); every workgroup adds them up in one fixed order,
+ *    so grad_norm equals gcc_adam_ema_step_scalars' to fp64 reordering;
+ *  - queue / K / keys / nkeys (queue NULL: none): gcc_queue_enqueue_scalars' copies as extra workgroups of the Adam launch.
+ * At least one of the two must be given.  The clipped gradient is left in `grad` and grad_norm[0] written as before. */
+int32_t gcc_adam_ema_enqueue_step_scalars(float *param, float *grad, float *exp_avg, float *exp_avg_sq, int64_t n,
+                                          float beta1, float beta2, float eps, float weight_decay, float max_norm,
+                                          float grad_scale, float *grad_norm, double *scratch, float *ema, int64_t n_ema, float ema_m,
+                                          const gcc_step_meters_args *meters, const gcc_step_scalars *scalars,
+                                          const double *sumsq_parts, int32_t nparts, float *queue, int32_t K, const float *keys,
+                                          int32_t nkeys, void *stream);
 
 /* ------------------------------------------------------- fine-tuning head ---
  * train.py --finetune (train_finetune / test_finetune of the reference, train.py:175-337): output_layer = nn.Linear(D, C),
