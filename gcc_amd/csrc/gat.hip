@@ -815,8 +815,15 @@ int check_weights(const char *who, const gcc_gat_weights *w)
 
 int check_pass(const char *who, const gcc_gat_pass *p, const Dims &d)
 {
-    if (!p || !p->node_off || !p->row_ptr || !p->col_idx || !p->saved || !p->out || (d.pos > 0 && !p->pos)) {
-        snprintf(g_err, kErrLen, "%s: NULL pass member", who);
+    const char *missing = !p ? "the pass itself"
+                          : !p->node_off ? "node_off"
+                          : !p->row_ptr ? "row_ptr"
+                          : !p->col_idx ? "col_idx (an edge-free batch still passes one placeholder element)"
+                          : !p->saved ? "saved"
+                          : !p->out ? "out"
+                          : (d.pos > 0 && !p->pos) ? "pos" : nullptr;
+    if (missing) {
+        snprintf(g_err, kErrLen, "%s: NULL pass member: %s", who, missing);
         return -1;
     }
     return 0;

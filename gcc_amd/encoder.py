@@ -208,7 +208,14 @@ class GatEngine:
         out = torch.empty(g.batch_size, enc.output_dim, dtype=torch.float32, device=dev)
         p = _cabi.GccGatPass()
         ptr = self.ptr
-        p.node_off, p.row_ptr, p.col_idx = ptr(g.node_off), ptr(g.row_ptr), ptr(g.col_idx)
+        col_idx = g.col_idx
+        if col_idx.numel() == 0:
+            # an edge-free batch (isolated nodes, empty graphs): every row is empty, so the kernels never read col_idx, but
+            # an empty tensor's data pointer is null and the C side refuses a null member (it cannot tell this batch from
+            # one with live entries without a sync).  One placeholder element stands in for it.
+            col_idx = torch.zeros(1, dtype=torch.int32, device=dev)
+        p.node_off, p.row_ptr, p.col_idx = ptr(g.node_off), ptr(g.row_ptr), ptr(col_idx)
+        p._col_idx = col_idx            # the struct holds a raw pointer that the backward reads too: it lives as long as p
         seed_local = getattr(g, "seed_local", None)
         p.seed_local = ptr(seed_local) if seed_local is not None else None
         p.pos = ptr(g.pos_undirected)
@@ -445,6 +452,9 @@ class GraphEncoder(nn.Module):
         if node_input_dim > H:
             raise NotImplementedError(f"the GAT kernels take input features up to {H} columns (positional + degree "
                                       f"embedding + 1 = {node_input_dim})")
+        if deg_emb < 1:
+            raise NotImplementedError(f"degree_embedding_size={deg_emb}: the GAT kernels read a degree embedding of at least "
+                                      "one column (train.py:617 always passes degree_input=True)")
         if not 1 <= num_layers <= _cabi.GAT_MAX_LAYERS or not 1 <= num_layer_set2set <= _cabi.GAT_MAX_S2S_LAYERS \
                 or num_step_set2set < 1:
             raise NotImplementedError(f"the GAT kernels serve 1..{_cabi.GAT_MAX_LAYERS} GAT layers, 1.."

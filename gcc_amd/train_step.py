@@ -13,6 +13,7 @@ each; ``state_dict()`` is unaffected.
 """
 from __future__ import annotations
 
+import gc
 import os
 import time
 
@@ -499,11 +500,21 @@ class _GraphedStep:
                 # (GCC_CAPTURE_MODE=relaxed was tried against the invalidated captures of the collectives path: no difference,
                 #  2 of 6 runs died either way -- see _drain_collectives)
                 mode = os.environ.get("GCC_CAPTURE_MODE") or "thread_local"
-                gobj.capture_begin(capture_error_mode=mode, **({} if pool is None else dict(pool=pool)))
+                # No cyclic garbage collection between capture_begin and capture_end: a collection that an allocation of
+                # fn() happens to trigger runs the destructors of whatever unreachable cycles the process holds by then
+                # (an earlier trainer's graphs, events, streams, pinned buffers), and their runtime calls on a thread that
+                # is capturing abort the process.  The garbage waits for the first collection after the capture.
+                gc_was_on = gc.isenabled()
+                gc.disable()
                 try:
-                    fn()
+                    gobj.capture_begin(capture_error_mode=mode, **({} if pool is None else dict(pool=pool)))
+                    try:
+                        fn()
+                    finally:
+                        gobj.capture_end()
                 finally:
-                    gobj.capture_end()
+                    if gc_was_on:
+                        gc.enable()
                 pool = pool or gobj.pool()
                 items.append(gobj)
             cap = result()

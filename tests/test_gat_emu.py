@@ -84,6 +84,12 @@ def test_gat_refuses_unsupported_widths(bad):
         gat_encoder(**bad)
 
 
+def test_degree_embedding_size_zero_is_refused_at_construction():
+    """the kernels read a degree embedding; a model without one used to fail at its first forward ("a weight pointer is NULL")"""
+    with pytest.raises(NotImplementedError, match="degree_embedding_size"):
+        gat_encoder(deg_emb=0)
+
+
 def test_mpnn_is_refused_with_the_supported_list():
     from gcc_amd.encoder import GraphEncoder
 
