@@ -122,7 +122,8 @@ class GccGinxPass(ctypes.Structure):          # gcc_ginx_pass: the encoder at an
         ("batch_size", ctypes.c_int32), ("training", ctypes.c_int32), ("update_running_stats", ctypes.c_int32),
         ("normalize", ctypes.c_int32),
         ("dropout_keep", _VP),
-        ("hidden", ctypes.c_int32), ("out_dim", ctypes.c_int32), ("edge_multiplicity", ctypes.c_int32), ("reserved_", ctypes.c_int32),
+        ("hidden", ctypes.c_int32), ("out_dim", ctypes.c_int32), ("edge_multiplicity", ctypes.c_int32),
+        ("gemm_dtype", ctypes.c_int32),       # 0: f32, 1: bf16 operands of the per-node Linears (GEMM_DTYPES)
         ("node_cap", ctypes.c_int64),
         ("w", GccGinWeights),
         ("workspace", _VP), ("workspace_bytes", ctypes.c_int64),
@@ -185,6 +186,7 @@ class GccClsHeadArgs(ctypes.Structure):      # gcc_cls_head_args: the fine-tunin
 CLS_HEAD_MAX_CLASSES = 64
 CLS_HEAD_MAX_DIM = 256
 
+GEMM_DTYPES = {"f32": 0, "bf16": 1}      # gcc_ginx_pass.gemm_dtype / gcc_ncex_forward_dt
 ABI_VERSION = 3          # GCC_AMD_ABI_VERSION of the include/gcc_amd.h these structs mirror (checked in load())
 GRAPH_CONTRACT_CHECKED = 1   # gcc_graph.flags
 
@@ -278,6 +280,8 @@ SIGNATURES = {
     "gcc_ginx_backward": (ctypes.c_int32, [ctypes.POINTER(GccGinxPass), ctypes.c_void_p, ctypes.POINTER(GccGinGrads), ctypes.c_void_p]),
     "gcc_ncex_forward": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
                                           ctypes.c_float, ctypes.c_int32] + [ctypes.c_void_p] * 8),
+    "gcc_ncex_forward_dt": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
+                                             ctypes.c_float, ctypes.c_int32] + [ctypes.c_void_p] * 7 + [ctypes.c_int32, ctypes.c_void_p]),
     "gcc_queue_enqueue_x": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32,
                                              ctypes.c_void_p]),
     "gcc_ginw_forward": (ctypes.c_int32, [ctypes.POINTER(GccGinwArgs), ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),

@@ -254,9 +254,12 @@ class WideNceEngine:
     """The head at feature sizes above 64 (csrc/ginx.hip: gcc_ncex_forward / gcc_queue_enqueue_x): dense logits, and the
     gradient of the loss taken in the forward call -- against the queue before the step's keys overwrite rows of it."""
 
-    def __init__(self, lib=None, ptr=None):
+    def __init__(self, lib=None, ptr=None, dtype="f32"):
         self.lib = lib if lib is not None else _cabi.load()
         self.ptr = ptr if ptr is not None else _cabi.dev_ptr
+        if dtype not in _cabi.GEMM_DTYPES:
+            raise ValueError(f"dtype={dtype!r}: the any-size head's products take {sorted(_cabi.GEMM_DTYPES)} operands")
+        self.dtype = dtype            # "f32": parity mode (gcc_ncex_forward); "bf16": operands of the three dense products rounded to bf16
 
     def forward(self, rows, k, mem, T, mode, stream=None):
         """mode 0: MoCo (rows = q, k = keys, mem = queue [K, D]); mode 1: in-batch (rows = feat_k, mem = feat_q).
@@ -268,12 +271,16 @@ class WideNceEngine:
         o = dict(out=torch.empty(B, ncols, **f32), dlog=torch.empty(B, ncols, **f32), grad_rows=torch.empty(B, D, **f32),
                  grad_mem=torch.empty(K, D, **f32) if mode == 1 else None, loss=torch.empty(1, **f32), prob=torch.empty(1, **f32),
                  acc=torch.zeros(2 + B * D, dtype=torch.float64, device=rows.device))     # [2] loss / prob sums + [B, D] accumulator of grad_rows
-        rc = self.lib.gcc_ncex_forward(self.ptr(rows), self.ptr(k) if k is not None else None, self.ptr(mem), B, K, D, 1.0 / T, mode,
-                                       self.ptr(o["out"]), self.ptr(o["dlog"]), self.ptr(o["grad_rows"]),
-                                       self.ptr(o["grad_mem"]) if o["grad_mem"] is not None else None, self.ptr(o["loss"]),
-                                       self.ptr(o["prob"]), self.ptr(o["acc"]), stream)
+        args = (self.ptr(rows), self.ptr(k) if k is not None else None, self.ptr(mem), B, K, D, 1.0 / T, mode,
+                self.ptr(o["out"]), self.ptr(o["dlog"]), self.ptr(o["grad_rows"]),
+                self.ptr(o["grad_mem"]) if o["grad_mem"] is not None else None, self.ptr(o["loss"]),
+                self.ptr(o["prob"]), self.ptr(o["acc"]))
+        if self.dtype == "f32":
+            rc, who = self.lib.gcc_ncex_forward(*args, stream), "gcc_ncex_forward"
+        else:
+            rc, who = self.lib.gcc_ncex_forward_dt(*args, _cabi.GEMM_DTYPES[self.dtype], stream), "gcc_ncex_forward_dt"
         if rc != 0:
-            raise RuntimeError(f"gcc_ncex_forward failed ({rc}): {self.lib.gcc_last_error().decode()}")
+            raise RuntimeError(f"{who} failed ({rc}): {self.lib.gcc_last_error().decode()}")
         return o
 
     def enqueue(self, mem, keys, index, stream=None):
@@ -326,10 +333,10 @@ class MemoryMoCo(nn.Module):
             raise ValueError("feature size must be positive")
         # up to 64: the fused head of csrc/nce.hip (narrower than 64: zero-padded, exactly); above: the dense any-size head of
         # csrc/ginx.hip (--hidden-size above 64, train.py:93,627-629)
+        # (nce_dtype "bf16": the bf16-operand kernels of csrc/nce.hip up to 64, gcc_ncex_forward_dt above)
         self.wide = inputSize > D
-        if self.wide and nce_dtype != "f32":
-            raise NotImplementedError(f"nce_dtype={nce_dtype!r} is the 64-channel head's throughput mode (csrc/nce.hip); the any-size head "
-                                      f"(feature size {inputSize} > {D}) computes in f32 -- drop --nce-dtype or use --hidden-size <= {D}")
+        if nce_dtype not in _cabi.GEMM_DTYPES:
+            raise ValueError(f"nce_dtype={nce_dtype!r}: expected one of {sorted(_cabi.GEMM_DTYPES)}")
         if not use_softmax:
             raise NotImplementedError("train.py:628 always passes use_softmax=True (the exp/Z branch is dead)")
         self.outputSize = outputSize
@@ -347,7 +354,7 @@ class MemoryMoCo(nn.Module):
 
     def engine(self):
         if self._engine is None:
-            self._engine = WideNceEngine() if self.wide else NceEngine(dtype=self.nce_dtype)
+            self._engine = WideNceEngine(dtype=self.nce_dtype) if self.wide else NceEngine(dtype=self.nce_dtype)
         return self._engine
 
     # ---- feature sizes below 64 (--hidden-size): the kernels' rows are 64 floats.  The ``memory`` buffer keeps the
@@ -429,10 +436,11 @@ class NCESoftmaxLossNS(nn.Module):
         raise TypeError("NCESoftmaxLossNS expects the NCELogits returned by gcc_amd.contrast.e2e_logits")
 
 
-def e2e_logits(feat_q, feat_k, T, engine=None):
-    """``torch.matmul(feat_k, feat_q.t()) / T`` of train.py:400, fused with its loss."""
+def e2e_logits(feat_q, feat_k, T, engine=None, nce_dtype="f32"):
+    """``torch.matmul(feat_k, feat_q.t()) / T`` of train.py:400, fused with its loss.  ``nce_dtype``: the operands of the any-size head's
+    default engine (``--nce-dtype`` above 64 features); an ``engine`` passed in carries its own."""
     if feat_q.shape[1] > D:                        # --hidden-size above 64: the dense any-size head (csrc/ginx.hip)
-        eng = engine if engine is not None else WideNceEngine()
+        eng = engine if engine is not None else WideNceEngine(dtype=nce_dtype)
         fq, fk = feat_q.contiguous(), feat_k.contiguous()
         o = eng.forward(fk.detach(), None, fq.detach(), T, 1, stream=_stream(fq))      # rows = feat_k, columns = feat_q
         loss = _WideLoss.apply(fk, fq, o)

@@ -1,5 +1,7 @@
 // gcc_amd/csrc/ginx.hip -- the GIN encoder at ANY hidden / output width, training mode included: forward with batch
-// statistics and the full backward, fp32 on the matrix cores (v_mfma_f32_16x16x4_f32).  `--hidden-size` is part of the
+// statistics and the full backward, fp32 on the matrix cores (v_mfma_f32_16x16x4_f32) -- or, opt-in per pass
+// (gcc_ginx_pass.gemm_dtype = 1, `--encoder-dtype bf16`), the per-node Linears and their two gradients with bf16 operands
+// on v_mfma_f32_16x16x32_bf16 (ginx_gemm_bf16_kernel below states the rule).  `--hidden-size` is part of the
 // reference's flag surface (train.py:93; GraphEncoder node_hidden_dim / output_dim, graph_encoder.py:44-63); the fused
 // 64-channel kernels of encoder.hip / encoder_bwd.hip serve widths up to 64 (zero-padded, exact), this file serves the
 // rest.  Reference arithmetic, statement by statement:
@@ -163,6 +165,131 @@ __global__ __launch_bounds__(kGT) void ginx_gemm_kernel(GemmArgs g)
                     float v = acc[i][j][r] * g.alpha;
                     if (g.bias && (g.rows_dim < 2 || blockIdx.z == 0)) v += g.bias[n];
                     if (g.atomic) atomicAdd(g.Cd + (int64_t)m * g.ldc + n, (double)v); else g.C[(int64_t)m * g.ldc + n] = v;
+                }
+            }
+}
+
+// ---- the same product with bf16 OPERANDS (gemm_dtype 1; `--encoder-dtype bf16`, `--nce-dtype bf16` above 64 features):
+//     C[m][n] (+)= alpha * sum_k bf16(A(m, k)) * bf16(B(k, n)) [+ bias[n]]
+// bf16() rounds to nearest even (pack2_bf16: the integer formula of f32_to_bf16_bits), the products are exact in fp32 and are
+// summed in fp32 on v_mfma_f32_16x16x32_bf16; bias, alpha, the fp64 accumulation across split-K slabs and the output are the
+// f32 kernel's.  Operands and outputs stay fp32 in memory: a value is rounded when its tile is staged into LDS.  Same GemmArgs,
+// same grid (64 x 64 tile of C per workgroup, four waves with a 32 x 32 quarter each), k-tile 64.
+//   LDS: both operand tiles are [64 rows or columns of C][64 k] bf16, k contiguous, so a lane's 8 bf16 of one matrix instruction
+//   are ONE 16-byte read; the row stride is 144 bytes = 9 sixteen-byte slots (odd: the 16 rows a lane group reads at one k fall
+//   on 16 distinct slots of the 256-byte bank row).
+//   Staging: waves 0-1 stage A, waves 2-3 stage B, 32 values per thread, requested a k-tile ahead of the products.  An operand
+//   that is contiguous along k (forward, data gradient: activations [N, W] as A, weights as B) gives a thread 8 consecutive k of
+//   4 rows; one that is contiguous along the OTHER index (the weight gradient dz^T a: the node dimension is k) gives it 4
+//   consecutive rows at 8 consecutive k, read 16 bytes at a time along the rows and transposed in registers -- either way a
+//   thread writes four 16-byte LDS rows-of-8.  What lies outside M, N or [k_lo, k_hi) is never read and is zero in LDS (d_in = 49,
+//   widths such as 72 or 96, the last slab of a split reduction, stale rows past the live row count).
+constexpr int kHK = 64;                  // k-tile of the bf16 kernel
+constexpr int kHLd = kHK / 2 + 4;        // 32-bit words per LDS row: 64 bf16 + 16 bytes
+
+__global__ __launch_bounds__(kGT) void ginx_gemm_bf16_kernel(GemmArgs g)
+{
+    __shared__ __attribute__((aligned(16))) uint32_t T[2][kBM * kHLd];      // [0]: A as [m][k], [1]: B as [n][k]
+    const int tid = (int)threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    int M = g.M, K = g.K;
+    if (g.rows_dim == 1) M = *g.rows;
+    if (g.rows_dim == 2) K = *g.rows;
+    const int m0 = (int)blockIdx.x * kBM, n0 = (int)blockIdx.y * kBN;
+    int k_lo = 0, k_hi = K;
+    if (g.rows_dim >= 2) { k_lo = (int)blockIdx.z * kSplitRows; k_hi = min(K, k_lo + kSplitRows); }
+    if (m0 >= M || k_lo >= k_hi) return;                     // (block-uniform)
+    const f32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
+    f32x4 acc[2][2] = {{zero4, zero4}, {zero4, zero4}};
+    const int wr = (wv >> 1) * 32, wc = (wv & 1) * 32;       // this wave's 32 x 32 quarter of the tile
+    // the operand this wave stages, as X(r, k) = X[r * sr + k * sk] with r the index it shares with C
+    const int op = wave_uniform(wv >> 1);
+    const float *X = op ? g.B : g.A;
+    const int64_t sr = op ? g.sbn : g.sam, sk = op ? g.sbk : g.sak;
+    const int R = op ? g.N : M, r0 = op ? n0 : m0;
+    const bool vec = ((g.vec >> op) & 1) != 0, kc = sk == 1;
+    const int t = tid & 127;
+    float v[32];                                             // kc: v[8 i + j] = X(r + 16 i, k + j);  else: v[4 j + u] = X(r + u, k + j)
+    auto fetch = [&](int k0) {
+        if (kc) {
+            const int kk = k0 + (t & 7) * 8;
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                const int r = r0 + (t >> 3) + 16 * i;
+                const float *p = X + (int64_t)r * sr + kk;
+                if (vec && r < R && kk + 7 < k_hi) {
+                    const float4 a = *(const float4 *)p, b = *(const float4 *)(p + 4);
+                    v[8 * i + 0] = a.x; v[8 * i + 1] = a.y; v[8 * i + 2] = a.z; v[8 * i + 3] = a.w;
+                    v[8 * i + 4] = b.x; v[8 * i + 5] = b.y; v[8 * i + 6] = b.z; v[8 * i + 7] = b.w;
+                } else {
+#pragma unroll
+                    for (int j = 0; j < 8; ++j) v[8 * i + j] = (r < R && kk + j < k_hi) ? p[j] : 0.f;
+                }
+            }
+        } else {
+            const int r = r0 + (t & 15) * 4;
+#pragma unroll
+            for (int j = 0; j < 8; ++j) {
+                const int kk = k0 + (t >> 4) * 8 + j;
+                const float *p = X + (int64_t)r * sr + (int64_t)kk * sk;
+                if (vec && sr == 1 && r + 3 < R && kk < k_hi) {
+                    const float4 a = *(const float4 *)p;
+                    v[4 * j + 0] = a.x; v[4 * j + 1] = a.y; v[4 * j + 2] = a.z; v[4 * j + 3] = a.w;
+                } else {
+#pragma unroll
+                    for (int u = 0; u < 4; ++u) v[4 * j + u] = (r + u < R && kk < k_hi) ? p[(int64_t)u * sr] : 0.f;
+                }
+            }
+        }
+    };
+    auto store = [&]() {                                     // fp32 registers -> bf16 LDS rows, 8 consecutive k per 16-byte write
+        uint32_t *tile = T[op];
+        if (kc) {
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                const u32x4 w = {pack2_bf16(v[8 * i + 0], v[8 * i + 1]), pack2_bf16(v[8 * i + 2], v[8 * i + 3]),
+                                 pack2_bf16(v[8 * i + 4], v[8 * i + 5]), pack2_bf16(v[8 * i + 6], v[8 * i + 7])};
+                *(u32x4 *)(tile + ((t >> 3) + 16 * i) * kHLd + (t & 7) * 4) = w;
+            }
+        } else {
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                const u32x4 w = {pack2_bf16(v[0 + u], v[4 + u]), pack2_bf16(v[8 + u], v[12 + u]),
+                                 pack2_bf16(v[16 + u], v[20 + u]), pack2_bf16(v[24 + u], v[28 + u])};
+                *(u32x4 *)(tile + ((t & 15) * 4 + u) * kHLd + (t >> 4) * 4) = w;
+            }
+        }
+    };
+    fetch(k_lo);
+    for (int k0 = k_lo; k0 < k_hi; k0 += kHK) {
+        store();
+        __syncthreads();
+        if (k0 + kHK < k_hi) fetch(k0 + kHK);
+#pragma unroll
+        for (int ks = 0; ks < kHK / 32; ++ks) {
+            const int kw = ks * 16 + (lane >> 4) * 4;         // this lane's 8 k of the 32: words kw .. kw + 3 of a row
+            u32x4 a[2], b[2];
+#pragma unroll
+            for (int i = 0; i < 2; ++i) a[i] = *(const u32x4 *)(T[0] + (wr + 16 * i + (lane & 15)) * kHLd + kw);
+#pragma unroll
+            for (int j = 0; j < 2; ++j) b[j] = *(const u32x4 *)(T[1] + (wc + 16 * j + (lane & 15)) * kHLd + kw);
+#pragma unroll
+            for (int i = 0; i < 2; ++i)
+#pragma unroll
+                for (int j = 0; j < 2; ++j) acc[i][j] = mfma_16x16x32_bf16(a[i], b[j], acc[i][j]);
+        }
+        __syncthreads();
+    }
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int j = 0; j < 2; ++j)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int m = m0 + wr + 16 * i + 4 * (lane >> 4) + r, n = n0 + wc + 16 * j + (lane & 15);
+                if (m < M && n < g.N) {
+                    float val = acc[i][j][r] * g.alpha;
+                    if (g.bias && (g.rows_dim < 2 || blockIdx.z == 0)) val += g.bias[n];
+                    if (g.atomic) atomicAdd(g.Cd + (int64_t)m * g.ldc + n, (double)val); else g.C[(int64_t)m * g.ldc + n] = val;
                 }
             }
 }
@@ -638,7 +765,8 @@ XLayout ginx_layout(int64_t N, int B, int L, int d_in, int W, int O)
 }
 
 void gemm(hipStream_t s, const float *A, int64_t sam, int64_t sak, const float *B, int64_t sbk, int64_t sbn, float *C, int64_t ldc,
-          int M, int N, int K, const float *bias, const int32_t *rows, int rows_dim, int64_t rows_cap, float alpha = 1.0f, double *acc64 = nullptr)
+          int M, int N, int K, const float *bias, const int32_t *rows, int rows_dim, int64_t rows_cap, float alpha = 1.0f, double *acc64 = nullptr,
+          int dtype = 0 /* 0: f32 operands, 1: bf16 operands (ginx_gemm_bf16_kernel) */)
 {
     // 16-byte loads along the contiguous index need the base and the OTHER index's stride to keep that alignment
     const auto al16 = [](const void *p_) { return (((uintptr_t)p_) & 15) == 0; };
@@ -649,7 +777,8 @@ void gemm(hipStream_t s, const float *A, int64_t sam, int64_t sak, const float *
     const int64_t kcap = rows_dim == 2 ? rows_cap : K;
     dim3 grid((mcap + kBM - 1) / kBM, (N + kBN - 1) / kBN, rows_dim >= 2 ? (unsigned)((kcap + kSplitRows - 1) / kSplitRows) : 1u);
     if (rows_dim >= 2) (void)hipMemsetAsync(acc64, 0, sizeof(double) * (size_t)M * (size_t)ldc, s);     // (C is dense: ldc == N)
-    hipLaunchKernelGGL(ginx_gemm_kernel, grid, dim3(kGT), 0, s, g);
+    if (dtype == 1) hipLaunchKernelGGL(ginx_gemm_bf16_kernel, grid, dim3(kGT), 0, s, g);
+    else hipLaunchKernelGGL(ginx_gemm_kernel, grid, dim3(kGT), 0, s, g);
     if (rows_dim >= 2) hipLaunchKernelGGL(ginx_sums_to_grad_kernel, dim3((unsigned)(((int64_t)M * ldc + 255) / 256)), dim3(256), 0, s, (const double *)acc64, (int)(M * ldc), C, 0);
 }
 
@@ -679,6 +808,10 @@ static int ginx_check(const gcc_ginx_pass *p, const char *who)
         snprintf(g_err, kErrLen, "%s: bad sizes", who);
         return -2;
     }
+    if (p->gemm_dtype != 0 && p->gemm_dtype != 1) {
+        snprintf(g_err, kErrLen, "%s: gemm_dtype %d (0 = f32, 1 = bf16 operands)", who, (int)p->gemm_dtype);
+        return -5;
+    }
     const int d_in = w.pos_dim + w.deg_emb_dim + 1;
     if (p->workspace_bytes < gcc_ginx_workspace_bytes(p->node_cap, p->batch_size, w.num_gin_layers, d_in, p->hidden, p->out_dim)) {
         snprintf(g_err, kErrLen, "%s: workspace too small", who);
@@ -698,6 +831,7 @@ int32_t gcc_ginx_forward(const gcc_ginx_pass *p, void *stream)
     float *ws = (float *)p->workspace;
     double *sums = (double *)(ws + x.sums);
     const int32_t *rows = p->node_off + B;                   // the live row count, on the device
+    const int dt = p->gemm_dtype;                            // the per-node Linears; the [B, .] readout Linears stay f32
     hipLaunchKernelGGL(ginx_feat_kernel, dim3(blocks(N * d_in)), dim3(256), 0, s, p->node_off, p->row_ptr, p->graph_id, p->seed_local, p->pos,
                        w.degree_embedding, B, w.pos_dim, w.deg_emb_dim, w.max_degree, p->edge_multiplicity > 0 ? p->edge_multiplicity : 1, ws + x.x0);
     const float *h = ws + x.x0;
@@ -718,9 +852,9 @@ int32_t gcc_ginx_forward(const gcc_ginx_pass *p, void *stream)
     for (int l = 0; l < L; ++l) {
         hipLaunchKernelGGL(ginx_spmm_kernel, dim3(blocks(N, 4)), dim3(256), 0, s, p->node_off, p->row_ptr, p->col_idx, B, h, D, (const float *)nullptr,
                            ws + x.agg[l], (float)(p->edge_multiplicity > 1 ? p->edge_multiplicity : 1));
-        gemm(s, ws + x.agg[l], D, 1, w.lin0_w[l], 1, D, ws + x.z1[l], W, 0, W, D, w.lin0_b[l], rows, 1, N);            // z1 = agg W0^T + b0
+        gemm(s, ws + x.agg[l], D, 1, w.lin0_w[l], 1, D, ws + x.z1[l], W, 0, W, D, w.lin0_b[l], rows, 1, N, 1.0f, nullptr, dt);   // z1 = agg W0^T + b0
         bn(ws + x.z1[l], w.bn_a[l], x.mr[l][0], ws + x.a1[l]);
-        gemm(s, ws + x.a1[l], W, 1, w.lin1_w[l], 1, W, ws + x.z2[l], W, 0, W, W, w.lin1_b[l], rows, 1, N);             // z2 = a1 W1^T + b1
+        gemm(s, ws + x.a1[l], W, 1, w.lin1_w[l], 1, W, ws + x.z2[l], W, 0, W, W, w.lin1_b[l], rows, 1, N, 1.0f, nullptr, dt);    // z2 = a1 W1^T + b1
         bn(ws + x.z2[l], w.bn_b[l], x.mr[l][1], ws + x.a2[l]);
         bn(ws + x.a2[l], w.bn_c[l], x.mr[l][2], ws + x.h[l]);
         h = ws + x.h[l];
@@ -756,6 +890,7 @@ int32_t gcc_ginx_backward(const gcc_ginx_pass *p, const float *dfeat, const gcc_
     float *ws = (float *)p->workspace;
     double *sums = (double *)(ws + x.sums);
     const int32_t *rows = p->node_off + B;
+    const int dt = p->gemm_dtype;                            // the per-node Linears' data and weight gradients; the readout's stay f32
     float *dA = ws + x.da, *dB_ = ws + x.db, *dC = ws + x.dc;
     double *wg64 = (double *)(ws + x.wg64);
     // ---- readout: dscore -> per hidden_rep: dy = dscore * keep / (1 - p); dWp = dy^T pooled; dbp = colsum(dy); dpooled = dy Wp
@@ -795,13 +930,13 @@ int32_t gcc_ginx_backward(const gcc_ginx_pass *p, const float *dfeat, const gcc_
         const int Din = l == 0 ? d_in : W;
         bn_bwd(ws + x.a2[l], ws + x.h[l], dA, w.bn_c[l], x.mr[l][2], dB_, gr->bn_c_w[l], gr->bn_c_b[l]);                  // -> d a2
         bn_bwd(ws + x.z2[l], ws + x.a2[l], dB_, w.bn_b[l], x.mr[l][1], dA, gr->bn_b_w[l], gr->bn_b_b[l]);                 // -> d z2
-        gemm(s, dA, 1, W, ws + x.a1[l], W, 1, gr->lin1_w[l], W, W, W, 0, nullptr, rows, 2, N, 1.0f, wg64);                            // dW1 [W, W] = dz2^T a1
+        gemm(s, dA, 1, W, ws + x.a1[l], W, 1, gr->lin1_w[l], W, W, W, 0, nullptr, rows, 2, N, 1.0f, wg64, dt);                        // dW1 [W, W] = dz2^T a1
         bias_grad(dA, gr->lin1_b[l]);
-        gemm(s, dA, W, 1, w.lin1_w[l], W, 1, dB_, W, 0, W, W, nullptr, rows, 1, N);                                        // d a1 = dz2 W1
+        gemm(s, dA, W, 1, w.lin1_w[l], W, 1, dB_, W, 0, W, W, nullptr, rows, 1, N, 1.0f, nullptr, dt);                     // d a1 = dz2 W1
         bn_bwd(ws + x.z1[l], ws + x.a1[l], dB_, w.bn_a[l], x.mr[l][0], dA, gr->bn_a_w[l], gr->bn_a_b[l]);                 // -> d z1
-        gemm(s, dA, 1, W, ws + x.agg[l], Din, 1, gr->lin0_w[l], Din, W, Din, 0, nullptr, rows, 2, N, 1.0f, wg64);                     // dW0 [W, Din] = dz1^T agg
+        gemm(s, dA, 1, W, ws + x.agg[l], Din, 1, gr->lin0_w[l], Din, W, Din, 0, nullptr, rows, 2, N, 1.0f, wg64, dt);                 // dW0 [W, Din] = dz1^T agg
         bias_grad(dA, gr->lin0_b[l]);
-        gemm(s, dA, W, 1, w.lin0_w[l], Din, 1, dB_, Din, 0, Din, W, nullptr, rows, 1, N);                                  // d agg = dz1 W0
+        gemm(s, dA, W, 1, w.lin0_w[l], Din, 1, dB_, Din, 0, Din, W, nullptr, rows, 1, N, 1.0f, nullptr, dt);               // d agg = dz1 W0
         // d h_{l-1} = d agg + A d agg (the batched subgraph is symmetric) + the pooled readout of hidden_rep[l]'s input
         readout_bwd(l, ws + x.dpool);
         hipLaunchKernelGGL(ginx_pool_bwd_kernel, dim3(blocks((Din & 3) == 0 ? N * Din / 4 : N * Din)), dim3(256), 0, s, p->node_off, p->graph_id, B, ws + x.dpool, Din, dC, 0,
@@ -818,9 +953,15 @@ int32_t gcc_ginx_backward(const gcc_ginx_pass *p, const float *dfeat, const gcc_
 }
 
 /* ---- the head at any feature size */
-int32_t gcc_ncex_forward(const float *q, const float *k, const float *mem, int32_t B, int32_t K, int32_t D, float inv_T, int32_t mode,
-                         float *out, float *dlog, float *grad_rows, float *grad_mem, float *loss, float *prob, double *acc, void *stream)
+int32_t gcc_ncex_forward_dt(const float *q, const float *k, const float *mem, int32_t B, int32_t K, int32_t D, float inv_T, int32_t mode,
+                            float *out, float *dlog, float *grad_rows, float *grad_mem, float *loss, float *prob, double *acc, int32_t gemm_dtype,
+                            void *stream)
 {
+    if (gemm_dtype != 0 && gemm_dtype != 1) {
+        snprintf(g_err, kErrLen, "gcc_ncex_forward_dt: gemm_dtype %d (0 = f32, 1 = bf16 operands)", (int)gemm_dtype);
+        return -5;
+    }
+    const int dt = gemm_dtype;             // the three dense products: logits, d loss / d rows, d loss / d mem (the positive logit stays f32)
     if (!q || !mem || !out || !dlog || !grad_rows || !loss || !prob || !acc || B < 1 || K < 1 || D < 1 || (mode == 0 && !k) || (mode == 1 && (K != B || !grad_mem))) {
         snprintf(g_err, kErrLen, "gcc_ncex_forward: bad arguments");
         return -1;
@@ -831,20 +972,26 @@ int32_t gcc_ncex_forward(const float *q, const float *k, const float *mem, int32
     float *neg = out + (mode == 0 ? 1 : 0);
     (void)hipMemsetAsync(acc, 0, 2 * sizeof(double), s);
     if (mode == 0) hipLaunchKernelGGL(ginx_rowdot_kernel, dim3(B), dim3(64), 0, s, q, k, D, inv_T, out, ld);
-    gemm(s, q, D, 1, mem, 1, D, neg, ld, B, K, D, nullptr, nullptr, 0, 0, inv_T);                                  // q mem^T / T
+    gemm(s, q, D, 1, mem, 1, D, neg, ld, B, K, D, nullptr, nullptr, 0, 0, inv_T, nullptr, dt);                                // q mem^T / T
     hipLaunchKernelGGL(ginx_ce_kernel, dim3(B), dim3(256), 0, s, (const float *)out, ld, ncols, mode, dlog, acc);
     hipLaunchKernelGGL(ginx_ce_final_kernel, dim3(1), dim3(64), 0, s, (const double *)acc, B, loss, prob);
     // the gradients for a unit upstream gradient, taken NOW -- before the caller enqueues the step's keys over queue rows
     // (memory_moco.py:55-61): d loss / d rows = (softmax - onehot) [k; mem] / (T B)
     const float coef = inv_T / (float)B;
     // (reduction over the K queue rows: split over workgroups when it is long, fp64 atomics into acc + 2)
-    if (K >= 4 * kSplitRows) gemm(s, dlog + (mode == 0 ? 1 : 0), ld, 1, mem, D, 1, grad_rows, D, B, D, K, nullptr, nullptr, 3, 0, coef, acc + 2);
-    else gemm(s, dlog + (mode == 0 ? 1 : 0), ld, 1, mem, D, 1, grad_rows, D, B, D, K, nullptr, nullptr, 0, 0, coef);
+    if (K >= 4 * kSplitRows) gemm(s, dlog + (mode == 0 ? 1 : 0), ld, 1, mem, D, 1, grad_rows, D, B, D, K, nullptr, nullptr, 3, 0, coef, acc + 2, dt);
+    else gemm(s, dlog + (mode == 0 ? 1 : 0), ld, 1, mem, D, 1, grad_rows, D, B, D, K, nullptr, nullptr, 0, 0, coef, nullptr, dt);
     if (mode == 0) hipLaunchKernelGGL(ginx_rank1_rows_kernel, dim3(blocks((int64_t)B * D)), dim3(256), 0, s, (const float *)dlog, ld, k, B, D, coef, grad_rows);
-    else gemm(s, dlog, 1, ld, q, D, 1, grad_mem, D, K, D, B, nullptr, nullptr, 0, 0, coef);                         // d loss / d mem rows = dlog^T rows / (T B)
+    else gemm(s, dlog, 1, ld, q, D, 1, grad_mem, D, K, D, B, nullptr, nullptr, 0, 0, coef, nullptr, dt);                       // d loss / d mem rows = dlog^T rows / (T B)
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) { snprintf(g_err, kErrLen, "gcc_ncex_forward: launch failed: %s", hipGetErrorString(e)); return -10; }
     return 0;
+}
+
+int32_t gcc_ncex_forward(const float *q, const float *k, const float *mem, int32_t B, int32_t K, int32_t D, float inv_T, int32_t mode,
+                         float *out, float *dlog, float *grad_rows, float *grad_mem, float *loss, float *prob, double *acc, void *stream)
+{
+    return gcc_ncex_forward_dt(q, k, mem, B, K, D, inv_T, mode, out, dlog, grad_rows, grad_mem, loss, prob, acc, 0, stream);
 }
 
 int32_t gcc_queue_enqueue_x(float *mem, int32_t K, int32_t D, const float *keys, int32_t nkeys, int32_t index, void *stream)

@@ -402,8 +402,13 @@ class GraphEncoder(nn.Module):
     def __init__(self, positional_embedding_size=32, max_node_freq=8, max_edge_freq=8, max_degree=128,
                  freq_embedding_size=32, degree_embedding_size=32, output_dim=32, node_hidden_dim=32,
                  edge_hidden_dim=32, num_layers=6, num_heads=4, num_step_set2set=6, num_layer_set2set=3,
-                 norm=False, gnn_model="mpnn", degree_input=False, lstm_as_gate=False):
+                 norm=False, gnn_model="mpnn", degree_input=False, lstm_as_gate=False, encoder_dtype="f32"):
         super().__init__()
+        # ``encoder_dtype`` is not in the reference: "bf16" runs the per-node Linears of the any-width GIN (forward, data and weight
+        # gradients) with bf16 operands on the matrix cores (csrc/ginx.hip: ginx_gemm_bf16_kernel); "f32" is the parity mode
+        if encoder_dtype not in _cabi.GEMM_DTYPES:
+            raise ValueError(f"encoder_dtype={encoder_dtype!r}: expected one of {sorted(_cabi.GEMM_DTYPES)}")
+        self.encoder_dtype = encoder_dtype
         if gnn_model not in ("gin", "gat"):
             raise NotImplementedError(f"gnn_model={gnn_model!r}: gcc_amd runs the \"gin\" (train.py:77 default) and \"gat\" "
                                       "backbones (\"mpnn\" does not run in the reference: graph_encoder.py:188 feeds "
@@ -413,6 +418,11 @@ class GraphEncoder(nn.Module):
         if node_hidden_dim < 1 or output_dim < 1:
             raise ValueError(f"hidden / output size must be positive (got {node_hidden_dim} / {output_dim})")
         node_input_dim = positional_embedding_size + degree_embedding_size + 1      # graph_encoder.py:66-67
+        if encoder_dtype != "f32" and (gnn_model != "gin" or not (node_hidden_dim > H or output_dim > H or node_input_dim > H)):
+            raise NotImplementedError(f"encoder_dtype={encoder_dtype!r} is the any-width GIN's throughput mode (csrc/ginx.hip, hidden / output "
+                                      f"size above {H}); the fused {H}-channel GIN kernels (csrc/encoder.hip, encoder_bwd.hip, "
+                                      f"encoder_eval.hip) and the GAT kernels (csrc/gat.hip) compute in f32 -- drop --encoder-dtype or "
+                                      f"use --model gin with --hidden-size above {H}")
         if gnn_model == "gat":
             self._init_gat(positional_embedding_size, max_node_freq, max_edge_freq, max_degree, degree_embedding_size,
                            output_dim, node_hidden_dim, num_layers, num_heads, num_step_set2set, num_layer_set2set, norm)
@@ -633,3 +643,16 @@ class GraphEncoder(nn.Module):
         if return_all_outputs:                       # the kernels' 64 channels -> the model's own widths
             return out[0][:, : self.output_dim], [t[:, : self.hidden] for t in out[1]]
         return out[:, : self.output_dim]
+
+
+def encoder_from_opt(args):
+    """The GraphEncoder of a checkpoint's ``opt`` (generate.py:102-118, train.py:601-620 with the pre-training run's options).
+    ``encoder_dtype`` is read with a default: checkpoints written before ``--encoder-dtype`` existed build the f32 encoder they
+    were trained with."""
+    return GraphEncoder(
+        positional_embedding_size=args.positional_embedding_size, max_node_freq=args.max_node_freq,
+        max_edge_freq=args.max_edge_freq, max_degree=args.max_degree, freq_embedding_size=args.freq_embedding_size,
+        degree_embedding_size=args.degree_embedding_size, output_dim=args.hidden_size, node_hidden_dim=args.hidden_size,
+        edge_hidden_dim=args.hidden_size, num_layers=args.num_layer, num_step_set2set=args.set2set_iter,
+        num_layer_set2set=args.set2set_lstm_layer, norm=args.norm, gnn_model=args.model, degree_input=True,
+        encoder_dtype=getattr(args, "encoder_dtype", "f32"))

@@ -52,6 +52,7 @@ class WideGinEngine:
         p.dropout_keep = ptr(keep) if keep is not None else None
         p.hidden, p.out_dim = enc.hidden, enc.output_dim
         p.edge_multiplicity = int(getattr(g, "edge_multiplicity", 1))
+        p.gemm_dtype = _cabi.GEMM_DTYPES[getattr(enc, "encoder_dtype", "f32")]      # (--encoder-dtype: the per-node Linears' operands)
         p.node_cap = node_cap
         p.w = fill_weights(enc, ptr)
         p.workspace, p.workspace_bytes = ptr(buf["ws"]), nbytes

@@ -85,7 +85,7 @@ def _summary_writer(folder):
 
 
 def main_finetune(args, option_update):
-    from .encoder import GraphEncoder
+    from .encoder import encoder_from_opt
     from .finetune import FinetuneTrainStep, LabeledProducer, clear_bn, cls_head_loss, evaluate
     from .train_step import flatten_parameters
 
@@ -113,12 +113,7 @@ def main_finetune(args, option_update):
     dataset = load_labelled(args, dev)                              # train.py:516-545
     train_idx, test_idx = fold_split(dataset.labels.tolist(), args.fold_idx, args.seed)
 
-    model = GraphEncoder(                                           # train.py:601-620
-        positional_embedding_size=args.positional_embedding_size, max_node_freq=args.max_node_freq,
-        max_edge_freq=args.max_edge_freq, max_degree=args.max_degree, freq_embedding_size=args.freq_embedding_size,
-        degree_embedding_size=args.degree_embedding_size, output_dim=args.hidden_size, node_hidden_dim=args.hidden_size,
-        edge_hidden_dim=args.hidden_size, num_layers=args.num_layer, num_step_set2set=args.set2set_iter,
-        num_layer_set2set=args.set2set_lstm_layer, norm=args.norm, gnn_model=args.model, degree_input=True).to(dev)
+    model = encoder_from_opt(args).to(dev)                          # train.py:601-620
     from .contrast import MemoryMoCo
 
     contrast = MemoryMoCo(args.hidden_size, None, args.nce_k, args.nce_t, use_softmax=True).to(dev)   # (checkpointed only)

@@ -18,7 +18,7 @@ import torch
 def main(args_test):
     from gcc_amd import ingest
     from gcc_amd.datasets import GraphClassificationDataset, NodeClassificationDataset
-    from gcc_amd.encoder import GraphEncoder
+    from gcc_amd.encoder import encoder_from_opt
     from gcc_amd.generate import test_moco
     from gcc_amd.posemb import DevicePosEmb
 
@@ -67,12 +67,7 @@ def main(args_test):
             graph=graph, edge_multiplicity=mult, batch_size=args_test.batch_size, run_seed=getattr(args, "seed", 0),
             device=args.device)
         node_cap = train_dataset.sampler.node_cap
-    model = GraphEncoder(                                            # generate.py:102-118
-        positional_embedding_size=args.positional_embedding_size, max_node_freq=args.max_node_freq,
-        max_edge_freq=args.max_edge_freq, max_degree=args.max_degree, freq_embedding_size=args.freq_embedding_size,
-        degree_embedding_size=args.degree_embedding_size, output_dim=args.hidden_size, node_hidden_dim=args.hidden_size,
-        edge_hidden_dim=args.hidden_size, num_layers=args.num_layer, num_step_set2set=args.set2set_iter,
-        num_layer_set2set=args.set2set_lstm_layer, gnn_model=args.model, norm=args.norm, degree_input=True)
+    model = encoder_from_opt(args)                                   # generate.py:102-118
     model = model.to(args.device)
     model.load_state_dict(checkpoint["model"])
     del checkpoint

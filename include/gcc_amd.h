@@ -414,7 +414,8 @@ int32_t gcc_gin_backward_sumsq(const gcc_gin_pass *pass, const float *dfeat, con
 /* ------------------------------------- GIN encoder at any width (training) ---
  * The same encoder -- GraphEncoder(gnn_model="gin").forward, graph_encoder.py:132-200 -> gin.py:213-232 -- for hidden /
  * output sizes the 64-channel kernels above do not serve (`--hidden-size` above 64, train.py:93), forward in training
- * or eval mode and the full backward, fp32 on the matrix cores.  Not fused: one launch per operator (CSR gather, strided
+ * or eval mode and the full backward, fp32 on the matrix cores (gemm_dtype 0, the default) or with bf16 operands for the
+ * per-node Linears (gemm_dtype 1, below).  Not fused: one launch per operator (CSR gather, strided
  * MFMA GEMM, fp64 column statistics, BatchNorm + ReLU passes, per-graph pooling); every activation is kept in the
  * caller's workspace for the backward pass.  Weights / gradients use gcc_gin_weights / gcc_gin_grads with the tensors'
  * own (unpadded) shapes: lin0_w[0] [hidden, d_in], lin0_w[i > 0] and lin1_w [hidden, hidden], pred_w[0] [out_dim, d_in],
@@ -432,7 +433,14 @@ typedef struct gcc_ginx_pass {
     const float *dropout_keep;   /* device [num_gin_layers + 1, B, out_dim] 0 / 1 keep masks, or NULL: no dropout       */
     int32_t hidden, out_dim;     /* node_hidden_dim, output_dim: any positive size                                      */
     int32_t edge_multiplicity;   /* gcc_gin_pass.edge_multiplicity (forward; the backward pass requires 0 / 1)          */
-    int32_t reserved_;
+    int32_t gemm_dtype;          /* (the former reserved_ field: 0 in every older caller) operands of the per-node Linears   */
+                                 /* z1 / z2, their data gradients d a1 / d agg and weight gradients dW1 / dW0:          */
+                                 /*   0: f32 on v_mfma_f32_16x16x4_f32 (parity mode);                                   */
+                                 /*   1: C = alpha * sum_k bf16(A) * bf16(B) [+ bias] -- operands rounded to nearest    */
+                                 /*      even as their tiles are staged, products and sums in fp32 on                   */
+                                 /*      v_mfma_f32_16x16x32_bf16; memory stays fp32.  Gather, statistics, BatchNorm,   */
+                                 /*      pooling, bias gradients, the [B, .] readout Linears and the normalisation are  */
+                                 /*      f32 / fp64 in both modes.  Any other value: rc -5.                             */
     int64_t node_cap;            /* rows the launches are sized for (node_off[B] <= node_cap, read on the device)       */
     gcc_gin_weights w;
     void *workspace;             /* device, gcc_ginx_workspace_bytes(): activations of the forward pass (kept for the   */
@@ -455,6 +463,13 @@ int32_t gcc_ginx_backward(const gcc_ginx_pass *p, const float *dfeat, const gcc_
  * over the K queue rows and is split over workgroups). */
 int32_t gcc_ncex_forward(const float *q, const float *k, const float *mem, int32_t B, int32_t K, int32_t D, float inv_T, int32_t mode,
                          float *out, float *dlog, float *grad_rows, float *grad_mem, float *loss, float *prob, double *acc, void *stream);
+/* gcc_ncex_forward with the operand type of its three dense products -- the logits rows mem^T / T, d loss / d rows =
+ * dlog mem / (T B) and (mode 1) d loss / d mem = dlog^T rows / (T B): gemm_dtype 0 = f32 (what gcc_ncex_forward calls),
+ * 1 = operands rounded to bf16, fp32 products and sums (the rule of gcc_ginx_pass.gemm_dtype; `--nce-dtype bf16` above 64
+ * features).  The positive logit <q, k> / T, the softmax and the positive's share of d loss / d q stay f32.  Other values: rc -5. */
+int32_t gcc_ncex_forward_dt(const float *q, const float *k, const float *mem, int32_t B, int32_t K, int32_t D, float inv_T, int32_t mode,
+                            float *out, float *dlog, float *grad_rows, float *grad_mem, float *loss, float *prob, double *acc,
+                            int32_t gemm_dtype, void *stream);
 /* memory.index_copy_(0, (arange(nkeys) + index) % K, keys) (memory_moco.py:55-61) for rows of D floats.  nkeys <= K is required
  * (rc -1 otherwise), as gcc_queue_enqueue requires it: with more keys than queue rows the indices collide and the reference's
  * index_copy_ result depends on the order its kernel happens to write in -- nothing a replacement could be bit-equal to. */

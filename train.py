@@ -122,6 +122,7 @@ def parse_option(argv=None):
     parser.add_argument("--graph-npz", type=str, default=None, help="npz with row_ptr/col_idx (instead of data/small.bin)")
     parser.add_argument("--synthetic", type=str, default=None, help="V,E of a synthetic power-law graph, e.g. 1000000,10000000")
     parser.add_argument("--nce-dtype", type=str, default="f32", choices=["f32", "bf16"], help="operands of the MoCo head: f32 = exact (1e-3 parity with the reference), bf16 = matrix-core throughput mode")
+    parser.add_argument("--encoder-dtype", type=str, default="f32", choices=["f32", "bf16"], help="operands of the GIN layers' Linears above --hidden-size 64 (forward, data and weight gradients): f32 = exact, bf16 = matrix-core throughput mode")
     parser.add_argument("--max-steps", type=int, default=0, help="stop after this many steps (0 = full schedule)")
     parser.add_argument("--producer-lanes", type=int, default=2, help="data-pipeline streams (the GPU's command processor serves few queues well)")
     parser.add_argument("--producer-chunk", type=int, default=4, help="steps a lane prepares per turn (2x as many views per eigensolver call, <= 32)")
@@ -222,7 +223,7 @@ def train_moco(epoch, dataset, trainer, model, model_ema, contrast, criterion, o
                 out = contrast(feat_q, feat_k)
             else:                                        # train.py:396-401
                 feat_k = model(graph_k)
-                out = e2e_logits(feat_q, feat_k, opt.nce_t)
+                out = e2e_logits(feat_q, feat_k, opt.nce_t, nce_dtype=getattr(opt, "nce_dtype", "f32"))
             prob = out.prob
             optimizer.zero_grad()
             loss = criterion(out)
@@ -339,7 +340,8 @@ def main(args):
             freq_embedding_size=args.freq_embedding_size, degree_embedding_size=args.degree_embedding_size,
             output_dim=args.hidden_size, node_hidden_dim=args.hidden_size, edge_hidden_dim=args.hidden_size,
             num_layers=args.num_layer, num_step_set2set=args.set2set_iter, num_layer_set2set=args.set2set_lstm_layer,
-            norm=args.norm, gnn_model=args.model, degree_input=True).to(dev)
+            norm=args.norm, gnn_model=args.model, degree_input=True,
+            encoder_dtype=getattr(args, "encoder_dtype", "f32")).to(dev)
         for _ in range(2)
     ]
     flatten_parameters(model)
