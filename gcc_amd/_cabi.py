@@ -381,9 +381,38 @@ def load() -> ctypes.CDLL:
     return _lib
 
 
-def check(rc: int, what: str) -> None:
+def call(lib, name: str, *args) -> None:
+    """``lib.<name>(*args)`` for a symbol that returns 0 on success.  ``lib`` is the library the CALLER holds (an engine's
+    own ``self.lib``: the HIP library, or the emulator build a test injected), so the error text is that library's."""
+    rc = getattr(lib, name)(*args)
     if rc != 0:
-        raise RuntimeError(f"{what} failed ({rc}): {load().gcc_last_error().decode()}")
+        raise RuntimeError(error_text(lib, name, rc))
+
+
+def size_query(lib, name: str, *args, named=True) -> int:
+    """``lib.<name>(*args)`` for a symbol that returns an int64 size, negative on error.  ``named=False``: the bare error text
+    (what gcc_ginx_workspace_bytes has always raised)."""
+    n = getattr(lib, name)(*args)
+    if n < 0:
+        raise RuntimeError(error_text(lib, name, n) if named else lib.gcc_last_error().decode())
+    return n
+
+
+def error_text(lib, name, rc):
+    return f"{name} failed ({rc}): {lib.gcc_last_error().decode()}"
+
+
+def node_cap(g) -> int:
+    """rows of a batch's per-node arrays (a sampler batch carries ``parent_nid``, the hand-built ones only ``graph_id``)"""
+    return g.parent_nid.numel() if hasattr(g, "parent_nid") else g.graph_id.numel()
+
+
+def raw_stream(where):
+    """the raw handle of torch's current stream on the device of ``where`` (a tensor or a device); None off the GPU"""
+    import torch
+
+    dev = where.device if isinstance(where, torch.Tensor) else torch.device(where)
+    return torch.cuda.current_stream(dev).cuda_stream if dev.type == "cuda" else None
 
 
 def dev_ptr(t, dtype=None) -> int:

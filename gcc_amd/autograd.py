@@ -7,11 +7,8 @@ from __future__ import annotations
 
 import torch
 
+from ._cabi import raw_stream
 from .encoder import STALE_SLOT_MSG, H, gat_params, grad_params
-
-
-def _stream(t):
-    return torch.cuda.current_stream(t.device).cuda_stream if t.is_cuda else None
 
 
 class _GinFn(torch.autograd.Function):
@@ -21,9 +18,9 @@ class _GinFn(torch.autograd.Function):
         bn_training = enc.bn_training()
         p, buf = eng.make_pass(enc, g, training=bn_training, keep=keep, slot=enc.pass_slot(needs_backward))
         if not bn_training and getattr(enc, "fused_eval", True):
-            eng.eval_fused([p], stream=_stream(g.node_off))     # eval mode: one launch, one workgroup per subgraph
+            eng.eval_fused([p], stream=raw_stream(g.node_off))     # eval mode: one launch, one workgroup per subgraph
         else:
-            eng.forward([p], stream=_stream(g.node_off))
+            eng.forward([p], stream=raw_stream(g.node_off))
         ctx.enc, ctx.p, ctx.buf = enc, p, buf
         L = len(enc.gnn.ginlayers)
         outs = [buf["feat"].clone()] + [buf["pooled"][i + 1].float() for i in range(L)]
@@ -38,7 +35,7 @@ class _GinFn(torch.autograd.Function):
         if not enc.engine().slot_is_current(ctx.buf):
             raise RuntimeError(STALE_SLOT_MSG)
         targets = [enc.padded_zeros_like(param) for _, _, param in grad_params(enc)]
-        enc.engine().backward(enc, ctx.p, ctx.buf, dfeat, targets=targets, stream=_stream(dfeat))
+        enc.engine().backward(enc, ctx.p, ctx.buf, dfeat, targets=targets, stream=raw_stream(dfeat))
         return (None, None, None, None, *targets)
 
 
@@ -64,7 +61,7 @@ class _GatFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, enc, g, *params):
-        out, saved, p, w = enc.engine().forward(enc, g, stream=_stream(g.node_off))
+        out, saved, p, w = enc.engine().forward(enc, g, stream=raw_stream(g.node_off))
         ctx.enc, ctx.g, ctx.p, ctx.w = enc, g, p, w
         ctx.saved_gat = saved          # p / w hold raw pointers into `saved` and the parameters of this pass
         ctx.save_for_backward(*params)
@@ -75,7 +72,7 @@ class _GatFn(torch.autograd.Function):
         enc = ctx.enc
         params = ctx.saved_tensors     # (raises if a parameter was modified in place since the forward)
         targets = [torch.zeros_like(t) for t in params]
-        enc.engine().backward(enc, ctx.p, ctx.w, dout, targets, stream=_stream(dout))
+        enc.engine().backward(enc, ctx.p, ctx.w, dout, targets, stream=raw_stream(dout))
         return (None, None, *targets)
 
 
@@ -86,6 +83,6 @@ def gat_apply(enc, g):
     params = [t for _, _, t in gat_params(enc)]
     if not (torch.is_grad_enabled() and any(t.requires_grad for t in params)):
         with torch.no_grad():
-            out, _saved, _p, _w = enc.engine().forward(enc, g, stream=_stream(g.node_off))
+            out, _saved, _p, _w = enc.engine().forward(enc, g, stream=raw_stream(g.node_off))
         return out
     return _GatFn.apply(enc, g, *params)

@@ -17,6 +17,7 @@ import torch
 from torch import nn
 
 from . import _cabi
+from ._cabi import raw_stream
 
 D = 64
 
@@ -59,9 +60,7 @@ class NceEngine:
         out = torch.empty(B, K + (1 if pos_mode == 0 else 0), **f32) if dense else None
         ws, nbytes = self._workspace(B, K, q.device)
         a = self._args(q, k, mem, 1.0 / T, pos_mode, patch, patch_index, outs, out)
-        rc = self.lib.gcc_nce_forward(ctypes.byref(a), self.ptr(ws), nbytes, prof.handle if prof else None, stream)
-        if rc != 0:
-            raise RuntimeError(f"gcc_nce_forward failed ({rc}): {self.lib.gcc_last_error().decode()}")
+        _cabi.call(self.lib, "gcc_nce_forward", ctypes.byref(a), self.ptr(ws), nbytes, prof.handle if prof else None, stream)
         outs["out"] = out
         return outs
 
@@ -72,10 +71,8 @@ class NceEngine:
         ws, nbytes = self._workspace(B, K, q.device)
         a = self._args(q, k, mem, 1.0 / T, pos_mode, patch, patch_index, outs, None)
         dloss = dloss.reshape(1).to(torch.float32).contiguous()
-        rc = self.lib.gcc_nce_backward(ctypes.byref(a), self.ptr(dloss), int(by_mem_row), self.ptr(dq), self.ptr(ws),
-                                       nbytes, prof.handle if prof else None, stream)
-        if rc != 0:
-            raise RuntimeError(f"gcc_nce_backward failed ({rc}): {self.lib.gcc_last_error().decode()}")
+        _cabi.call(self.lib, "gcc_nce_backward", ctypes.byref(a), self.ptr(dloss), int(by_mem_row), self.ptr(dq), self.ptr(ws),
+                   nbytes, prof.handle if prof else None, stream)
         return dq
 
     def one_pass(self):
@@ -97,19 +94,15 @@ class NceEngine:
         ws, nbytes = self._workspace(B, K, q.device)
         a = self._args(q, k, mem, 1.0 / T, 0, patch, patch_index, outs, None)
         dloss = dloss.reshape(1).to(torch.float32).contiguous()
-        rc = self.lib.gcc_nce_forward_backward(ctypes.byref(a), self.ptr(dloss), self.ptr(dq), self.ptr(ws), nbytes,
-                                               prof_fwd.handle if prof_fwd else None, prof_bwd.handle if prof_bwd else None,
-                                               stream)
-        if rc != 0:
-            raise RuntimeError(f"gcc_nce_forward_backward failed ({rc}): {self.lib.gcc_last_error().decode()}")
+        _cabi.call(self.lib, "gcc_nce_forward_backward", ctypes.byref(a), self.ptr(dloss), self.ptr(dq), self.ptr(ws), nbytes,
+                   prof_fwd.handle if prof_fwd else None, prof_bwd.handle if prof_bwd else None,
+                   stream)
         return outs, dq
 
     def set_scalars(self, scalars, lr, betas, adam_step, enqueue_index, dropout_seed, stream=None):
         """gcc_step_scalars_set: the per-step scalars of a replayed step into their device struct (uint8[24] tensor)."""
-        rc = self.lib.gcc_step_scalars_set(self.ptr(scalars), float(lr), float(betas[0]), float(betas[1]), int(adam_step),
-                                           int(enqueue_index), int(dropout_seed) & 0xFFFFFFFFFFFFFFFF, stream)
-        if rc != 0:
-            raise RuntimeError(f"gcc_step_scalars_set failed ({rc}): {self.lib.gcc_last_error().decode()}")
+        _cabi.call(self.lib, "gcc_step_scalars_set", self.ptr(scalars), float(lr), float(betas[0]), float(betas[1]), int(adam_step),
+                   int(enqueue_index), int(dropout_seed) & 0xFFFFFFFFFFFFFFFF, stream)
 
     def fill_scalars(self, ring, slot, lr, betas, adam_step, enqueue_index, dropout_seed):
         """gcc_step_scalars_fill: entry ``slot`` of the host-pinned ring (a CPU uint8 tensor), no device work."""
@@ -118,32 +111,24 @@ class NceEngine:
 
     def fetch_scalars(self, scalars, ring, ring_len, counter, stream=None):
         """gcc_step_scalars_fetch: the step's first launch (captured with it): ring[counter % ring_len] -> device struct."""
-        rc = self.lib.gcc_step_scalars_fetch(self.ptr(scalars), ring.data_ptr(), int(ring_len), self.ptr(counter), stream)
-        if rc != 0:
-            raise RuntimeError(f"gcc_step_scalars_fetch failed ({rc}): {self.lib.gcc_last_error().decode()}")
+        _cabi.call(self.lib, "gcc_step_scalars_fetch", self.ptr(scalars), ring.data_ptr(), int(ring_len), self.ptr(counter), stream)
 
     def enqueue(self, mem, keys, index, save=True, stream=None, scalars=None):
         if scalars is not None:                      # ring pointer from the device struct (replayed step); no saved rows
-            rc = self.lib.gcc_queue_enqueue_scalars(self.ptr(mem), mem.shape[0], self.ptr(keys), keys.shape[0],
-                                                    self.ptr(scalars), stream)
-            if rc != 0:
-                raise RuntimeError(f"gcc_queue_enqueue_scalars failed ({rc}): {self.lib.gcc_last_error().decode()}")
+            _cabi.call(self.lib, "gcc_queue_enqueue_scalars", self.ptr(mem), mem.shape[0], self.ptr(keys), keys.shape[0],
+                       self.ptr(scalars), stream)
             return None
         saved = torch.empty_like(keys) if save else None
-        rc = self.lib.gcc_queue_enqueue(self.ptr(mem), mem.shape[0], self.ptr(keys), keys.shape[0], int(index),
-                                        self.ptr(saved) if saved is not None else None, stream)
-        if rc != 0:
-            raise RuntimeError(f"gcc_queue_enqueue failed ({rc}): {self.lib.gcc_last_error().decode()}")
+        _cabi.call(self.lib, "gcc_queue_enqueue", self.ptr(mem), mem.shape[0], self.ptr(keys), keys.shape[0], int(index),
+                   self.ptr(saved) if saved is not None else None, stream)
         return saved
 
     def adam(self, param, grad, exp_avg, exp_avg_sq, lr, betas, eps, weight_decay, step, max_norm, grad_norm,
              scratch, stream=None, grad_scale=1.0):
-        rc = self.lib.gcc_adam_step(self.ptr(param), self.ptr(grad), self.ptr(exp_avg), self.ptr(exp_avg_sq),
-                                    param.numel(), float(lr), float(betas[0]), float(betas[1]), float(eps),
-                                    float(weight_decay), int(step), float(max_norm), float(grad_scale), self.ptr(grad_norm),
-                                    self.ptr(scratch), stream)
-        if rc != 0:
-            raise RuntimeError(f"gcc_adam_step failed ({rc}): {self.lib.gcc_last_error().decode()}")
+        _cabi.call(self.lib, "gcc_adam_step", self.ptr(param), self.ptr(grad), self.ptr(exp_avg), self.ptr(exp_avg_sq),
+                   param.numel(), float(lr), float(betas[0]), float(betas[1]), float(eps),
+                   float(weight_decay), int(step), float(max_norm), float(grad_scale), self.ptr(grad_norm),
+                   self.ptr(scratch), stream)
 
     def adam_ema(self, param, grad, exp_avg, exp_avg_sq, lr, betas, eps, weight_decay, step, max_norm, grad_norm,
                  scratch, stream=None, grad_scale=1.0, ema=None, ema_src=None, ema_m=0.0, meters=None, scalars=None,
@@ -165,7 +150,8 @@ class NceEngine:
         if sumsq_parts is not None or enqueue is not None:
             parts, nparts = sumsq_parts if sumsq_parts is not None else (None, 0)
             queue, keys = enqueue if enqueue is not None else (None, None)
-            rc = self.lib.gcc_adam_ema_enqueue_step_scalars(
+            _cabi.call(
+                self.lib, "gcc_adam_ema_enqueue_step_scalars",
                 self.ptr(param), self.ptr(grad), self.ptr(exp_avg), self.ptr(exp_avg_sq), param.numel(), float(betas[0]),
                 float(betas[1]), float(eps), float(weight_decay), float(max_norm), float(grad_scale), self.ptr(grad_norm),
                 self.ptr(scratch), self.ptr(ema) if ema is not None else None, ema.numel() if ema is not None else 0,
@@ -173,42 +159,29 @@ class NceEngine:
                 self.ptr(parts) if parts is not None else None, int(nparts),
                 self.ptr(queue) if queue is not None else None, queue.shape[0] if queue is not None else 0,
                 self.ptr(keys) if keys is not None else None, keys.shape[0] if keys is not None else 0, stream)
-            if rc != 0:
-                raise RuntimeError(f"gcc_adam_ema_enqueue_step_scalars failed ({rc}): {self.lib.gcc_last_error().decode()}")
             return
         if scalars is not None:                      # lr / bias corrections from the device struct (replayed step)
-            rc = self.lib.gcc_adam_ema_step_scalars(
+            _cabi.call(
+                self.lib, "gcc_adam_ema_step_scalars",
                 self.ptr(param), self.ptr(grad), self.ptr(exp_avg), self.ptr(exp_avg_sq), param.numel(), float(betas[0]),
                 float(betas[1]), float(eps), float(weight_decay), float(max_norm), float(grad_scale), self.ptr(grad_norm),
                 self.ptr(scratch), self.ptr(ema) if ema is not None else None, ema.numel() if ema is not None else 0,
                 float(ema_m), ctypes.byref(ma) if ma is not None else None, self.ptr(scalars), stream)
-            if rc != 0:
-                raise RuntimeError(f"gcc_adam_ema_step_scalars failed ({rc}): {self.lib.gcc_last_error().decode()}")
             return
-        rc = self.lib.gcc_adam_ema_step(self.ptr(param), self.ptr(grad), self.ptr(exp_avg), self.ptr(exp_avg_sq),
-                                        param.numel(), float(lr), float(betas[0]), float(betas[1]), float(eps),
-                                        float(weight_decay), int(step), float(max_norm), float(grad_scale),
-                                        self.ptr(grad_norm), self.ptr(scratch),
-                                        self.ptr(ema) if ema is not None else None, ema.numel() if ema is not None else 0,
-                                        float(ema_m), ctypes.byref(ma) if ma is not None else None, stream)
-        if rc != 0:
-            raise RuntimeError(f"gcc_adam_ema_step failed ({rc}): {self.lib.gcc_last_error().decode()}")
+        _cabi.call(self.lib, "gcc_adam_ema_step", self.ptr(param), self.ptr(grad), self.ptr(exp_avg), self.ptr(exp_avg_sq),
+                   param.numel(), float(lr), float(betas[0]), float(betas[1]), float(eps),
+                   float(weight_decay), int(step), float(max_norm), float(grad_scale),
+                   self.ptr(grad_norm), self.ptr(scratch),
+                   self.ptr(ema) if ema is not None else None, ema.numel() if ema is not None else 0,
+                   float(ema_m), ctypes.byref(ma) if ma is not None else None, stream)
 
     def meters(self, acc, mx, loss, prob, grad_norm, q, k, stream=None):
-        rc = self.lib.gcc_step_meters(self.ptr(acc), self.ptr(mx), self.ptr(loss), self.ptr(prob), self.ptr(grad_norm),
-                                      self.ptr(q.node_off), self.ptr(q.edge_off), self.ptr(k.node_off),
-                                      int(q.batch_size), stream)
-        if rc != 0:
-            raise RuntimeError(f"gcc_step_meters failed ({rc}): {self.lib.gcc_last_error().decode()}")
+        _cabi.call(self.lib, "gcc_step_meters", self.ptr(acc), self.ptr(mx), self.ptr(loss), self.ptr(prob), self.ptr(grad_norm),
+                   self.ptr(q.node_off), self.ptr(q.edge_off), self.ptr(k.node_off),
+                   int(q.batch_size), stream)
 
     def ema(self, ema, p, m, stream=None):
-        rc = self.lib.gcc_ema_update(self.ptr(ema), self.ptr(p), ema.numel(), float(m), stream)
-        if rc != 0:
-            raise RuntimeError(f"gcc_ema_update failed ({rc}): {self.lib.gcc_last_error().decode()}")
-
-
-def _stream(t):
-    return torch.cuda.current_stream(t.device).cuda_stream if t.is_cuda else None
+        _cabi.call(self.lib, "gcc_ema_update", self.ptr(ema), self.ptr(p), ema.numel(), float(m), stream)
 
 
 class _MoCoLoss(torch.autograd.Function):
@@ -225,7 +198,7 @@ class _MoCoLoss(torch.autograd.Function):
         q, k = ctx.saved_tensors
         m = ctx.module
         dq = m.engine().backward(q, k, m.kernel_memory(), m.T, 0, ctx.outs, dloss, patch=ctx.patch,
-                                 patch_index=ctx.patch_index, stream=_stream(q))
+                                 patch_index=ctx.patch_index, stream=raw_stream(q))
         return dq, None, None, None, None, None
 
 
@@ -235,7 +208,7 @@ class _NSLoss(torch.autograd.Function):
     @staticmethod
     def forward(ctx, feat_q, feat_k, T, eng):
         fq, fk = feat_q.contiguous(), feat_k.contiguous()
-        outs = eng.forward(fk, None, fq, T, 1, stream=_stream(fq))     # rows = feat_k, columns = feat_q
+        outs = eng.forward(fk, None, fq, T, 1, stream=raw_stream(fq))     # rows = feat_k, columns = feat_q
         ctx.eng, ctx.T, ctx.outs = eng, T, outs
         ctx.save_for_backward(fq, fk)
         ctx.mark_non_differentiable(outs["prob"])
@@ -245,8 +218,8 @@ class _NSLoss(torch.autograd.Function):
     def backward(ctx, dloss, _dprob):
         fq, fk = ctx.saved_tensors
         eng, T, outs = ctx.eng, ctx.T, ctx.outs
-        dk = eng.backward(fk, None, fq, T, 1, outs, dloss, stream=_stream(fq))
-        dq = eng.backward(fq, None, fk, T, 1, outs, dloss, by_mem_row=True, stream=_stream(fq))
+        dk = eng.backward(fk, None, fq, T, 1, outs, dloss, stream=raw_stream(fq))
+        dq = eng.backward(fq, None, fk, T, 1, outs, dloss, by_mem_row=True, stream=raw_stream(fq))
         return dq, dk, None, None
 
 
@@ -276,17 +249,13 @@ class WideNceEngine:
                 self.ptr(o["grad_mem"]) if o["grad_mem"] is not None else None, self.ptr(o["loss"]),
                 self.ptr(o["prob"]), self.ptr(o["acc"]))
         if self.dtype == "f32":
-            rc, who = self.lib.gcc_ncex_forward(*args, stream), "gcc_ncex_forward"
+            _cabi.call(self.lib, "gcc_ncex_forward", *args, stream)
         else:
-            rc, who = self.lib.gcc_ncex_forward_dt(*args, _cabi.GEMM_DTYPES[self.dtype], stream), "gcc_ncex_forward_dt"
-        if rc != 0:
-            raise RuntimeError(f"{who} failed ({rc}): {self.lib.gcc_last_error().decode()}")
+            _cabi.call(self.lib, "gcc_ncex_forward_dt", *args, _cabi.GEMM_DTYPES[self.dtype], stream)
         return o
 
     def enqueue(self, mem, keys, index, stream=None):
-        rc = self.lib.gcc_queue_enqueue_x(self.ptr(mem), mem.shape[0], mem.shape[1], self.ptr(keys), keys.shape[0], int(index), stream)
-        if rc != 0:
-            raise RuntimeError(f"gcc_queue_enqueue_x failed ({rc}): {self.lib.gcc_last_error().decode()}")
+        _cabi.call(self.lib, "gcc_queue_enqueue_x", self.ptr(mem), mem.shape[0], mem.shape[1], self.ptr(keys), keys.shape[0], int(index), stream)
 
 
 class _WideLoss(torch.autograd.Function):
@@ -378,7 +347,7 @@ class MemoryMoCo(nn.Module):
     def _forward_wide(self, q, k):
         eng = self.engine()
         qc, kc = q.contiguous(), k.detach().contiguous()               # memory_moco.py:28
-        st = _stream(qc)
+        st = raw_stream(qc)
         o = eng.forward(qc.detach(), kc, self.memory, self.T, 0, stream=st)   # logits AND gradient vs the queue before the update
         keys = self.gather_keys(kc) if self.gather_keys is not None else kc
         with torch.no_grad():                                          # memory_moco.py:55-61
@@ -394,7 +363,7 @@ class MemoryMoCo(nn.Module):
         mem = self.kernel_memory()
         qc = self._pad(q).contiguous()                                 # (differentiable: the gradient comes back sliced)
         kc = self._pad(k.detach()).contiguous()                        # memory_moco.py:28
-        st = _stream(qc)
+        st = raw_stream(qc)
         outs = eng.forward(qc.detach(), kc, mem, self.T, 0, stream=st)   # logits vs the queue BEFORE the update
         keys = self.gather_keys(kc) if self.gather_keys is not None else kc
         index = self.index
@@ -412,9 +381,9 @@ class MemoryMoCo(nn.Module):
     def logits(self, q, k):
         """Dense ``out`` of memory_moco.py:40-44 without the enqueue side effect (tests, debugging)."""
         if self.wide:
-            return self.engine().forward(q.detach().contiguous(), k.detach().contiguous(), self.memory, self.T, 0, stream=_stream(q))["out"]
+            return self.engine().forward(q.detach().contiguous(), k.detach().contiguous(), self.memory, self.T, 0, stream=raw_stream(q))["out"]
         outs = self.engine().forward(self._pad(q.detach()).contiguous(), self._pad(k.detach()).contiguous(), self.kernel_memory(), self.T, 0,
-                                     dense=True, stream=_stream(q))
+                                     dense=True, stream=raw_stream(q))
         return outs["out"]
 
 
@@ -442,7 +411,7 @@ def e2e_logits(feat_q, feat_k, T, engine=None, nce_dtype="f32"):
     if feat_q.shape[1] > D:                        # --hidden-size above 64: the dense any-size head (csrc/ginx.hip)
         eng = engine if engine is not None else WideNceEngine(dtype=nce_dtype)
         fq, fk = feat_q.contiguous(), feat_k.contiguous()
-        o = eng.forward(fk.detach(), None, fq.detach(), T, 1, stream=_stream(fq))      # rows = feat_k, columns = feat_q
+        o = eng.forward(fk.detach(), None, fq.detach(), T, 1, stream=raw_stream(fq))      # rows = feat_k, columns = feat_q
         loss = _WideLoss.apply(fk, fq, o)
         return NCELogits(loss, o["prob"].reshape(()), None, (fq.shape[0], fq.shape[0]), lambda: o["out"])
     eng = engine if engine is not None else NceEngine()
@@ -453,7 +422,7 @@ def e2e_logits(feat_q, feat_k, T, engine=None, nce_dtype="f32"):
 
     def dense():
         return eng.forward(feat_k.detach().contiguous(), None, feat_q.detach().contiguous(), T, 1, dense=True,
-                           stream=_stream(feat_q))["out"]
+                           stream=raw_stream(feat_q))["out"]
 
     B = feat_q.shape[0]
     return NCELogits(loss, prob, None, (B, B), dense)

@@ -187,22 +187,14 @@ class GatEngine:
         w.normalize, w.norm_eps = int(enc.norm), 1e-5                     # graph_encoder.py:196
         return _fill_struct(w, [(n, i, t.detach()) for n, i, t in gat_params(enc)], self.ptr)
 
-    @staticmethod
-    def _stream(t, stream):
-        if stream is None and t.is_cuda:
-            return torch.cuda.current_stream(t.device).cuda_stream
-        return stream
-
     def forward(self, enc, g, stream=None):
         """-> (out [B, out_dim], saved, pass struct, weights struct)"""
-        stream = self._stream(g.node_off, stream)
+        stream = stream if stream is not None else _cabi.raw_stream(g.node_off)
         if g.pos_undirected is None:
             raise RuntimeError("the batch has no pos_undirected (run the positional embedding first)")
         w = self.weights(enc)
-        node_cap = g.parent_nid.numel() if hasattr(g, "parent_nid") else g.graph_id.numel()
-        n = self.lib.gcc_gat_saved_floats(ctypes.byref(w), node_cap, g.batch_size)
-        if n < 0:
-            raise RuntimeError(f"gcc_gat_saved_floats failed ({n}): {self.lib.gcc_last_error().decode()}")
+        node_cap = _cabi.node_cap(g)
+        n = _cabi.size_query(self.lib, "gcc_gat_saved_floats", ctypes.byref(w), node_cap, g.batch_size)
         dev = g.node_off.device
         saved = torch.empty(n, dtype=torch.float32, device=dev)
         out = torch.empty(g.batch_size, enc.output_dim, dtype=torch.float32, device=dev)
@@ -222,24 +214,18 @@ class GatEngine:
         p.batch_size, p.node_cap = g.batch_size, node_cap
         p.edge_multiplicity = int(getattr(g, "edge_multiplicity", 1))
         p.saved, p.out = ptr(saved), ptr(out)
-        rc = self.lib.gcc_gat_forward(ctypes.byref(p), ctypes.byref(w), stream)
-        if rc != 0:
-            raise RuntimeError(f"gcc_gat_forward failed ({rc}): {self.lib.gcc_last_error().decode()}")
+        _cabi.call(self.lib, "gcc_gat_forward", ctypes.byref(p), ctypes.byref(w), stream)
         return out, saved, p, w
 
     def backward(self, enc, p, w, dout, targets, accumulate=False, stream=None):
         """gradients into ``targets`` (tensors in :func:`gat_params` order)."""
-        stream = self._stream(dout, stream)
-        nbytes = self.lib.gcc_gat_backward_workspace_bytes(ctypes.byref(w), p.node_cap, p.batch_size)
-        if nbytes < 0:
-            raise RuntimeError(f"gcc_gat_backward_workspace_bytes failed ({nbytes}): {self.lib.gcc_last_error().decode()}")
+        stream = stream if stream is not None else _cabi.raw_stream(dout)
+        nbytes = _cabi.size_query(self.lib, "gcc_gat_backward_workspace_bytes", ctypes.byref(w), p.node_cap, p.batch_size)
         ws = torch.empty(nbytes, dtype=torch.uint8, device=dout.device)
         grads = _fill_struct(_cabi.GccGatGrads(), [(n, i, t) for (n, i, _), t in zip(gat_params(enc), targets)], self.ptr)
         dout = dout.contiguous()
-        rc = self.lib.gcc_gat_backward(ctypes.byref(p), ctypes.byref(w), self.ptr(dout), ctypes.byref(grads), int(accumulate),
-                                       self.ptr(ws), nbytes, stream)
-        if rc != 0:
-            raise RuntimeError(f"gcc_gat_backward failed ({rc}): {self.lib.gcc_last_error().decode()}")
+        _cabi.call(self.lib, "gcc_gat_backward", ctypes.byref(p), ctypes.byref(w), self.ptr(dout), ctypes.byref(grads), int(accumulate),
+                   self.ptr(ws), nbytes, stream)
         return targets
 
 
@@ -286,7 +272,7 @@ class GinEngine:
         ptr = self.ptr
         L = len(enc.gnn.ginlayers)
         enc.ensure_padded()
-        node_cap = g.parent_nid.numel() if hasattr(g, "parent_nid") else g.graph_id.numel()
+        node_cap = _cabi.node_cap(g)
         buf = self._buffers(slot, node_cap, g.batch_size, L, g.node_off.device)
         p = _cabi.GccGinPass()
         p.node_off, p.row_ptr, p.col_idx, p.graph_id = ptr(g.node_off), ptr(g.row_ptr), ptr(g.col_idx), ptr(g.graph_id)
@@ -333,22 +319,16 @@ class GinEngine:
         arr = (_cabi.GccGinPass * len(passes))(*passes)
         if fetch is not None:
             scalars, ring, ring_len, counter = fetch
-            rc = self.lib.gcc_gin_forward_fetch(arr, len(passes), self.ptr(scalars), ring.data_ptr(), int(ring_len),
-                                                self.ptr(counter), prof.handle if prof is not None else None, stream)
-            if rc != 0:
-                raise RuntimeError(f"gcc_gin_forward_fetch failed ({rc}): {self.lib.gcc_last_error().decode()}")
+            _cabi.call(self.lib, "gcc_gin_forward_fetch", arr, len(passes), self.ptr(scalars), ring.data_ptr(), int(ring_len),
+                       self.ptr(counter), prof.handle if prof is not None else None, stream)
             return
-        rc = self.lib.gcc_gin_forward(arr, len(passes), prof.handle if prof is not None else None, stream)
-        if rc != 0:
-            raise RuntimeError(f"gcc_gin_forward failed ({rc}): {self.lib.gcc_last_error().decode()}")
+        _cabi.call(self.lib, "gcc_gin_forward", arr, len(passes), prof.handle if prof is not None else None, stream)
 
     def eval_fused(self, passes, mean_out=None, stream=None):
         """gcc_gin_eval_fused: eval-mode passes (running statistics) as one launch, one workgroup per subgraph; with
         ``mean_out`` [B, 64] the mean of the passes' embeddings (generate.py:52)."""
         arr = (_cabi.GccGinPass * len(passes))(*passes)
-        rc = self.lib.gcc_gin_eval_fused(arr, len(passes), self.ptr(mean_out) if mean_out is not None else None, stream)
-        if rc != 0:
-            raise RuntimeError(f"gcc_gin_eval_fused failed ({rc}): {self.lib.gcc_last_error().decode()}")
+        _cabi.call(self.lib, "gcc_gin_eval_fused", arr, len(passes), self.ptr(mean_out) if mean_out is not None else None, stream)
 
     def backward(self, enc, p, buf, dfeat, targets=None, accumulate=False, stream=None, prof=None, sumsq=None):
         """Backward of a training-mode pass.  Gradients are written (or added, ``accumulate``) into
@@ -357,14 +337,12 @@ class GinEngine:
         (gcc_gin_backward_sumsq; not with ``accumulate``) -- the call then returns (targets, number of partials)."""
         ptr = self.ptr
         L = len(enc.gnn.ginlayers)
-        g = buf["_keepalive"][0]
-        node_cap = g.parent_nid.numel() if hasattr(g, "parent_nid") else g.graph_id.numel()
+        node_cap = _cabi.node_cap(buf["_keepalive"][0])
         nbytes = self.lib.gcc_gin_backward_workspace_bytes(node_cap, p.batch_size, L)
         key = ("bwd", nbytes, str(dfeat.device))
         if key not in self._bufs:
             self._bufs[key] = torch.empty(nbytes, dtype=torch.uint8, device=dfeat.device)
         ws = self._bufs[key]
-        grads = _cabi.GccGinGrads()
         plist = grad_params(enc)
         if targets is None:
             targets = []
@@ -372,26 +350,18 @@ class GinEngine:
                 if param.grad is None or (enc.is_padded() and not getattr(param.grad, "_gcc_padded", False)):
                     param.grad = enc.padded_zeros_like(param)
                 targets.append(param.grad)
-        for (name, idx, _), tgt in zip(plist, targets):
-            if idx is None:
-                setattr(grads, name, ptr(tgt))
-            else:
-                getattr(grads, name)[idx] = ptr(tgt)
+        grads = _fill_struct(_cabi.GccGinGrads(), [(n, i, t) for (n, i, _), t in zip(plist, targets)], ptr)
         dfeat = dfeat.contiguous()
         if sumsq is not None:
             if accumulate:
                 raise ValueError("sumsq: the partial sums are of what ONE backward pass stores (accumulate=False)")
             nparts = ctypes.c_int32(0)
-            rc = self.lib.gcc_gin_backward_sumsq(ctypes.byref(p), ptr(dfeat), ctypes.byref(grads), ptr(ws), nbytes, node_cap,
-                                                 ptr(sumsq), sumsq.numel(), ctypes.byref(nparts),
-                                                 prof.handle if prof is not None else None, stream)
-            if rc != 0:
-                raise RuntimeError(f"gcc_gin_backward_sumsq failed ({rc}): {self.lib.gcc_last_error().decode()}")
+            _cabi.call(self.lib, "gcc_gin_backward_sumsq", ctypes.byref(p), ptr(dfeat), ctypes.byref(grads), ptr(ws), nbytes, node_cap,
+                       ptr(sumsq), sumsq.numel(), ctypes.byref(nparts),
+                       prof.handle if prof is not None else None, stream)
             return targets, nparts.value
-        rc = self.lib.gcc_gin_backward(ctypes.byref(p), ptr(dfeat), ctypes.byref(grads), int(accumulate),
-                                       ptr(ws), nbytes, node_cap, prof.handle if prof is not None else None, stream)
-        if rc != 0:
-            raise RuntimeError(f"gcc_gin_backward failed ({rc}): {self.lib.gcc_last_error().decode()}")
+        _cabi.call(self.lib, "gcc_gin_backward", ctypes.byref(p), ptr(dfeat), ctypes.byref(grads), int(accumulate),
+                   ptr(ws), nbytes, node_cap, prof.handle if prof is not None else None, stream)
         return targets
 
 
@@ -614,7 +584,7 @@ class GraphEncoder(nn.Module):
                 fq = self(graph_q)
                 return fq.clone() if graph_k is graph_q else (fq + self(graph_k)) / 2
         eng = self.engine()
-        st = torch.cuda.current_stream(graph_q.node_off.device).cuda_stream if graph_q.node_off.is_cuda else None
+        st = _cabi.raw_stream(graph_q.node_off)
         views = [graph_q] if graph_k is graph_q else [graph_q, graph_k]        # entire_graph: both views are one graph
         passes, keep = [], []
         for i, g in enumerate(views):

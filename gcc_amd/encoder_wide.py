@@ -11,6 +11,8 @@ import ctypes
 import torch
 
 from . import _cabi
+from ._cabi import raw_stream
+from .encoder import STALE_SLOT_MSG, _fill_struct, fill_weights, grad_params
 
 
 class WideGinEngine:
@@ -24,16 +26,12 @@ class WideGinEngine:
         self._gen = {}                      # workspace key -> generation: a forward stamps its slot, a backward checks the stamp
 
     def make_pass(self, enc, g, training, keep=None, slot=0, want_pooled=False):
-        from .encoder import fill_weights
-
         ptr = self.ptr
         L = len(enc.gnn.ginlayers)
-        node_cap = g.parent_nid.numel() if hasattr(g, "parent_nid") else g.graph_id.numel()
+        node_cap = _cabi.node_cap(g)
         B, dev = g.batch_size, g.node_off.device
         d_in = enc.positional_embedding_size + enc.degree_embedding_size + 1
-        nbytes = self.lib.gcc_ginx_workspace_bytes(node_cap, B, L, d_in, enc.hidden, enc.output_dim)
-        if nbytes < 0:
-            raise RuntimeError(self.lib.gcc_last_error().decode())
+        nbytes = _cabi.size_query(self.lib, "gcc_ginx_workspace_bytes", node_cap, B, L, d_in, enc.hidden, enc.output_dim, named=False)
         key = (slot, nbytes, str(dev))
         if key not in self._ws:
             self._ws[key] = dict(ws=torch.zeros(nbytes, dtype=torch.uint8, device=dev),
@@ -64,33 +62,20 @@ class WideGinEngine:
         return p, out
 
     def forward(self, p, stream=None):
-        rc = self.lib.gcc_ginx_forward(ctypes.byref(p), stream)
-        if rc != 0:
-            raise RuntimeError(f"gcc_ginx_forward failed ({rc}): {self.lib.gcc_last_error().decode()}")
+        _cabi.call(self.lib, "gcc_ginx_forward", ctypes.byref(p), stream)
 
     def slot_is_current(self, buf):
         """False once a later forward has reused the workspace slot this pass's activations were stored in."""
         key, gen = buf["_slot"]
         return self._gen.get(key) == gen
 
-    def backward(self, enc, p, dfeat, targets, stream=None):
-        from .encoder import grad_params
-
-        grads = _cabi.GccGinGrads()
-        for (name, idx, _), tgt in zip(grad_params(enc), targets):
-            if idx is None:
-                setattr(grads, name, self.ptr(tgt))
-            else:
-                getattr(grads, name)[idx] = self.ptr(tgt)
+    def backward(self, enc, p, buf, dfeat, targets, stream=None):
+        """Gradients of the pass ``(p, buf)`` of :meth:`make_pass` into ``targets`` (tensors in :func:`grad_params` order): the
+        argument order of :meth:`GinEngine.backward` (the activations are addressed through ``p.workspace``)."""
+        grads = _fill_struct(_cabi.GccGinGrads(), [(n, i, t) for (n, i, _), t in zip(grad_params(enc), targets)], self.ptr)
         dfeat = dfeat.contiguous()
-        rc = self.lib.gcc_ginx_backward(ctypes.byref(p), self.ptr(dfeat), ctypes.byref(grads), stream)
-        if rc != 0:
-            raise RuntimeError(f"gcc_ginx_backward failed ({rc}): {self.lib.gcc_last_error().decode()}")
+        _cabi.call(self.lib, "gcc_ginx_backward", ctypes.byref(p), self.ptr(dfeat), ctypes.byref(grads), stream)
         return targets
-
-
-def _stream(t):
-    return torch.cuda.current_stream(t.device).cuda_stream if t.is_cuda else None
 
 
 class _GinxFn(torch.autograd.Function):
@@ -99,7 +84,7 @@ class _GinxFn(torch.autograd.Function):
         eng = enc.wide_engine()
         training = enc.bn_training()
         p, buf = eng.make_pass(enc, g, training=training, keep=keep, slot=enc.pass_slot(needs_backward), want_pooled=want_pooled)
-        eng.forward(p, stream=_stream(g.node_off))
+        eng.forward(p, stream=raw_stream(g.node_off))
         ctx.enc, ctx.p, ctx.buf = enc, p, buf
         L = len(enc.gnn.ginlayers)
         outs = [buf["feat"].clone()] + ([buf["pooled"][i].clone() for i in range(L)] if want_pooled else [])
@@ -108,22 +93,18 @@ class _GinxFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dfeat, *_unused):
-        from .encoder import STALE_SLOT_MSG, grad_params
-
         enc = ctx.enc
         if not ctx.p.training:
             raise RuntimeError("backward through an eval-mode (running statistics) pass is not supported")
         if not enc.wide_engine().slot_is_current(ctx.buf):
             raise RuntimeError(STALE_SLOT_MSG)
         targets = [torch.zeros_like(param) for _, _, param in grad_params(enc)]
-        enc.wide_engine().backward(enc, ctx.p, dfeat, targets, stream=_stream(dfeat))
+        enc.wide_engine().backward(enc, ctx.p, ctx.buf, dfeat, targets, stream=raw_stream(dfeat))
         return (None, None, None, None, None, *targets)
 
 
 def ginx_apply(enc, g, return_all_outputs=False):
     """GraphEncoder.forward (graph_encoder.py:132-200) on a BatchedCSR, any width."""
-    from .encoder import grad_params
-
     keep = None
     if enc.gnn.drop.training and enc.gnn.drop.p > 0:          # gin.py:202,230 nn.Dropout(0.5)
         L = len(enc.gnn.ginlayers)

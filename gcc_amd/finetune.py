@@ -18,7 +18,8 @@ import torch
 import torch.nn as nn
 
 from . import _cabi
-from .encoder import H, grad_params
+from .encoder import H
+from .train_step import flat_grad_views, flatten_parameters
 
 
 class ClsHeadEngine:
@@ -55,9 +56,7 @@ class ClsHeadEngine:
             acc, mx, g = meters
             a.meter_acc, a.meter_max = self.ptr(acc), self.ptr(mx)
             a.node_off, a.edge_off = self.ptr(g.node_off), self.ptr(g.edge_off)
-        rc = self.lib.gcc_cls_head_train(ctypes.byref(a), stream)
-        if rc != 0:
-            raise RuntimeError(f"gcc_cls_head_train failed ({rc}): {self.lib.gcc_last_error().decode()}")
+        _cabi.call(self.lib, "gcc_cls_head_train", ctypes.byref(a), stream)
         return out
 
     def eval(self, feat, W, b, labels, loss_sum, counts, logits=None, stream=None):
@@ -65,17 +64,13 @@ class ClsHeadEngine:
         a = self._args(feat, W, b, labels)
         a.logits = self.ptr(logits) if logits is not None else None
         a.eval_loss_sum, a.eval_counts = self.ptr(loss_sum), self.ptr(counts)
-        rc = self.lib.gcc_cls_head_eval(ctypes.byref(a), stream)
-        if rc != 0:
-            raise RuntimeError(f"gcc_cls_head_eval failed ({rc}): {self.lib.gcc_last_error().decode()}")
+        _cabi.call(self.lib, "gcc_cls_head_eval", ctypes.byref(a), stream)
 
     def adam_clipvalue(self, param, grad, exp_avg, exp_avg_sq, lr, betas, eps, weight_decay, step, clip_value,
                        grad_scale=1.0, stream=None):
-        rc = self.lib.gcc_adam_clipvalue_step(self.ptr(param), self.ptr(grad), self.ptr(exp_avg), self.ptr(exp_avg_sq),
-                                              param.numel(), lr, betas[0], betas[1], eps, weight_decay, int(step),
-                                              clip_value, grad_scale, stream)
-        if rc != 0:
-            raise RuntimeError(f"gcc_adam_clipvalue_step failed ({rc}): {self.lib.gcc_last_error().decode()}")
+        _cabi.call(self.lib, "gcc_adam_clipvalue_step", self.ptr(param), self.ptr(grad), self.ptr(exp_avg), self.ptr(exp_avg_sq),
+                   param.numel(), lr, betas[0], betas[1], eps, weight_decay, int(step),
+                   clip_value, grad_scale, stream)
 
 
 class FlatAdamClipValue:
@@ -141,19 +136,13 @@ class FinetuneTrainStep:
 
     def __init__(self, model, head: nn.Linear, learning_rate=0.005, betas=(0.9, 0.999), weight_decay=1e-5, clip_value=1.0,
                  engine=None):
-        from .train_step import flatten_parameters
-
         if model.wide:
             raise NotImplementedError("the fused fine-tuning step runs the 64-channel kernels; wider models take the API path")
         self.model, self.head = model, head
         self.dev = next(model.parameters()).device
         self.flat, self.n_live = flatten_parameters(model)
         self.live = self.flat[: self.n_live]
-        self.flat_grad = torch.zeros(self.n_live, dtype=torch.float32, device=self.dev)
-        self.grad_views, off = [], 0
-        for _, _, p in grad_params(model):
-            self.grad_views.append(self.flat_grad[off:off + p.numel()].view_as(p))
-            off += model.padded_numel(p)
+        self.flat_grad, self.grad_views = flat_grad_views(model, self.n_live, self.dev)
         self.hflat, self.hgrad, self.dW, self.db = flatten_head(head)
         self.gin = model.engine()
         self.eng = engine if engine is not None else ClsHeadEngine()
@@ -165,12 +154,9 @@ class FinetuneTrainStep:
         self._dfeat = {}
         self.last = None
 
-    def _stream(self):
-        return torch.cuda.current_stream(self.dev).cuda_stream if self.dev.type == "cuda" else None
-
     def step(self, step, graph_q, labels, lr):
         """one training step on the current stream; -> dict(loss, correct, logits, dlogits, feat) (device tensors)"""
-        st = self._stream()
+        st = _cabi.raw_stream(self.dev)
         model = self.model
         model.train()
         B = graph_q.batch_size
@@ -263,7 +249,7 @@ def evaluate(model, head, dataset, order, engine=None, stream=None):
     loss_sum = torch.zeros(1, dtype=torch.float64, device=dev)
     counts = torch.zeros(2, dtype=torch.int32, device=dev)
     W, b = head.weight.detach(), head.bias.detach()
-    st = torch.cuda.current_stream(dev).cuda_stream if dev.type == "cuda" else None
+    st = _cabi.raw_stream(dev)
     for graph_q, labels in dataset.batches(order):
         feat = embed_eval(model, graph_q, st)
         eng.eval(feat, W.contiguous(), b.contiguous(), labels, loss_sum, counts, stream=st)
@@ -291,7 +277,7 @@ class _ClsHeadFn(torch.autograd.Function):
         feat = feat.contiguous()
         dW, db = torch.empty_like(W), torch.empty_like(b)
         dfeat = torch.empty_like(feat)
-        st = torch.cuda.current_stream(feat.device).cuda_stream if feat.is_cuda else None
+        st = _cabi.raw_stream(feat)
         out = engine.train(feat, W.detach().contiguous(), b.detach().contiguous(), labels, dW, db, dfeat, stream=st)
         ctx.save_for_backward(dW, db, dfeat)
         ctx.mark_non_differentiable(out["logits"], out["correct"])

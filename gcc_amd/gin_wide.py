@@ -47,11 +47,10 @@ class FoldedWideGIN:
                     raise ValueError(f"{k} must be [{HIDDEN}]")
                 d[k] = v.to(self.device).contiguous()
             # the same weights in the order the kernel's waves request them (include/gcc_amd.h: gcc_ginw_pack_weights)
-            st = torch.cuda.current_stream(self.device).cuda_stream
+            st = _cabi.raw_stream(self.device)
             for which, k in enumerate(("w0", "w1")):
                 d[k + "_frag"] = torch.empty_like(d[k])
-                _cabi.check(self.lib.gcc_ginw_pack_weights(_cabi.dev_ptr(d[k]), _cabi.dev_ptr(d[k + "_frag"]), which, st),
-                            "gcc_ginw_pack_weights")
+                _cabi.call(self.lib, "gcc_ginw_pack_weights", _cabi.dev_ptr(d[k]), _cabi.dev_ptr(d[k + "_frag"]), which, st)
             self.layers.append(d)
         self.status = torch.zeros(1, dtype=torch.int32, device=self.device)
         self._scratch = None             # rows in transit + work list of subgraphs over 128 nodes (gcc_ginw_scratch_bytes)
@@ -96,9 +95,9 @@ class FoldedWideGIN:
             if self._scratch is None or self._scratch.numel() < need:
                 self._scratch = torch.empty(need, dtype=torch.uint8, device=self.device)
             a.scratch, a.scratch_bytes, a.num_nodes = _cabi.dev_ptr(self._scratch), need, x.shape[0]
-        st = torch.cuda.current_stream(self.device).cuda_stream
-        _cabi.check(self.lib.gcc_ginw_forward(ctypes.byref(a), _cabi.dev_ptr(self.status),
-                                              prof.handle if prof is not None else None, st), "gcc_ginw_forward")
+        st = _cabi.raw_stream(self.device)
+        _cabi.call(self.lib, "gcc_ginw_forward", ctypes.byref(a), _cabi.dev_ptr(self.status),
+                   prof.handle if prof is not None else None, st)
         return rows, pooled
 
     def check_status(self):

@@ -8,7 +8,11 @@ bench.py labels its output accordingly.
 """
 from __future__ import annotations
 
+import ctypes
+
 import torch
+
+from . import _cabi
 
 
 class PlaceholderPosEmb:
@@ -49,11 +53,6 @@ class DevicePosEmb:
 
     def __init__(self, batch_size, node_cap, hidden_size=32, device="cuda", seed=0, num_buffers=2, lib=None, ptr=None,
                  max_views=1):
-        import ctypes
-
-        from . import _cabi
-
-        self._ct, self._cabi = ctypes, _cabi
         self.lib = lib if lib is not None else _cabi.load()
         self.ptr = ptr if ptr is not None else _cabi.dev_ptr
         self.B, self.hidden, self.seed = int(batch_size), int(hidden_size), int(seed)
@@ -72,17 +71,15 @@ class DevicePosEmb:
     def __call__(self, graph, evals=None, raw=None, prof=None):
         out = self._ring[self._next]
         self._next = (self._next + 1) % len(self._ring)
-        c = self._cabi.GccBatchOut(node_off=self.ptr(graph.node_off), edge_off=0, parent_nid=0, graph_id=0,
-                                   row_ptr=self.ptr(graph.row_ptr), col_idx=self.ptr(graph.col_idx),
-                                   node_cap=out.shape[0], edge_cap=graph.col_idx.numel())
-        st = torch.cuda.current_stream(out.device).cuda_stream if out.is_cuda else None
-        rc = self.lib.gcc_posemb(self._ct.byref(c), self.B, self.hidden, self.ptr(out),
-                                 self.ptr(evals) if evals is not None else None,
-                                 self.ptr(raw) if raw is not None else None, self.seed,
-                                 self.ptr(self.workspace), self.nbytes, self.ptr(self.status),
-                                 prof.handle if prof is not None else None, st)
-        if rc != 0:
-            raise RuntimeError(f"gcc_posemb failed ({rc}): {self.lib.gcc_last_error().decode()}")
+        c = _cabi.GccBatchOut(node_off=self.ptr(graph.node_off), edge_off=0, parent_nid=0, graph_id=0,
+                              row_ptr=self.ptr(graph.row_ptr), col_idx=self.ptr(graph.col_idx),
+                              node_cap=out.shape[0], edge_cap=graph.col_idx.numel())
+        st = _cabi.raw_stream(out)
+        _cabi.call(self.lib, "gcc_posemb", ctypes.byref(c), self.B, self.hidden, self.ptr(out),
+                   self.ptr(evals) if evals is not None else None,
+                   self.ptr(raw) if raw is not None else None, self.seed,
+                   self.ptr(self.workspace), self.nbytes, self.ptr(self.status),
+                   prof.handle if prof is not None else None, st)
         graph.pos_undirected = out
         return graph
 
@@ -95,32 +92,32 @@ class DevicePosEmb:
                            evals=evals[i:i + self.max_views] if evals is not None else None,
                            raws=raws[i:i + self.max_views] if raws is not None else None, gate=gate)
             return graphs
-        views = (self._cabi.GccPosembView * len(graphs))()
+        views = (_cabi.GccPosembView * len(graphs))()
         keep = []
         for i, graph in enumerate(graphs):
             out = self._ring[self._next]
             self._next = (self._next + 1) % len(self._ring)
-            c = self._cabi.GccBatchOut(node_off=self.ptr(graph.node_off), edge_off=0, parent_nid=0, graph_id=0,
-                                       row_ptr=self.ptr(graph.row_ptr), col_idx=self.ptr(graph.col_idx),
-                                       node_cap=out.shape[0], edge_cap=graph.col_idx.numel())
+            c = _cabi.GccBatchOut(node_off=self.ptr(graph.node_off), edge_off=0, parent_nid=0, graph_id=0,
+                                  row_ptr=self.ptr(graph.row_ptr), col_idx=self.ptr(graph.col_idx),
+                                  node_cap=out.shape[0], edge_cap=graph.col_idx.numel())
             keep.append(c)
-            views[i] = self._cabi.GccPosembView(g=self._ct.addressof(c), pos=self.ptr(out),
-                                                evals=self.ptr(evals[i]) if evals is not None else None,
-                                                raw=self.ptr(raws[i]) if raws is not None else None)
+            views[i] = _cabi.GccPosembView(g=ctypes.addressof(c), pos=self.ptr(out),
+                                           evals=self.ptr(evals[i]) if evals is not None else None,
+                                           raw=self.ptr(raws[i]) if raws is not None else None)
             graph.pos_undirected = out
         dev = self._ring[0].device
-        st = torch.cuda.current_stream(dev).cuda_stream if dev.type == "cuda" else None
+        st = _cabi.raw_stream(dev)
         if gate is not None and dev.type == "cuda":
             wait, rec, self._gate_keep = gate.next_pair(torch.cuda.current_stream(dev))
             rc = self.lib.gcc_posemb_multi_gated(views, len(graphs), self.B, self.node_cap, self.hidden, self.seed,
                                                  self.ptr(self.workspace), self.nbytes, self.ptr(self.status),
                                                  prof.handle if prof is not None else None, wait, rec, st)
+            if rc != 0:                              # (reported under the ungated call's name, as ever)
+                raise RuntimeError(_cabi.error_text(self.lib, "gcc_posemb_multi", rc))
         else:
-            rc = self.lib.gcc_posemb_multi(views, len(graphs), self.B, self.node_cap, self.hidden, self.seed,
-                                           self.ptr(self.workspace), self.nbytes, self.ptr(self.status),
-                                           prof.handle if prof is not None else None, st)
-        if rc != 0:
-            raise RuntimeError(f"gcc_posemb_multi failed ({rc}): {self.lib.gcc_last_error().decode()}")
+            _cabi.call(self.lib, "gcc_posemb_multi", views, len(graphs), self.B, self.node_cap, self.hidden, self.seed,
+                       self.ptr(self.workspace), self.nbytes, self.ptr(self.status),
+                       prof.handle if prof is not None else None, st)
         return graphs
 
     def check_status(self, strict=False):

@@ -16,7 +16,7 @@ class Prof:
 
     def elapsed_ms(self, a: int, b: int) -> float:
         ms = ctypes.c_float(0.0)
-        _cabi.check(self.lib.gcc_prof_elapsed_ms(self.handle, a, b, ctypes.byref(ms)), "gcc_prof_elapsed_ms")
+        _cabi.call(self.lib, "gcc_prof_elapsed_ms", self.handle, a, b, ctypes.byref(ms))
         return float(ms.value)
 
     def __del__(self):

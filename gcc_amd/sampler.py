@@ -195,11 +195,10 @@ class DeviceRWRSampler:
             seeds=_cabi.dev_ptr(seeds, torch.int32) if seeds is not None else None,
             prof=prof.handle if prof is not None else None, hub_degree=self.hub_degree, max_hubs=self.max_hubs)
         cq, ck = q.c_struct(), k.c_struct()
-        rc = self.lib.gcc_sample_batch(
-            self.graph.byref(), ctypes.byref(params), ctypes.byref(cq), ctypes.byref(ck),
+        _cabi.call(
+            self.lib, "gcc_sample_batch", self.graph.byref(), ctypes.byref(params), ctypes.byref(cq), ctypes.byref(ck),
             self.workspace.data_ptr(), self.workspace.numel(), self.scratch_entries,
-            self.status.data_ptr(), torch.cuda.current_stream(self.graph.device).cuda_stream)
-        _cabi.check(rc, "gcc_sample_batch")
+            self.status.data_ptr(), _cabi.raw_stream(self.graph.device))
         self._last_steps = 1
         return q, k
 
@@ -207,8 +206,6 @@ class DeviceRWRSampler:
         """The batches of ``num_steps`` consecutive steps in one launch set (gcc_sample_multi): step t covers the sample
         ids ``first_sample_id + t * stride + [0, B)`` (``stride`` defaults to the batch size).  -> [(q, k)] per step, each
         pair in its own ring slot; every subgraph is bit for bit what :meth:`sample` gives for the same id."""
-        import torch
-
         B = self.batch_size
         stride = B if stride is None else int(stride)
         pairs = []
@@ -226,11 +223,9 @@ class DeviceRWRSampler:
                 run_seed=self.run_seed, first_sample_id=int(first_sample_id) + at * stride, batch_size=B,
                 restart_u32=self.graph.restart_u32, seeds=None,
                 prof=prof.handle if (prof is not None and at == 0) else None, hub_degree=self.hub_degree, max_hubs=self.max_hubs)
-            rc = self.lib.gcc_sample_multi(
-                self.graph.byref(), ctypes.byref(params), n, stride, outs, self.workspace.data_ptr(),
-                self.workspace.numel(), self.scratch_entries, self.status.data_ptr(),
-                torch.cuda.current_stream(self.graph.device).cuda_stream)
-            _cabi.check(rc, "gcc_sample_multi")
+            _cabi.call(
+                self.lib, "gcc_sample_multi", self.graph.byref(), ctypes.byref(params), n, stride, outs, self.workspace.data_ptr(),
+                self.workspace.numel(), self.scratch_entries, self.status.data_ptr(), _cabi.raw_stream(self.graph.device))
             self._last_steps = n
             at += n
         return pairs

@@ -16,9 +16,11 @@ from __future__ import annotations
 import gc
 import os
 import time
+import warnings
 
 import torch
 
+from ._cabi import raw_stream
 from .contrast import MemoryMoCo, NceEngine
 from .encoder import GraphEncoder, H, grad_params
 
@@ -62,18 +64,28 @@ def flatten_parameters(enc: GraphEncoder):
     return flat, n_live
 
 
+def flat_grad_views(enc: GraphEncoder, n_live, device):
+    """-> (flat fp32 gradient of the live parameters, its views in :func:`grad_params` order).  The views tile the buffer as the
+    parameters tile the live prefix of :func:`flatten_parameters`' buffer (zero-padded blocks when hidden < 64), so the
+    optimiser and the gradient all-reduce run over one buffer each."""
+    flat_grad = torch.zeros(n_live, dtype=torch.float32, device=device)
+    views, off = [], 0
+    for _, _, p in grad_params(enc):
+        views.append(flat_grad[off:off + p.numel()].view_as(p))
+        off += enc.padded_numel(p)
+    return flat_grad, views
+
+
 def moment_update(model, model_ema, m, engine: NceEngine | None = None):
     """train.py:169-172: model_ema = m * model_ema + (1 - m) * model over ALL parameters
     (the reference also averages the unused set2set / lin_readout weights)."""
     eng = engine or NceEngine()
     f1, f2 = getattr(model, "_flat", None), getattr(model_ema, "_flat", None)
     if f1 is not None and f2 is not None and f1.numel() == f2.numel():
-        st = torch.cuda.current_stream(f1.device).cuda_stream if f1.is_cuda else None
-        eng.ema(f2, f1, m, stream=st)
+        eng.ema(f2, f1, m, stream=raw_stream(f1))
         return
     for p1, p2 in zip(model.parameters(), model_ema.parameters()):
-        st = torch.cuda.current_stream(p2.device).cuda_stream if p2.is_cuda else None
-        eng.ema(p2.data, p1.detach().data.contiguous(), m, stream=st)
+        eng.ema(p2.data, p1.detach().data.contiguous(), m, stream=raw_stream(p2))
 
 
 def clip_grad_norm(params, max_norm):
@@ -120,7 +132,6 @@ class BatchProducer:
         # lane's heavy workgroups hold CUs at a time.  Measured (scripts/gpu/r3_call12.sh): no gain -- 1.29 vs 1.28 ms per
         # step sustained, the training kernels are as slow next to 64 heavy workgroups as next to 300 -- so it is OFF
         # unless GCC_POSEMB_GATE=1.
-        import os
         if gate_heavy is None:
             gate_heavy = os.environ.get("GCC_POSEMB_GATE", "0") == "1"
         self.gate = None
@@ -276,16 +287,11 @@ def _is_capture_error(e):
 
 
 def _hint_rows_once(engine, q, k):
-    if not hasattr(engine, "hint_rows"):         # (the any-width engine launches for the capacity)
-        return
-    _hint_rows_once_(engine, q, k)
-
-
-def _hint_rows_once_(engine, q, k):
     """The FIRST batch of a run tells the encoder engine how many rows a batch has (one host read of two device integers, once
     per run: every later step stays free of host synchronisation); :func:`read_meters` raises the estimate when a log line finds a
-    larger batch.  Graphs captured under an earlier estimate stay valid (any grid is correct)."""
-    if engine.rows_hint is None:
+    larger batch.  Graphs captured under an earlier estimate stay valid (any grid is correct).  (The any-width engine has no
+    ``hint_rows``: it launches for the capacity.)"""
+    if hasattr(engine, "hint_rows") and engine.rows_hint is None:
         B = q.batch_size
         engine.hint_rows(max(int(q.node_off[B].item()), int(k.node_off[B].item())))
 
@@ -340,7 +346,7 @@ class FlatAdam:
         device-side meters -- both inside the Adam launch (gcc_adam_ema_step) instead of launches of their own."""
         g = self.param_groups[0]
         self.steps += 1
-        st = torch.cuda.current_stream(self.param.device).cuda_stream if self.param.is_cuda else None
+        st = raw_stream(self.param)
         if ema is None and meters is None and scalars is None:
             self.engine.adam(self.param, self.grad, self.exp_avg, self.exp_avg_sq, g["lr"], g["betas"], g["eps"],
                              g["weight_decay"], self.steps, self.clip_norm, self.grad_norm, self._scratch, stream=st,
@@ -361,7 +367,8 @@ class FlatAdam:
 
 
 class _GraphedStep:
-    """hipGraph replay of a fused training step (shared by MoCoTrainStep and E2ETrainStep).
+    """What MoCoTrainStep and E2ETrainStep share: the flat buffers, the producer lanes, the step's stream and its hand-offs,
+    the status check, and hipGraph replay of the step's launches.
 
     A step is a FIXED sequence of launches whose arguments depend only on (a) which ring slot holds the batch and (b) a few
     scalars: lr, Adam's step count, the queue's ring pointer, the dropout key.  (b) lives in a device struct
@@ -373,6 +380,33 @@ class _GraphedStep:
     producer lanes' launches."""
 
     RING_LEN = 2048                         # entries of the pinned scalars ring (tests shrink it to exercise the wrap)
+    KEYS_PER_STEP = 1                       # dropout keys a step draws (the E2E step: one per view, both through ``model``)
+
+    def __init__(self, model, sampler, posemb, lanes, prefetch, depth, chunk, ahead, graph, collectives=False, **lane_kw):
+        """What the fused steps share: ``model``'s parameters re-homed into one flat buffer with a flat gradient beside it, the
+        device-side meters, the step's stream, the producer lanes in front of it (``lane_kw``: BatchProducer's CU reservation)
+        and the graph-replay state.  A subclass adds its engines ``self.gin`` / ``self.nce`` and ``self.optimizer``."""
+        self.model, self.sampler, self.posemb = model, sampler, posemb
+        self.collectives = collectives
+        self.dev = next(model.parameters()).device
+        self.flat, self.n_live = flatten_parameters(model)
+        self.flat_grad, self.grad_views = flat_grad_views(model, self.n_live, self.dev)
+        self.live = self.flat[: self.n_live]
+        self.mask_fn = None          # tests inject explicit dropout keep-masks here; default = in-kernel Philox (wide: torch.rand)
+        self.dropout_seed = 0x5EED0000
+        self.B = sampler.batch_size
+        self.one = torch.ones(1, device=self.dev)
+        self.meter_acc, self.meter_max = _meter_buffers(self.dev)
+        self.prefetch = prefetch and self.dev.type == "cuda"
+        # the ~75 short training kernels of a step must not queue behind the producers' millisecond-long
+        # eigensolver workgroups: the step runs on a high-priority stream
+        self.main = torch.cuda.Stream(self.dev, priority=-1) if self.prefetch else None
+        self.producer = BatchProducer(lanes if self.prefetch else lanes[:1], self._first_id,
+                                      self.dev if self.prefetch else "cpu", depth=depth if self.prefetch else 1,
+                                      chunk=chunk if self.prefetch else 1, ahead=ahead, **lane_kw)
+        if not self.prefetch:
+            self.producer.cuda = False
+        self._graph_init(graph)
 
     def _graph_init(self, graph):
         self.relaxed_streams = False        # see step(): drop the per-step stream hand-offs (bench.py / train.py loops)
@@ -447,7 +481,7 @@ class _GraphedStep:
             torch.cuda.synchronize(self.dev)
             self.ring_counter.fill_(self.ring_count)
             self._ring_dirty = False
-        regrown = getattr(getattr(self, "producer", None), "regrown", 0)
+        regrown = self.producer.regrown
         if regrown != self._graphs_regrown:
             # an edge-capacity regrow replaced every ring slot's col_idx: every key changed, the graphs captured over the
             # retired buffers are never replayed again.  They are dropped one regrow later (launches of theirs may be in flight).
@@ -527,7 +561,6 @@ class _GraphedStep:
             # due to a previous error during capture", with RCCL's threads busy beside the capturing one).  Nothing executed and
             # nothing is lost: the slot stays uncaptured, its next step is issued launch by launch and captured again afterwards.
             self.graph_capture_failures = getattr(self, "graph_capture_failures", 0) + 1
-            import warnings
             if self.graph_capture_failures > 4:
                 # not a stray event but the rule on this system: stop trying, every step is issued launch by launch from here on
                 self.use_graph = False
@@ -563,7 +596,6 @@ class _GraphedStep:
         if wait is not None:
             wait()
         else:                                    # (older torch: one watchdog period)
-            import time
             time.sleep(0.25)
 
     def _precapture_ready(self, st):
@@ -572,12 +604,9 @@ class _GraphedStep:
         as well, without an eager step of their own: a capture only records.  The steps that consume those slots are replays
         from the start instead of each paying an eager issue + a capture (+ 0.6 ms per step over the first lanes x depth x
         chunk steps of a run: what a 20-step window right after 5 warm-up steps measured)."""
-        prod = getattr(self, "producer", None)
-        if prod is None or not hasattr(self, "_capture_body"):
-            return
         self.graphs_precaptured = 0
-        for c in sorted(prod.ready):
-            pairs, _ev = prod.ready[c]
+        for c in sorted(self.producer.ready):
+            pairs, _ev = self.producer.ready[c]
             for q, k in pairs:
                 key = self._slot_key(q, k)
                 if key not in self.graphs and self._capture(key, self._capture_body(q, k, st)):
@@ -587,89 +616,6 @@ class _GraphedStep:
         """first launch of a step that uses the device-resident scalars: this step's ring entry -> the device struct"""
         if scalars is not None:
             self.nce.fetch_scalars(scalars, self.ring, self.ring_len, self.ring_counter, stream=st)
-
-
-class MoCoTrainStep(_GraphedStep):
-    def __init__(self, model: GraphEncoder, model_ema: GraphEncoder, contrast: MemoryMoCo, sampler, posemb,
-                 learning_rate=0.005, betas=(0.9, 0.999), weight_decay=1e-5, clip_norm=1.0, alpha=0.999,
-                 world_size=1, rank=0, prefetch=True, extra_lanes=(), depth=2, lanes=None, chunk=1, reserved_cus=0, cu_layout="interleaved",
-                 collectives=None, ahead=None, graph=None, flat_engine=None, fold=None, onepass_head=None):
-        """``sampler``/``posemb``: producer lane 0; ``extra_lanes``: more (sampler, posemb) pairs with their own
-        workspaces for multi-stream prefetch (see :class:`BatchProducer`).
-        ``graph``: replay the step's ~45 launches as ONE captured hipGraph per ring slot (default: on with prefetch on a
-        device, off with collectives -- see :meth:`_step`).
-        ``fold``: the folded launches of the 64-channel step that compute what the separate ones compute -- the scalars fetch
-        inside the step's first kernel, the clip's sum of squares inside the backward's last kernel, the enqueue inside the Adam
-        launch (default: on; ``GCC_STEP_FOLD=0`` or ``fold=False`` selects the separate launches: the A/B switch of
-        profiles/step_fold_bench_ab.txt).
-        ``onepass_head``: the head as one pass over the queue (gcc_nce_forward_backward, two launches instead of four).  OFF
-        unless asked for (``GCC_STEP_ONEPASS_HEAD=1``): it adds the same terms in another order, d loss / d q moves by ~1e-7
-        relative, and Adam turns that into visibly different weights within a few steps (DESIGN.md 5) -- a training run is no
-        longer the run the four launches give."""
-        self.model, self.ema, self.contrast = model, model_ema, contrast
-        self.fold = (os.environ.get("GCC_STEP_FOLD", "1") != "0") if fold is None else bool(fold)
-        self.onepass_head = (os.environ.get("GCC_STEP_ONEPASS_HEAD", "0") == "1") if onepass_head is None else bool(onepass_head)
-        self.sampler, self.posemb = sampler, posemb
-        self.clip_norm, self.alpha = clip_norm, alpha
-        self.world, self.rank = world_size, rank
-        # collectives run whenever there is more than one rank (``collectives=True`` forces them at world_size 1: tests)
-        self.collectives = world_size > 1 if collectives is None else bool(collectives)
-        self.dev = next(model.parameters()).device
-        self.flat, self.n_live = flatten_parameters(model)
-        self.flat_ema, n2 = flatten_parameters(model_ema)
-        assert n2 == self.n_live and self.flat.numel() == self.flat_ema.numel()
-        # gradient buffer: views in grad_params order
-        self.flat_grad = torch.zeros(self.n_live, dtype=torch.float32, device=self.dev)
-        self.grad_views, off = [], 0
-        for _, _, p in grad_params(model):                              # (blocks are zero-padded when hidden < 64)
-            self.grad_views.append(self.flat_grad[off:off + p.numel()].view_as(p))
-            off += model.padded_numel(p)
-        self.live = self.flat[: self.n_live]
-        # --hidden-size above 64 (train.py:93): the any-width kernels of csrc/ginx.hip (one launch per operator; dense head) under the
-        # SAME step -- producer lanes, flat buffers, clip + Adam + EMA + meters as two launches, key all-gather / gradient all-reduce
-        # across ranks -- issued launch by launch (their enqueue index / learning rate are by-value arguments: no graph replay)
-        self.wide = bool(model.wide or contrast.wide)
-        if self.wide and not (model.wide and contrast.wide and model_ema.wide):
-            raise ValueError("a wide step needs a wide encoder pair AND a wide head (hidden-size and MemoryMoCo's feature size above 64)")
-        self.gin = model.wide_engine() if self.wide else model.engine()
-        self.nce = contrast.engine()
-        # Adam(lr, betas, weight_decay as L2) over exactly the parameters that get gradients, train.py:667-672
-        self.optimizer = FlatAdam(self.live, self.flat_grad, learning_rate, betas, weight_decay, clip_norm,
-                                  (flat_engine or NceEngine()) if self.wide else self.nce)      # (the flat-buffer kernels live in csrc/nce.hip; ``flat_engine``: tests)
-        self.mask_fn = None          # tests inject explicit dropout keep-masks here; default = in-kernel Philox (wide: torch.rand)
-        self.dropout_seed = 0x5EED0000
-        self.B = sampler.batch_size
-        if contrast.queueSize < self.B * world_size:
-            # memory_moco.py:55-61 enqueues all keys of a step with fmod indices; more keys than queue rows would make
-            # rows collide (the reference's index_copy_ result is then order dependent), gcc_queue_enqueue refuses it
-            raise ValueError(f"nce_k = {contrast.queueSize} is smaller than the {self.B * world_size} keys enqueued per step "
-                             f"(batch_size {self.B} x world {world_size}): raise --nce-k")
-        self.L = len(model.gnn.ginlayers)
-        self.keys_all = torch.empty(self.B * world_size, contrast.inputSize if self.wide else H, device=self.dev) if self.collectives else None
-        self.one = torch.ones(1, device=self.dev)
-        self.meter_acc, self.meter_max = _meter_buffers(self.dev)
-        self.prefetch = prefetch and self.dev.type == "cuda"
-        # the ~75 short training kernels of a step must not queue behind the producers' millisecond-long
-        # eigensolver workgroups: the step runs on a high-priority stream
-        self.main = torch.cuda.Stream(self.dev, priority=-1) if self.prefetch else None
-        lanes = list(lanes) if lanes is not None else [(sampler, posemb)] + list(extra_lanes)
-        self.producer = BatchProducer(lanes if self.prefetch else lanes[:1], self._first_id,
-                                      self.dev if self.prefetch else "cpu", depth=depth if self.prefetch else 1,
-                                      chunk=chunk if self.prefetch else 1, reserved_cus=reserved_cus, cu_layout=cu_layout,
-                                      ahead=ahead)
-        if not self.prefetch:
-            self.producer.cuda = False
-        if self.wide and graph:
-            raise ValueError("graph replay is the 64-channel step's (device-resident scalars); the wide step is issued launch by launch")
-        self._graph_init(False if self.wide else graph)
-        model.train()                                                    # train.py:357-365
-        model_ema.eval()
-        for mod in model_ema.modules():
-            if isinstance(mod, torch.nn.BatchNorm1d):
-                mod.train()
-
-    def _first_id(self, step):
-        return (step * self.world + self.rank) * self.B
 
     def check_status(self, strict_posemb=False):
         """Synchronising check of the device status words of EVERY producer lane: sampler overflows (scratch / node /
@@ -709,32 +655,6 @@ class MoCoTrainStep(_GraphedStep):
     def _staged(self):
         return self.dev.type == "cuda" and torch.distributed.get_backend() == "gloo"
 
-    def _all_gather_begin(self, out, x):
-        """Key all-gather issued right after the encoder forward: RCCL runs it on its own stream (after the
-        work queued on the current one so far); nothing on the training stream waits for it until
-        :meth:`_all_gather_end`, just before the enqueue -- the InfoNCE forward / backward and the whole encoder
-        backward do not need ``keys_all`` (they read the queue as it was before the enqueue)."""
-        if self._staged():
-            return ("staged", out, x)
-        return ("rccl", torch.distributed.all_gather_into_tensor(out, x, async_op=True))
-
-    def _all_gather_end(self, pending):
-        if pending[0] == "staged":
-            _, out, x = pending
-            o, xi = out.cpu(), x.cpu()
-            torch.distributed.all_gather_into_tensor(o, xi)
-            out.copy_(o)
-        else:
-            pending[1].wait()                   # the current stream waits for RCCL's stream; the host does not
-
-    def _all_reduce(self, x):
-        if self._staged():
-            xi = x.cpu()
-            torch.distributed.all_reduce(xi)
-            x.copy_(xi)
-        else:
-            torch.distributed.all_reduce(x)
-
     # ---- one step
     def step(self, step, lr, prof=None):
         """``prof``: optional dict of gcc_amd.prof.Prof (sampler: 4 marks; gin_fwd/nce_fwd/nce_bwd/gin_bwd: 2).
@@ -768,21 +688,20 @@ class MoCoTrainStep(_GraphedStep):
             torch.cuda.current_stream(self.dev).wait_stream(self.main)
             self._joined_caller = False          # whatever the caller enqueues next is waited for by the next step
 
-    def _step(self, step, lr, prof=None):
+    def _step(self, step, lr, prof=None, enqueue_index=0):
         pr = prof or {}
         self._release_pending()
         q, k = self.producer.get(step, prof=prof)
         _hint_rows_once(self.gin, q, k)
-        st = torch.cuda.current_stream(self.dev).cuda_stream if self.dev.type == "cuda" else None
-        p_drop = self.model.gnn.drop.p
+        st = raw_stream(self.dev)
         keep = self.mask_fn() if self.mask_fn is not None else None
-        seed = (self.dropout_seed + step * 0x9E3779B97F4A7C15) & 0xFFFFFFFFFFFFFFFF if p_drop > 0 else None
-        c = self.contrast
+        seed = None
+        if self.model.gnn.drop.p > 0:
+            seed = (self.dropout_seed + self.KEYS_PER_STEP * step * 0x9E3779B97F4A7C15) & 0xFFFFFFFFFFFFFFFF
         for grp in self.optimizer.param_groups:                          # train.py:411-416
             grp["lr"] = lr
-        out = self._run_step(q, k, lr, seed, c.index, keep is not None, pr, st,
+        out = self._run_step(q, k, lr, seed, enqueue_index, keep is not None, pr, st,
                              lambda scalars, marks: self._body(q, k, keep, seed, scalars, marks, st))
-        c.index = (c.index + self.B * (self.world if self.collectives else 1)) % c.queueSize
         self._pending_release = step
         return dict(out, graph_q=q, graph_k=k)
 
@@ -797,56 +716,103 @@ class MoCoTrainStep(_GraphedStep):
             self._pending_release = None
             self.producer.release(step)
 
-    def _body_wide(self, q, k, keep, S, st):
-        """:meth:`MoCoTrainStep._body` on the any-width kernels (csrc/ginx.hip; train.py:93 ``--hidden-size`` above 64): the same five
-        stages -- forward of both views | key all-gather begins | head + encoder backward | gradient all-reduce, gather joined | clip +
-        Adam + EMA + meters, enqueue -- with explicit dropout masks (torch.rand on the device, as nn.Dropout draws them: gin.py:202,230)
-        and by-value scalars."""
-        c, enc = self.contrast, self.model
-        p_drop = enc.gnn.drop.p
-
-        def fwd():
-            kq = keep
-            if kq is None and p_drop > 0:
-                kq = (torch.rand(len(enc.gnn.ginlayers) + 1, self.B, enc.output_dim, device=self.dev) >= p_drop).float()
-            S["pq"], S["bufq"] = self.gin.make_pass(enc, q, training=True, keep=kq, slot=("step", 0))
-            S["pk"], S["bufk"] = self.gin.make_pass(self.ema, k, training=True, keep=None, slot=("step", 1))
-            self.gin.forward(S["pq"], stream=st)                             # train.py:389
-            self.gin.forward(S["pk"], stream=st)                             # train.py:390-391
-            self.last_bufs = (S["bufq"], S["bufk"])                          # (tests / bench.py's parity step read the embeddings here)
-
-        def gather_begin():
-            S["gathering"] = self._all_gather_begin(self.keys_all, S["bufk"]["feat"])
-
-        def head_and_backward():
-            # logits, loss and d loss / d q against the queue BEFORE the enqueue (memory_moco.py:31 clones it): train.py:393,407-408
-            S["outs"] = self.nce.forward(S["bufq"]["feat"], S["bufk"]["feat"], c.memory, c.T, 0, stream=st)
-            self.gin.backward(enc, S["pq"], S["outs"]["grad_rows"], self.grad_views, stream=st)
-
-        def reduce_and_join():
-            self._all_reduce(self.flat_grad)
-            self._all_gather_end(S["gathering"])
-
-        def update():
-            outs = S["outs"]
-            S["gnorm"] = self.optimizer.step(grad_scale=1.0 / self.world if self.collectives else 1.0,
-                                             ema=self.flat_ema, ema_src=self.flat, ema_m=self.alpha,
-                                             meters=(self.meter_acc, self.meter_max, outs["loss"], outs["prob"], q, k), scalars=None)
-            keys = self.keys_all if self.collectives else S["bufk"]["feat"]
-            self.nce.enqueue(c.memory, keys, c.index, stream=st)             # memory_moco.py:55-61
-
-        def result():
-            return dict(loss=S["outs"]["loss"], prob=S["outs"]["prob"], grad_norm=S["gnorm"])
-
-        if self.collectives:
-            segments = [(False, fwd), (False, gather_begin), (False, head_and_backward), (False, reduce_and_join), (False, update)]
-        else:
-            segments = [(False, lambda: (fwd(), head_and_backward(), update()))]
-        return segments, result
-
     def _capture_body(self, q, k, st):
         seed = 0 if self.model.gnn.drop.p > 0 else None              # (with scalars only dropout on / off matters here)
         return lambda scalars, marks: self._body(q, k, None, seed, scalars, marks, st)
+
+
+class MoCoTrainStep(_GraphedStep):
+    def __init__(self, model: GraphEncoder, model_ema: GraphEncoder, contrast: MemoryMoCo, sampler, posemb,
+                 learning_rate=0.005, betas=(0.9, 0.999), weight_decay=1e-5, clip_norm=1.0, alpha=0.999,
+                 world_size=1, rank=0, prefetch=True, extra_lanes=(), depth=2, lanes=None, chunk=1, reserved_cus=0, cu_layout="interleaved",
+                 collectives=None, ahead=None, graph=None, flat_engine=None, fold=None, onepass_head=None):
+        """``sampler``/``posemb``: producer lane 0; ``extra_lanes``: more (sampler, posemb) pairs with their own
+        workspaces for multi-stream prefetch (see :class:`BatchProducer`).
+        ``graph``: replay the step's ~45 launches as ONE captured hipGraph per ring slot (default: on with prefetch on a
+        device, off with collectives -- see :meth:`_step`).
+        ``fold``: the folded launches of the 64-channel step that compute what the separate ones compute -- the scalars fetch
+        inside the step's first kernel, the clip's sum of squares inside the backward's last kernel, the enqueue inside the Adam
+        launch (default: on; ``GCC_STEP_FOLD=0`` or ``fold=False`` selects the separate launches: the A/B switch of
+        profiles/step_fold_bench_ab.txt).
+        ``onepass_head``: the head as one pass over the queue (gcc_nce_forward_backward, two launches instead of four).  OFF
+        unless asked for (``GCC_STEP_ONEPASS_HEAD=1``): it adds the same terms in another order, d loss / d q moves by ~1e-7
+        relative, and Adam turns that into visibly different weights within a few steps (DESIGN.md 5) -- a training run is no
+        longer the run the four launches give."""
+        self.ema, self.contrast = model_ema, contrast
+        self.fold = (os.environ.get("GCC_STEP_FOLD", "1") != "0") if fold is None else bool(fold)
+        self.onepass_head = (os.environ.get("GCC_STEP_ONEPASS_HEAD", "0") == "1") if onepass_head is None else bool(onepass_head)
+        self.clip_norm, self.alpha = clip_norm, alpha
+        self.world, self.rank = world_size, rank
+        # --hidden-size above 64 (train.py:93): the any-width kernels of csrc/ginx.hip (one launch per operator; dense head) under the
+        # SAME step -- producer lanes, flat buffers, clip + Adam + EMA + meters as two launches, key all-gather / gradient all-reduce
+        # across ranks -- issued launch by launch (their enqueue index / learning rate are by-value arguments: no graph replay)
+        self.wide = bool(model.wide or contrast.wide)
+        if self.wide and not (model.wide and contrast.wide and model_ema.wide):
+            raise ValueError("a wide step needs a wide encoder pair AND a wide head (hidden-size and MemoryMoCo's feature size above 64)")
+        if self.wide and graph:
+            raise ValueError("graph replay is the 64-channel step's (device-resident scalars); the wide step is issued launch by launch")
+        if contrast.queueSize < sampler.batch_size * world_size:
+            # memory_moco.py:55-61 enqueues all keys of a step with fmod indices; more keys than queue rows would make
+            # rows collide (the reference's index_copy_ result is then order dependent), gcc_queue_enqueue refuses it
+            raise ValueError(f"nce_k = {contrast.queueSize} is smaller than the {sampler.batch_size * world_size} keys enqueued per step "
+                             f"(batch_size {sampler.batch_size} x world {world_size}): raise --nce-k")
+        # collectives run whenever there is more than one rank (``collectives=True`` forces them at world_size 1: tests)
+        super().__init__(model, sampler, posemb, list(lanes) if lanes is not None else [(sampler, posemb)] + list(extra_lanes),
+                         prefetch, depth, chunk, ahead, False if self.wide else graph,
+                         collectives=world_size > 1 if collectives is None else bool(collectives),
+                         reserved_cus=reserved_cus, cu_layout=cu_layout)
+        self.flat_ema, n2 = flatten_parameters(model_ema)
+        assert n2 == self.n_live and self.flat.numel() == self.flat_ema.numel()
+        self.gin = model.wide_engine() if self.wide else model.engine()
+        self.nce = contrast.engine()
+        # Adam(lr, betas, weight_decay as L2) over exactly the parameters that get gradients, train.py:667-672
+        self.optimizer = FlatAdam(self.live, self.flat_grad, learning_rate, betas, weight_decay, clip_norm,
+                                  (flat_engine or NceEngine()) if self.wide else self.nce)      # (the flat-buffer kernels live in csrc/nce.hip; ``flat_engine``: tests)
+        self.L = len(model.gnn.ginlayers)
+        self.keys_all = torch.empty(self.B * world_size, contrast.inputSize if self.wide else H, device=self.dev) if self.collectives else None
+        model.train()                                                    # train.py:357-365
+        model_ema.eval()
+        for mod in model_ema.modules():
+            if isinstance(mod, torch.nn.BatchNorm1d):
+                mod.train()
+
+    def _first_id(self, step):
+        return (step * self.world + self.rank) * self.B
+
+    def _all_gather_begin(self, out, x):
+        """Key all-gather issued right after the encoder forward: RCCL runs it on its own stream (after the
+        work queued on the current one so far); nothing on the training stream waits for it until
+        :meth:`_all_gather_end`, just before the enqueue -- the InfoNCE forward / backward and the whole encoder
+        backward do not need ``keys_all`` (they read the queue as it was before the enqueue)."""
+        if self._staged():
+            return ("staged", out, x)
+        return ("rccl", torch.distributed.all_gather_into_tensor(out, x, async_op=True))
+
+    def _all_gather_end(self, pending):
+        if pending[0] == "staged":
+            _, out, x = pending
+            o, xi = out.cpu(), x.cpu()
+            torch.distributed.all_gather_into_tensor(o, xi)
+            out.copy_(o)
+        else:
+            pending[1].wait()                   # the current stream waits for RCCL's stream; the host does not
+
+    def _all_reduce(self, x):
+        if self._staged():
+            xi = x.cpu()
+            torch.distributed.all_reduce(xi)
+            x.copy_(xi)
+        else:
+            torch.distributed.all_reduce(x)
+
+    def _step(self, step, lr, prof=None):
+        c = self.contrast
+        out = super()._step(step, lr, prof, enqueue_index=c.index)
+        c.index = (c.index + self.B * (self.world if self.collectives else 1)) % c.queueSize
+        return out
+
+    def _body_wide(self, q, k, keep, S, st):     # bench.py's wide_step_roofline calls this
+        return self._body(q, k, keep, None, None, {}, st)
 
     def _body(self, q, k, keep, seed, scalars, pr, st):
         """The launches of one step on the current stream as (segments, result) for :meth:`_run_step` (eager, or under stream
@@ -854,20 +820,32 @@ class MoCoTrainStep(_GraphedStep):
         arguments.  Without collectives the step is one capturable segment; with them:
             forward (q, k)  |  key all-gather begins (RCCL, own stream)  |  head fwd + bwd, encoder bwd  |
             gradient all-reduce, all-gather joined  |  clip + Adam + EMA + meters, enqueue
-        -- three captured graphs with the two RCCL hand-offs issued between their launches."""
+        -- three captured graphs with the two RCCL hand-offs issued between their launches.
+        Both widths run this body.  The any-width kernels (csrc/ginx.hip; train.py:93 ``--hidden-size`` above 64) differ in how the
+        two forward passes are made and launched (one pass per call, explicit dropout masks: torch.rand on the device, as nn.Dropout
+        draws them, gin.py:202,230), in where d loss / d q comes from (the dense head's forward call) and in taking every scalar by
+        value (``scalars`` is None: the wide step is never captured)."""
         S = {}
-        c = self.contrast
-        if self.wide:
-            return self._body_wide(q, k, keep, S, st)
+        c, enc = self.contrast, self.model
 
         def fwd():
+            if self.wide:
+                kq = keep
+                if kq is None and enc.gnn.drop.p > 0:
+                    kq = (torch.rand(self.L + 1, self.B, enc.output_dim, device=self.dev) >= enc.gnn.drop.p).float()
+                S["pq"], S["bufq"] = self.gin.make_pass(enc, q, training=True, keep=kq, slot=("step", 0))
+                S["pk"], S["bufk"] = self.gin.make_pass(self.ema, k, training=True, keep=None, slot=("step", 1))
+                self.gin.forward(S["pq"], stream=st)                             # train.py:389
+                self.gin.forward(S["pk"], stream=st)                             # train.py:390-391
+                self.last_bufs = (S["bufq"], S["bufk"])                          # (tests / bench.py's parity step read the embeddings here)
+                return
             fetch = None
             if self.fold and scalars is not None:      # the fetch rides in the forward's first kernel
                 fetch = (scalars, self.ring, self.ring_len, self.ring_counter)
             else:
                 self._fetch_scalars(scalars, st)
             # (with scalars the by-value seed is an addend to the device-resident one: 0 here)
-            S["pq"], S["bufq"] = self.gin.make_pass(self.model, q, training=True, keep=keep, slot=("step", 0),
+            S["pq"], S["bufq"] = self.gin.make_pass(enc, q, training=True, keep=keep, slot=("step", 0),
                                                     dropout_seed=(0 if seed is not None else None) if scalars is not None else seed,
                                                     scalars=scalars)
             S["pk"], S["bufk"] = self.gin.make_pass(self.ema, k, training=True, keep=None, slot=("step", 1), backward=False)
@@ -882,20 +860,24 @@ class MoCoTrainStep(_GraphedStep):
             # The enqueue (memory_moco.py:55-61) is the LAST thing the step does with the queue: logits and their backward
             # are taken against the queue before the update (the reference clones it, memory_moco.py:31), so deferring the
             # update is the same computation -- and it takes the key all-gather off the critical chain.
-            if self.onepass_head:            # loss and d loss / d q in one pass over the queue (two launches; bf16 keeps the four)
+            if self.wide:                    # the dense head: logits, loss and d loss / d q in its forward call (train.py:393,407-408)
+                S["outs"] = self.nce.forward(feat_q, feat_k, mem, c.T, 0, stream=st)
+                dq = S["outs"]["grad_rows"]
+            elif self.onepass_head:          # loss and d loss / d q in one pass over the queue (two launches; bf16 keeps the four)
                 S["outs"], dq = self.nce.forward_backward(feat_q, feat_k, mem, c.T, self.one, stream=st,
                                                           prof_fwd=pr.get("nce_fwd"), prof_bwd=pr.get("nce_bwd"))
             else:
                 S["outs"] = self.nce.forward(feat_q, feat_k, mem, c.T, 0, stream=st, prof=pr.get("nce_fwd"))   # train.py:393,407
                 dq = self.nce.backward(feat_q, feat_k, mem, c.T, 0, S["outs"], self.one, stream=st,
                                        prof=pr.get("nce_bwd"))                    # loss.backward(), train.py:408
+            kw = {} if self.wide else dict(prof=pr.get("gin_bwd"))
             if self.fold and scalars is not None and not self.collectives:
                 # nothing touches the gradient between the backward's last kernel and Adam: its sum of squares is taken there
-                _, n = self.gin.backward(self.model, S["pq"], S["bufq"], dq, targets=self.grad_views, stream=st,
-                                         prof=pr.get("gin_bwd"), sumsq=self.optimizer.sumsq_parts)
+                _, n = self.gin.backward(enc, S["pq"], S["bufq"], dq, targets=self.grad_views, stream=st,
+                                         sumsq=self.optimizer.sumsq_parts, **kw)
                 S["sumsq"] = (self.optimizer.sumsq_parts, n)
             else:
-                self.gin.backward(self.model, S["pq"], S["bufq"], dq, targets=self.grad_views, stream=st, prof=pr.get("gin_bwd"))
+                self.gin.backward(enc, S["pq"], S["bufq"], dq, targets=self.grad_views, stream=st, **kw)
 
         def reduce_and_join():
             self._all_reduce(self.flat_grad)                             # SUM of one flat bucket (248 KiB) over xGMI
@@ -916,7 +898,8 @@ class MoCoTrainStep(_GraphedStep):
                                              meters=(self.meter_acc, self.meter_max, outs["loss"], outs["prob"], q, k),
                                              scalars=scalars)
             keys = self.keys_all if self.collectives else S["bufk"]["feat"]
-            self.nce.enqueue(c.kernel_memory(), keys, c.index, save=False, stream=st, scalars=scalars)
+            kw = {} if self.wide else dict(save=False, scalars=scalars)          # memory_moco.py:55-61
+            self.nce.enqueue(c.kernel_memory(), keys, c.index, stream=st, **kw)
 
         def result():
             return dict(loss=S["outs"]["loss"], prob=S["outs"]["prob"], grad_norm=S["gnorm"])
@@ -938,74 +921,29 @@ class E2ETrainStep(_GraphedStep):
     both passes accumulated into one flat buffer, clip + Adam as two launches.  Same producer pipeline as
     :class:`MoCoTrainStep`; single GPU (the reference has no data-parallel E2E mode)."""
 
+    KEYS_PER_STEP = 2
+
     def __init__(self, model: GraphEncoder, sampler, posemb, nce_t=0.07, learning_rate=0.005, betas=(0.9, 0.999),
                  weight_decay=1e-5, clip_norm=1.0, prefetch=True, depth=2, lanes=None, chunk=1, ahead=None, engine=None,
                  graph=None):
-        self.model = model
-        self.sampler, self.posemb = sampler, posemb
         self.T, self.clip_norm = nce_t, clip_norm
-        self.world, self.rank, self.collectives = 1, 0, False
-        self.dev = next(model.parameters()).device
-        self.flat, self.n_live = flatten_parameters(model)
-        self.flat_grad = torch.zeros(self.n_live, dtype=torch.float32, device=self.dev)
-        self.grad_views, off = [], 0
-        for _, _, p in grad_params(model):
-            self.grad_views.append(self.flat_grad[off:off + p.numel()].view_as(p))
-            off += model.padded_numel(p)
-        self.live = self.flat[: self.n_live]
+        self.world, self.rank = 1, 0
+        # graph replay is available but OFF by default here: measured 1.241 vs 1.240 ms per step at bsz 256 and 0.872 vs
+        # 0.806 ms at bsz 32 (scripts/gpu/r4_call8.sh) -- the E2E step waits for its own latency chain, not for the host
+        super().__init__(model, sampler, posemb, list(lanes) if lanes is not None else [(sampler, posemb)], prefetch, depth, chunk,
+                         ahead, False if graph is None else graph)
         self.gin = model.engine()
         self.nce = engine if engine is not None else NceEngine()
         self.optimizer = FlatAdam(self.live, self.flat_grad, learning_rate, betas, weight_decay, clip_norm, self.nce)
-        self.mask_fn = None          # tests: () -> (keep_q, keep_k); default = in-kernel Philox
-        self.dropout_seed = 0x5EED0000
-        self.B = sampler.batch_size
-        self.one = torch.ones(1, device=self.dev)
-        self.meter_acc, self.meter_max = _meter_buffers(self.dev)
-        self.prefetch = prefetch and self.dev.type == "cuda"
-        self.main = torch.cuda.Stream(self.dev, priority=-1) if self.prefetch else None
-        lanes = list(lanes) if lanes is not None else [(sampler, posemb)]
-        self.producer = BatchProducer(lanes if self.prefetch else lanes[:1], self._first_id,
-                                      self.dev if self.prefetch else "cpu", depth=depth if self.prefetch else 1,
-                                      chunk=chunk if self.prefetch else 1, ahead=ahead)
-        if not self.prefetch:
-            self.producer.cuda = False
-        # graph replay is available but OFF by default here: measured 1.241 vs 1.240 ms per step at bsz 256 and 0.872 vs
-        # 0.806 ms at bsz 32 (scripts/gpu/r4_call8.sh) -- the E2E step waits for its own latency chain, not for the host
-        self._graph_init(False if graph is None else graph)
         model.train()
 
     def _first_id(self, step):
         return step * self.B
 
-    _staged = MoCoTrainStep._staged
-    check_status = MoCoTrainStep.check_status
-    step = MoCoTrainStep.step
-    join = MoCoTrainStep.join
-
-    def _step(self, step, lr, prof=None):
-        pr = prof or {}
-        self._release_pending()
-        q, k = self.producer.get(step, prof=prof)
-        _hint_rows_once(self.gin, q, k)
-        st = torch.cuda.current_stream(self.dev).cuda_stream if self.dev.type == "cuda" else None
-        p_drop = self.model.gnn.drop.p
-        keep_q, keep_k = self.mask_fn() if self.mask_fn is not None else (None, None)
-        s0 = (self.dropout_seed + 2 * step * 0x9E3779B97F4A7C15) & 0xFFFFFFFFFFFFFFFF if p_drop > 0 else None
-        for grp in self.optimizer.param_groups:                          # train.py:411-416
-            grp["lr"] = lr
-        out = self._run_step(q, k, lr, s0, 0, keep_q is not None, pr, st,
-                             lambda scalars, marks: self._body(q, k, keep_q, keep_k, s0, scalars, marks, st))
-        self._pending_release = step
-        return dict(out, graph_q=q, graph_k=k)
-
-    _release_pending = MoCoTrainStep._release_pending
-
-    def _capture_body(self, q, k, st):
-        s0 = 0 if self.model.gnn.drop.p > 0 else None
-        return lambda scalars, marks: self._body(q, k, None, None, s0, scalars, marks, st)
-
-    def _body(self, q, k, keep_q, keep_k, s0, scalars, pr, st):
+    def _body(self, q, k, keep, s0, scalars, pr, st):
+        """``keep``: (keep_q, keep_k) of ``mask_fn`` (tests) or None = in-kernel Philox from the step's key ``s0``"""
         S = {}
+        keep_q, keep_k = keep if keep is not None else (None, None)
 
         def whole():
             self._fetch_scalars(scalars, st)

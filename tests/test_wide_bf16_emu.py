@@ -266,7 +266,7 @@ def test_bf16_wide_e2e_head_vs_rounded_reference():
 
 
 def test_fused_wide_step_bf16_encoder_and_head_vs_rounded_oracle():
-    """MoCoTrainStep._body_wide at hidden 128 with --encoder-dtype bf16 and --nce-dtype bf16, one step.  One GIN layer (num_layers
+    """MoCoTrainStep._body at hidden 128 with --encoder-dtype bf16 and --nce-dtype bf16, one step.  One GIN layer (num_layers
     2): every kind of bf16 product runs -- z1 with k = 49, z2, d a1, d agg, dW1 and dW0 over the node dimension, the head's three --
     while the rule's own fp32-vs-float64 gap stays near the f32 bars, so the comparison keeps its resolution (each further layer
     multiplies that gap: see the module docstring)."""

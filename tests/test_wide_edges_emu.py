@@ -1,7 +1,7 @@
 """The any-width encoder (csrc/ginx.hip) and the wide head at the edges the sampled batches of the other tests never reach, each
 against oracle/encoder.py run in float64.  Emulator tier; the device tier is tests/test_wide_step_gpu.py.
 
-- widths that are not multiples of four through the fused step (MoCoTrainStep._body_wide): parameters at offsets of the flat
+- widths that are not multiples of four through the fused step (MoCoTrainStep._body on the any-width engines): parameters at offsets of the flat
   buffer that are not 16-byte aligned, so the GEMM's, BatchNorm's, pooling's and spmm's scalar paths run on them;
 - a width above 256 through the API path: the 256-column loops of spmm, pooling and the column sums take a second trip;
 - hand-built batches of 1023, 1024, 1025 and 2049 live rows (the weight gradients' 1,024-row slabs and the end of the last one)

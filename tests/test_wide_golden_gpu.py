@@ -1,6 +1,6 @@
 """Device tier of the width-128 / 256 reference-executed fixtures (tests/wide_golden_check.py): one MoCo step of the any-width
 path on cuda:0 against what the reference's GraphEncoder / MemoryMoCo / loss / Adam produced at --hidden-size 128 and 256, through
-the API path (GraphEncoder.forward + torch Adam) and through the fused step (MoCoTrainStep._body_wide)."""
+the API path (GraphEncoder.forward + torch Adam) and through the fused step (MoCoTrainStep._body on the any-width engines)."""
 import pytest
 
 pytestmark = pytest.mark.gpu

@@ -1,4 +1,4 @@
-"""Device tier of tests/test_wide_edges_emu.py: the fused any-width step (MoCoTrainStep._body_wide over csrc/ginx.hip and the dense
+"""Device tier of tests/test_wide_edges_emu.py: the fused any-width step (MoCoTrainStep._body over csrc/ginx.hip and the dense
 head) at --hidden-size 256 on a device-sampled batch -- G1 (1M nodes / 10M edges), bsz 256, rw_hops 256, K 16384, positional
 embedding by the device eigensolvers -- against oracle/encoder.py fed the same batch, dropout masks, weights, Adam moments and
 queue, in fp32 and in float64 (tests/wide_step_check.py).  At ~25 k live rows per view every weight gradient spans many 1,024-row

@@ -1,5 +1,5 @@
 """tests/wide_step_check.py for ``--encoder-dtype bf16 --nce-dtype bf16``: ONE ``MoCoTrainStep.step`` of the any-width step
-(``_body_wide``) whose per-node Linears and dense head run with bf16 operands, against the ROUNDED oracle of
+(``_body`` on the any-width engines) whose per-node Linears and dense head run with bf16 operands, against the ROUNDED oracle of
 tests/bf16_reference.py -- oracle/encoder.py with the GIN layers' Linears swapped for the rule's, and the head's three products
 under the rule -- fed the same batch, dropout masks, weights, Adam moments and queue, in fp32 and in float64.  The float64 run
 on the rounded values is the exact value of the rule; the fp32 run is a second implementation of it, and its distance from the

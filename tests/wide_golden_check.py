@@ -4,7 +4,7 @@ float64 for the exact gradients).  One MoCo step through the any-width API path 
 MemoryMoCo -> gcc_ncex_forward, torch.optim.Adam as train.py's wide path uses it); shared by the emulator tier
 (tests/test_wide_golden_emu.py) and the device tier (tests/test_wide_golden_gpu.py).  The bar is north_star's: 1e-3 of the
 tensor's largest entry for gradients (against the float64 run), 1e-3 relative for embeddings / logits / loss.
-``run_fused_step`` is the same step through the fused MoCoTrainStep (MoCoTrainStep._body_wide) against the reference's post-step
+``run_fused_step`` is the same step through the fused MoCoTrainStep (MoCoTrainStep._body on the any-width engines) against the reference's post-step
 state."""
 import os
 

@@ -1,4 +1,4 @@
-"""Times the fused any-width MoCo step (MoCoTrainStep._body_wide over csrc/ginx.hip) with f32 and with bf16 operands on the MI355X,
+"""Times the fused any-width MoCo step (MoCoTrainStep._body over csrc/ginx.hip) with f32 and with bf16 operands on the MI355X,
 in one process and on one sampled batch stream:
 
   f32    GraphEncoder(encoder_dtype="f32"), MemoryMoCo(nce_dtype="f32")   -- ginx_gemm_kernel, v_mfma_f32_16x16x4_f32
