@@ -6,11 +6,17 @@
 //
 // Sampled ego-nets are star-like: ~75 % of them have FEWER than 32 positive eigenvalues, the
 // rest of the "top 32" is a large degenerate null space, and exact multiplicities occur among
-// the positive eigenvalues too.  Pipeline of one call (any number of views, see gcc_posemb_multi):
-//   posemb_classify_kernel  deflated size n' of every subgraph (twin leaves collapse) -> work lists
-//   posemb_direct_kernel    n' <= 384: dense symmetric eigensolver (tridiagonalise, bisect, inverse
-//                           iteration): exact multiplicities, deterministic run time; three size classes
-//   posemb_krylov_kernel    larger ones: thick-restart Krylov-Schur, Ritz problem by the same solver core
+// the positive eigenvalues too.  Pipeline of one call (any number of views, see gcc_posemb_multi); n' = deflated size:
+//   posemb_classify_kernel  n' of every subgraph (twin leaves and stalks collapse) -> one work list per class
+//   posemb_sort_kernel      every list longest item first
+//   posemb_wave_kernel      n' <= 48 / <= 64: one subgraph per WAVE, dense direct solver (tridiagonalise, bisect, inverse
+//                           iteration: exact multiplicities, deterministic run time)
+//   posemb_direct_kernel    the same solver per workgroup: n' <= 64 with many leaves (256 threads), 65..128 (four-wave teams,
+//                           the matrix rows in registers; or 1,024 threads with the matrix in LDS), and, behind the block
+//                           class, 129..384 and 385..704 with the matrix in a workspace slot
+//   posemb_cheb_kernel      129..1024: sparse block class (Chebyshev-filtered subspace iteration); hands on what it cannot do
+//   posemb_krylov_kernel    what is left: thick-restart Krylov-Schur, Ritz problem by the same solver core
+// Memory layouts are stated once each: PosWorkLayout (the caller's workspace) and one LDS layout per kernel.
 #include <mutex>
 #include "host_common.h"
 #include <type_traits>
@@ -331,7 +337,7 @@ __device__ __forceinline__ void item_args(const PosMulti &m, int item, PosArgs &
     a.list = nullptr; a.count = nullptr;
 }
 
-// Work lists.  posemb_classify_kernel sorts the subgraphs of a batch into four classes by deflated size; every
+// Work lists.  posemb_classify_kernel sorts the subgraphs of a batch into kNumCls classes by deflated size; every
 // solver kernel is launched with a SMALL fixed grid whose workgroups pull items from their class list.  (A grid of
 // one fat workgroup per subgraph that exits early when the class does not match keeps the workgroup dispatcher
 // busy placing 160-KiB-LDS / 1024-thread workgroups that do nothing, which delays every other queue.)
@@ -339,24 +345,17 @@ enum { kClsSmall = 0, kClsMid = 1, kClsSlot = 2, kClsKrylov = 3, kClsBig = 4, kC
 // one-wave teams (posemb_wave_kernel): deflated size <= 48 / <= 64 with at most kWaveNodes original nodes; the
 // 256-thread small class stays behind them for the (rare) leafier subgraphs
 constexpr int kWaveNodes = 256;
-// Both measured on the device in round 4 (scripts/gpu/r4_call1.sh, profiles/r4_posemb_phases_protos.txt): 'matrix' 17.2 -> 12.6 us
-// (n' <= 48) / 32.3 -> 20.9 us (<= 64) of wave time per item, 'expand' 12.7 -> 10.7 / 19.5 -> 15.9; strict device tests green.
-#ifndef GCC_POSEMB_EXPAND4
-#define GCC_POSEMB_EXPAND4 1         // expansion of the one-wave teams four nodes per iteration (0: two)
-#endif
-#ifndef GCC_POSEMB_EDGE_FILL
-#define GCC_POSEMB_EDGE_FILL 1       // matrix fill of the one-wave teams by entry instead of by row (0: lane = row)
-#endif
 constexpr int kWaveTeams = 4;        // teams (waves) per workgroup
 static_assert(kNumCls == GCC_POSEMB_TICK_CLASSES, "include/gcc_amd.h: tick buffer classes");
-struct PosHead {                     // head of the caller's workspace (zeroed per call)
-    int32_t *count;                  // [4] items per class
-    int32_t *next;                   // [4] work counters
-    int32_t *list;                   // [4][T] item ids, T = views * B
-    float *slots;                    // [workgroups of the slot class][slot_floats]: matrix (kGMax x kGMax) + deflation tables
-    float *bslots;                   // [workgroups of the big class][bslot_floats]: matrix (kBMax x kBMax) + deflation tables
+constexpr int kTabFloats = kNodeMax * 4;   // a workgroup's per-node table in the workspace, 16 bytes per node (defl_record fills the first 8)
+struct PosHead {                     // head of the caller's workspace (its first 64 bytes are zeroed per call) and the regions of PosWorkLayout
+    int32_t *count;                  // [kNumCls] items per class
+    int32_t *next;                   // [kNumCls] work counters
+    int32_t *list;                   // [kNumCls][T] item ids, T = views * B
+    float *slots;                    // [workgroups of the slot class][slot_floats]: DirectSlot<kGMax>
+    float *bslots;                   // [workgroups of the big class][bslot_floats]: DirectSlot<kBMax>
     int64_t bslot_floats;
-    float *tabs;                     // [workgroups of the mid class, then of the small class][kNodeMax * 4]: deflation tables
+    float *tabs;                     // [workgroups of the mid class, then of the small class][kTabFloats]: expansion records
     int32_t tabs_small_off;          // first small-class table (= workgroups of the mid class)
     int32_t T;
     int32_t ldv;                     // longest subgraph the Krylov class has room for (node_cap / batch_size, rounded up)
@@ -364,25 +363,14 @@ struct PosHead {                     // head of the caller's workspace (zeroed p
     int32_t use_wave;                // deflated sizes <= 64 go to the one-wave teams
     int32_t use_stalks;              // pendant two-paths of a hub are deflated too (GCC_POSEMB_STALKS, default 1)
     int64_t slot_floats;
-    float *pslots;                   // [workgroups of the register-resident 65..128 class (two / four waves)][kPairSlotFloats]: matrix / reflectors + expansion records
-    int32_t use_pair;
+    float *pslots;                   // [workgroups of the four-wave 65..128 class][PairSlot::floats]
+    int32_t use_pair;                // the 65..128 class on four-wave teams (0: 1,024-thread workgroups with the matrix in LDS)
 };
 
-// The deflation tables (24 KiB) are built in LDS where the eigenvector arrays go later; the 8 bytes per node that the
-// expansion at the end needs of them (defl_record) go to the workspace: it keeps the mid class at 132 KiB, so that a
-// workgroup of the training step (26 KiB) still fits on the same CU, and the small class at 50 KiB (3 per CU).
-template <int kNMax, int kT, bool kGlobalA>
-__host__ __device__ constexpr int direct_lds_bytes()
-{
-    return kGlobalA ? (kNMax > kGMax ? kBLds : kGLds)
-                    : (int)(sizeof(float) * (6 * kNMax + 32 * kYld + kT + kNMax * (kNMax + 1) + kNMax * kYld)
-                            + kNMax * (33 * 8 + 32));
-}
-
 struct TriLds {
-    float *dg, *of, *of2, *tau;      // [kNMax] diagonal, off-diagonal, its square, reflector scales
-    float *pbuf, *vbuf;              // [kNMax]
-    float *coef;                     // [nv][ldy] Gram-Schmidt coefficients; column ldy - 1 = squared norm  (nv = ldy - 1 vectors)
+    float *dg, *of, *of2, *tau;      // [rows] diagonal, off-diagonal, its square, reflector scales
+    float *pbuf, *vbuf;              // [rows]
+    float *coef;                     // [nv][ldy] scratch of the cluster sweep (nv = ldy - 1 vectors); its first nv floats: squared norms
     int *cnt;                        // [kT] Sturm counts of one bisection round
     float *Y;                        // [n'][ldy] eigenvectors
     int ldy;
@@ -390,6 +378,35 @@ struct TriLds {
     uint8_t *Uf;                     // [n'][bw]
     int bw, ldu;
 };
+
+// ---- LDS layouts.  Each kernel with dynamic LDS states its carve-up ONCE, as a constexpr struct of offsets and `bytes`
+// (DirectLds, WaveLds, kry_lds, ChebLds): the kernel binds its pointers from it, the host launches and opts in with its
+// `bytes`, and the static_asserts on overlays are written against its names.  The two pieces that every user of the
+// solver core carves are bound here.
+// head of a TriLds: six vectors of `rows` floats | coef | cnt [threads]
+__host__ __device__ constexpr int tri_head_floats(int rows, int coef_floats, int threads) { return 6 * rows + coef_floats + threads; }
+__device__ __forceinline__ void tri_bind_head(TriLds &w, float *p, int rows, int coef_floats)
+{
+    w.dg = p;
+    w.of = w.dg + rows;
+    w.of2 = w.of + rows;
+    w.tau = w.of2 + rows;
+    w.pbuf = w.tau + rows;
+    w.vbuf = w.pbuf + rows;
+    w.coef = w.vbuf + rows;
+    w.cnt = (int *)(w.coef + coef_floats);
+}
+// LU factors of a batch of bw inverse iterations on `rows` rows: Ud | Us [rows][bw + 1] floats | Uf [rows][bw] bytes
+// (bound `skip` floats behind p: the direct kernel's slots follow its n' rows of eigenvectors)
+__host__ __device__ constexpr int tri_lu_bytes(int rows, int bw) { return rows * ((bw + 1) * 8 + bw); }
+__device__ __forceinline__ void tri_bind_lu(TriLds &w, float *p, int skip, int rows, int bw)
+{
+    w.bw = bw;
+    w.ldu = bw + 1;
+    w.Ud = p + skip;
+    w.Us = w.Ud + rows * w.ldu;
+    w.Uf = (uint8_t *)(w.Us + rows * w.ldu);
+}
 
 struct EigShared {                   // per-workgroup scratch of the solver core (a __shared__ object of the kernel)
     float lamv[kVecCap], shiftv[kVecCap], lo[kVecCap], hi[kVecCap];
@@ -714,7 +731,7 @@ __device__ bool inverse_iteration_step(const TriLds &w, int n, int j, int jl, fl
     // back substitution, the next row's operands requested ahead in the same way
     float d = cd, us = 0.f, s2 = 0.f, yi = cy;               // row n - 1
     if constexpr (kDeep) {
-        // the factors live in the workspace (two- / four-wave teams): a row's operands come from L2, so they are requested FOUR rows (one
+        // the factors live in the workspace (four-wave teams): a row's operands come from L2, so they are requested FOUR rows (one
         // chunk) ahead; same arithmetic in the same order
         float dq[4], uq[4];
         uint8_t fq[4];
@@ -770,18 +787,10 @@ __device__ bool inverse_iteration_step(const TriLds &w, int n, int j, int jl, fl
     return ok;
 }
 
-// Gram-Schmidt inside every cluster of close eigenvalues; the t-th members of all clusters are processed together
-// (2 barriers per t).  Vectors stay un-normalised while the sweep runs (projections divide by the squared norms kept
-// in coef[.][32]); a second pass follows only where the first one removed more than half of a vector ("twice is
-// enough", Kahan / Parlett).  Returns (block-uniform) the number of vectors that vanished, i.e. were in the span of
-// their predecessors.  All threads call it; ends with a barrier.
 constexpr int kMaxInvIt = 12;         // solve + sweep rounds of eig_top_vectors (3 as a rule)
 constexpr float kVanish = 1e-4f;     // squared norm left of a unit vector below which it counts as "in the span of its predecessors"
 constexpr float kHeavy = 1e-2f;      // ... below which what is left is too noisy to be final
 
-// Returns (block-uniform) the number of vectors that vanished, i.e. were in the span of their predecessors; those are
-// refilled with fresh pseudo-random numbers (LAPACK stein restarts them the same way) and *min_left is the smallest
-// squared norm any member kept (1 = nothing removed).  All threads call it; ends with a barrier.
 // (one-wave solver core, further below)
 struct WaveTri {
     float *dg, *of, *of2, *tau;      // [kNMax] diagonal, off-diagonal, its square, reflector scales
@@ -790,10 +799,13 @@ struct WaveTri {
     int ldy;
 };
 
-// cluster_orthonormalize() for one wave: lane = rows lane, lane + 64, ... of Y (n <= 64 kCPL).  Members are taken in index
+// Gram-Schmidt inside every cluster of close eigenvalues by one wave: lane = rows lane, lane + 64, ... of Y (n <= 64 kCPL).  Members are taken in index
 // order (the members of a cluster are consecutive and its predecessors finished), projections on all predecessors are
 // computed from the same vector (classical Gram-Schmidt, a second pass where the first removed more than half: "twice is
 // enough").  No barrier: a sweep over a cluster of m copies is m^2 / 2 wave reductions instead of 3 m workgroup barriers.
+// Returns (wave-uniform) the number of vectors that vanished, i.e. were in the span of their predecessors; those are
+// refilled with fresh pseudo-random numbers (LAPACK stein restarts them the same way) and *min_left is the smallest
+// squared norm any member kept (1 = nothing removed).
 template <int kCPL>
 __device__ __forceinline__ int wave_cluster_orthonormalize(const WaveTri &w, int n, int na, const int *cs, const int *posi, int maxpos,
                                                            float *min_left, uint32_t hseed)
@@ -862,86 +874,6 @@ __device__ __forceinline__ int wave_cluster_orthonormalize(const WaveTri &w, int
     return lost;
 }
 
-template <int kT>
-__device__ int cluster_orthonormalize(const TriLds &w, int n, int na, const int *cs, const int *posi, int maxpos,
-                                      float *min_left, uint32_t hseed)
-{
-    *min_left = 1.0f;
-    constexpr int kNW = kT / 64;
-    const int tid = (int)threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    float *Y = w.Y, *coef = w.coef;
-    const int ldy = w.ldy, nc = w.ldy - 1;                  // coefficient rows have stride ldy, the norms sit in column nc
-    if (maxpos == 0) return 0;
-    if (tid < na) coef[tid * ldy + nc] = 1.0f;      // squared norms: unit vectors come out of the solves
-    __syncthreads();
-    int lost = 0;
-    float left = 1.0f;
-    for (int t = 1; t <= maxpos; ++t) {
-        for (int pass = 0; pass < 2; ++pass) {
-            // projections on the predecessors in the cluster (a vanished predecessor spans nothing)
-            for (int j = 0; j < na; ++j) {
-                if (posi[j] != t) continue;
-                for (int l = cs[j] + wv; l < j; l += kNW) {
-                    float s = 0.f;
-                    for (int r = lane; r < n; r += 64) s = fmaf(Y[r * ldy + j], Y[r * ldy + l], s);
-                    s = wave_sum(s);
-                    const float nl = coef[l * ldy + nc];
-                    if (lane == 0) coef[j * ldy + l] = nl >= kVanish ? s / nl : 0.f;
-                }
-            }
-            __syncthreads();
-            float *part_sq = (float *)w.cnt;                           // [vector][wave] partial squared norms
-            for (int j = 0; j < na; ++j) {
-                if (posi[j] != t) continue;
-                float part = 0.f;
-                for (int i = tid; i < n; i += kT) {
-                    float acc = 0.f;
-                    for (int l = cs[j]; l < j; ++l) acc = fmaf(coef[j * ldy + l], Y[i * ldy + l], acc);
-                    const float y = Y[i * ldy + j] - acc;
-                    Y[i * ldy + j] = y;
-                    part = fmaf(y, y, part);
-                }
-                part = wave_sum(part);
-                if (lane == 0) part_sq[j * kNW + wv] = part;
-            }
-            __syncthreads();
-            // every wave adds the partials up in the same order (lane = vector): identical, deterministic results
-            float now = 0.f;
-            const bool mine = lane < na && posi[lane] == t;
-            if (mine)
-                for (int q = 0; q < kNW; ++q) now += part_sq[lane * kNW + q];
-            // (the vectors enter with unit norm: "before" is 1 in the first pass; nobody reads coef[.][32] of step t here)
-            const bool again = pass == 0 && wave_ballot(mine && now < 0.5f) != 0ull;
-            if (wv == 0 && mine) coef[lane * ldy + nc] = now;
-#ifdef GCC_POSEMB_DEVDEBUG
-            if (wv == 0 && mine) printf("gs t=%d pass=%d j=%d now=%.6f\n", t, pass, lane, now);
-#endif
-            if (!again) break;
-        }
-        __syncthreads();
-        for (int j = 0; j < na; ++j) {
-            if (posi[j] != t) continue;
-            const float c = coef[j * ldy + nc];
-            left = c < left ? c : left;
-            if (c < kVanish) ++lost;
-        }
-    }
-    // normalise the members of the clusters; vanished ones restart from pseudo-random numbers
-    for (int j = 0; j < na; ++j) {
-        if (posi[j] == 0) continue;
-        const float c = coef[j * ldy + nc];
-        if (c < kVanish) {
-            for (int i = tid; i < n; i += kT) Y[i * ldy + j] = hash_unit(hseed, (uint32_t)j, (uint32_t)i);
-        } else {
-            const float inv = 1.0f / sqrtf(c);
-            for (int i = tid; i < n; i += kT) Y[i * ldy + j] *= inv;
-        }
-    }
-    __syncthreads();
-    *min_left = left;
-    return lost;
-}
-
 // ---- the kq largest eigenvalues of T: eigenvalue j (descending) has ascending index nr - 1 - j and lies in [lo, hi]
 // with count(lo) <= nr - 1 - j < count(hi); every round probes kT / kVec interior points per eigenvalue.  On exit
 // es.lamv[0..kq) holds them in descending order.  The spectrum must lie inside (-1.001, 1.001) (normalised adjacency
@@ -1003,7 +935,7 @@ template <int kCPL, int kT, bool kPair = false>
 __device__ bool eig_top_vectors(const float *A, int lda, int nr, int na, const TriLds &w, EigShared &es, uint32_t hseed,
                                 long long *tick_row, long long &tick)
 {
-    static_assert(!kPair || ((kT == 128 || kT == 256) && kCPL == 2), "two- / four-wave teams");
+    static_assert(!kPair || (kT == 256 && kCPL == 2), "four-wave teams");
     constexpr int kNW = kT / 64;
     const int tid = (int)threadIdx.x, lane = tid & 63, wv = tid >> 6;
     const int ldy = w.ldy;
@@ -1088,12 +1020,10 @@ __device__ bool eig_top_vectors(const float *A, int lda, int nr, int na, const T
 #endif
         if (it > 0) {                              // the first solve only enters the cluster subspaces
             float left;
-#ifdef GCC_POSEMB_BLOCK_GS
-            lost = cluster_orthonormalize<kT>(w, nr, na, es.cs, es.posi, maxpos, &left, hseed ^ (0x51ED27u * (uint32_t)(it + 1)));
-#else
             // The sweep is done by ONE wave without barriers (m^2 / 2 wave reductions for a cluster of m copies) while the
-            // others wait: the block version above needs 3 workgroup barriers per cluster position and pass, which cost
-            // 119 of the 484 us of a mid-class item (hub ego-nets carry clusters of 30-60 copies).
+            // others wait.  (A block-wide sweep, the t-th members of all clusters together, needs 3 workgroup barriers per
+            // cluster position and pass: 119 of the 484 us of a mid-class item, hub ego-nets carry clusters of 30-60 copies;
+            // profiles/HISTORY.md.)
             if (wv == 0) {
                 WaveTri ww;
                 ww.Y = w.Y; ww.ldy = w.ldy; ww.nrm = w.coef; ww.dg = ww.of = ww.of2 = ww.tau = nullptr;
@@ -1106,7 +1036,6 @@ __device__ bool eig_top_vectors(const float *A, int lda, int nr, int na, const T
             lost = es.gs_lost;
             left = es.gs_left;
             __syncthreads();
-#endif
             if (lost > 0) need_until = it + 3 > need_until ? it + 3 : need_until;
             else if (left < kHeavy) need_until = it + 1 > need_until ? it + 1 : need_until;
         }
@@ -1127,7 +1056,7 @@ __device__ bool eig_top_vectors(const float *A, int lda, int nr, int na, const T
         if (it >= need_until) break;
     }
     if constexpr (kPair) {
-        // x = H_0 ... H_{nr-3} y for a two- / four-wave team: kLPV = kT / 32 lanes per vector (4 / 8) -- lane group q of a wave holds the rows
+        // x = H_0 ... H_{nr-3} y for a four-wave team: kLPV = kT / 32 = 8 lanes per vector -- lane group q of a wave holds the rows
         // kLPV r + q of its vector in registers --, so a reflector costs (nr - kk) / kLPV multiply-adds per lane twice and 2 / 3 cross-lane
         // additions; the reflectors come from the workspace one step ahead, through a double-buffered LDS copy (one team barrier per
         // reflector).  (The version below gives a wave two vectors at a time: 8 passes over all reflectors with two full wave
@@ -1223,144 +1152,26 @@ __device__ bool eig_top_vectors(const float *A, int lda, int nr, int na, const T
     return lost > 0 || es.bad != 0;
 }
 
-// ---- two-wave teams (65 <= n' <= 128): tridiagonalize() for a workgroup of TWO waves with the matrix in REGISTERS -- thread r owns
-// row r (128 floats).  The 16-wave version above is bound by its two barriers and ~6 LDS round trips per column while it owns a whole
-// CU (1,024 threads at 128 registers, 132 KiB of LDS); here a column costs two 2-wave barriers, the FLOPs run out of registers with
-// the other operand broadcast from LDS (16 bytes per instruction), and a workgroup takes 128 threads and kPairLds of LDS, so that
-// four of them share a CU.  A lives in the workgroup's workspace slot (L2): read once (by columns -- A is symmetric -- so that the
-// read is coalesced), its rows then receive the reflectors as in the other versions.
+// ---- four-wave teams (65 <= n' <= 128): tridiagonalize() for a workgroup of FOUR waves with the matrix in REGISTERS.  The 16-wave
+// version above is bound by its two barriers and ~6 LDS round trips per column while it owns a whole CU (1,024 threads at 128
+// registers, 132 KiB of LDS); here a column costs two team barriers, the FLOPs run out of registers with the other operand broadcast
+// from LDS (16 bytes per instruction), and a workgroup takes kPairT threads and kPairLds of LDS, so that three of them share a CU.
+// A lives in the workgroup's workspace slot (L2): read once (by columns -- A is symmetric -- so that the read is coalesced), its rows
+// then receive the reflectors as in the other versions.
 //   column k:  the owners of rows k and k + 1 put them into LDS                                  | barrier
-//              all: sigma, x0, a_kk from row k (a 2 x 64 wave reduction, the same in both waves); v_r; S_r = sum_{c>k+1} a_rc row_k[c];
+//              all: sigma, x0, a_kk from row k (a wave reduction, the same in every wave); v_r; S_r = sum_{c>k+1} a_rc row_k[c];
 //              p_r = tau (a_{r,k+1} + scale S_r)  [a_{r,k+1} = row_{k+1}[r]];  p_r, v_r and the wave's part of p.v into LDS  | barrier
 //              K = tau/2 p.v;  a_rc -= v_r p_c + (p_r - 2 K v_r) v_c   [= v_r w_c + w_r v_c with w = p - K v]
-#ifndef GCC_POSEMB_PAIR_THREADS
-#define GCC_POSEMB_PAIR_THREADS 256  // 128: two waves, thread = row (tridiagonalize_pair); 256: four waves, thread = half a row (tridiagonalize_quad)
-#endif
+// Thread t owns HALF of row r = t >> 1 -- the columns of parity t & 1, 64 registers --: the two halves of a row's product meet with one
+// lane exchange.  (A two-wave variant, thread = whole row in 128 registers, took a quarter of a CU at 227 registers and measured 556
+// against 423 us per item: profiles/HISTORY.md.)  Rows and the p / v vectors lie in LDS de-interleaved (even columns | 16 bytes | odd
+// columns: the two parities of a 16-lane group read different banks).
 #ifndef GCC_POSEMB_QUAD_OCC
 #define GCC_POSEMB_QUAD_OCC 3        // waves per SIMD the four-wave kernel is compiled for: 3 = 168 registers, three workgroups per CU (423 us per item,
                                      // 0.827 ms per step); 4 = 128 registers with ~50 spilled values (467 us, 0.830); 2 = 208 registers (424 us, 0.837): scripts/gpu/r5_call24.sh, r5_call25.sh
 #endif
-constexpr int kPairT = GCC_POSEMB_PAIR_THREADS;
-static_assert(kPairT == 128 || kPairT == 256, "two- or four-wave teams");
-constexpr int kPairLds = (kPairT == 128 ? 32 : 33) * 1024;   // dynamic LDS of such a workgroup (+ ~2 KiB static): the deflation tables (24 KiB), later the eigenvectors (17 KiB)
-constexpr int kPairSlotFloats = 128 * 128 + 2048 + 2 * 128 * 33 + 1024 + 64;   // matrix / reflectors | expansion records (8 bytes per node) | LU factors
-template <int kNMax>
-__device__ void tridiagonalize_pair(float *A, int lda, int n, const TriLds &w, float *xb /* LDS, 16-byte aligned, 6 kNMax + 8 floats */)
-{
-    static_assert(kNMax == 128, "two waves, one row per thread");
-    constexpr int kB = kNMax / 8, kG = kNMax / 32;
-    const int r = (int)threadIdx.x, lane = r & 63, h = r >> 6;
-    float a[kNMax];
-    {   // unconditional loads (the slot holds kNMax rows) and a bit mask: a select is turned back into a branch per element, and
-        // addresses that do not depend on the item are hoisted out of the item loop -- 128 of them -- and spilled
-        uint64_t ap = (uint64_t)(A + r);
-        opaque_u64(ap);
-        const float *Ar = (const float *)ap;
-        const uint32_t mr = r < n ? 0xFFFFFFFFu : 0u;
-#pragma unroll
-        for (int c = 0; c < kNMax; ++c) a[c] = __uint_as_float(__float_as_uint(Ar[c * lda]) & (c < n ? mr : 0u));
-    }
-    __syncthreads();                                     // all rows are in registers: A's rows may now receive the reflectors
-    float *pv = xb + 4 * kNMax, *vv = xb + 5 * kNMax, *kpart = xb + 6 * kNMax;
-    const int ncols = (n + 31) & ~31;                    // the readers take groups of 32 columns: zeros up to the group's end
-    auto put_row = [&](float *dst, int from) {           // one lane: its row, blocks of eight columns from `from` on
-#pragma unroll
-        for (int cb = 0; cb < kB; ++cb) {
-            if (8 * cb + 7 >= from && 8 * cb < ncols) {
-                *(float4 *)(dst + 8 * cb) = make_float4(a[8 * cb], a[8 * cb + 1], a[8 * cb + 2], a[8 * cb + 3]);
-                *(float4 *)(dst + 8 * cb + 4) = make_float4(a[8 * cb + 4], a[8 * cb + 5], a[8 * cb + 6], a[8 * cb + 7]);
-            }
-        }
-    };
-#pragma unroll 1
-    for (int k = 0; k + 2 < n; ++k) {
-        float *rk = xb + (k & 1) * 2 * kNMax, *rk1 = rk + kNMax;     // (two buffers: a column without a reflector has one barrier only)
-        if (h == (k >> 6) && lane == (k & 63)) put_row(rk, k);
-        if (h == ((k + 1) >> 6) && lane == ((k + 1) & 63)) put_row(rk1, k);
-        __syncthreads();
-        const float c0 = lane < n ? rk[lane] : 0.f, c1 = lane + 64 < n ? rk[64 + lane] : 0.f;   // (blocks of columns beyond n are not written)
-        const float sig = wave_sum((lane > k + 1 ? c0 * c0 : 0.f) + (lane + 64 > k + 1 ? c1 * c1 : 0.f));
-        const float x0 = rk[k + 1], akk = rk[k];
-        if (sig <= 1e-30f) {                             // uniform over the workgroup: the column is already tridiagonal, H_k = I
-            if (r == 0) { w.dg[k] = akk; w.of[k] = x0; w.tau[k] = 0.f; }
-            continue;
-        }
-        const float mu = sqrtf(x0 * x0 + sig);
-        const float beta = x0 > 0.f ? -mu : mu;
-        const float t = (beta - x0) / beta;
-        const float scale = 1.0f / (x0 - beta);
-        const float vr = r == k + 1 ? 1.0f : (r > k + 1 ? (h ? c1 : c0) * scale : 0.f);
-        // (groups of 32 columns under one uniform branch: the operands of a group are requested together -- a branch per block of
-        //  eight made every block wait for its own LDS reads -- at the price of up to 31 columns of multiply-adds with zeros)
-        float s0 = 0.f, s1 = 0.f;
-#pragma unroll
-        for (int g = 0; g < kG; ++g) {
-            if (32 * g + 31 > k + 1 && 32 * g < n) {     // uniform
-                float q[32];
-#pragma unroll
-                for (int u = 0; u < 8; ++u) {
-                    const float4 t4 = *(const float4 *)(rk + 32 * g + 4 * u);
-                    q[4 * u] = t4.x; q[4 * u + 1] = t4.y; q[4 * u + 2] = t4.z; q[4 * u + 3] = t4.w;
-                }
-                if (32 * g > k + 1) {
-#pragma unroll
-                    for (int u = 0; u < 32; u += 2) { s0 = fmaf(a[32 * g + u], q[u], s0); s1 = fmaf(a[32 * g + u + 1], q[u + 1], s1); }
-                } else {                                 // the group the reflector starts in
-#pragma unroll
-                    for (int u = 0; u < 32; u += 2) {
-                        s0 = fmaf(a[32 * g + u], 32 * g + u > k + 1 ? q[u] : 0.f, s0);
-                        s1 = fmaf(a[32 * g + u + 1], 32 * g + u + 1 > k + 1 ? q[u + 1] : 0.f, s1);
-                    }
-                }
-            }
-        }
-        const float p = (r > k && r < n) ? t * fmaf(scale, s0 + s1, rk1[r]) : 0.f;
-        const float kp = wave_sum(p * vr);
-        pv[r] = p;
-        vv[r] = vr;
-        if (lane == 0) kpart[h] = kp;
-        if (r > k + 1 && r < n) A[(int64_t)k * lda + r] = vr;        // row k of A stores the reflector
-        if (r == 0) { w.dg[k] = akk; w.of[k] = beta; w.tau[k] = t; }
-        __syncthreads();
-        const float K = 0.5f * t * (kpart[0] + kpart[1]);
-        const float wr = fmaf(-2.0f * K, vr, p);
-#pragma unroll
-        for (int g = 0; g < kG; ++g) {
-            if (32 * g + 31 > k && 32 * g < n) {         // (p and v are zero left of column k + 1 and beyond n)
-#pragma unroll
-                for (int hf = 0; hf < 2; ++hf) {         // (two halves: 32 + 32 operand registers beside the 128 of the row spill a few)
-                    float pc[16], vc[16];
-#pragma unroll
-                    for (int u = 0; u < 4; ++u) {
-                        const float4 p4 = *(const float4 *)(pv + 32 * g + 16 * hf + 4 * u), v4 = *(const float4 *)(vv + 32 * g + 16 * hf + 4 * u);
-                        pc[4 * u] = p4.x; pc[4 * u + 1] = p4.y; pc[4 * u + 2] = p4.z; pc[4 * u + 3] = p4.w;
-                        vc[4 * u] = v4.x; vc[4 * u + 1] = v4.y; vc[4 * u + 2] = v4.z; vc[4 * u + 3] = v4.w;
-                    }
-#pragma unroll
-                    for (int u = 0; u < 16; ++u) a[32 * g + 16 * hf + u] = fmaf(-vr, pc[u], fmaf(-wr, vc[u], a[32 * g + 16 * hf + u]));
-                }
-            }
-        }
-    }
-    {   // the last 2 x 2 block
-        __syncthreads();
-        float *rk = xb, *rk1 = xb + kNMax;
-        if (n >= 2 && r == n - 2) put_row(rk, n - 2);
-        if (r == n - 1) put_row(rk1, n - 2);
-        __syncthreads();
-        if (r == 0) {
-            if (n >= 2) { w.dg[n - 2] = rk[n - 2]; w.of[n - 2] = rk[n - 1]; }
-            w.dg[n - 1] = rk1[n - 1];
-            w.of[n - 1] = 0.f;
-        }
-    }
-    __syncthreads();
-}
-
-// The same for FOUR waves: thread t owns HALF of row r = t >> 1 -- the columns of parity t & 1, 64 registers -- so that a column's
-// multiply-adds and LDS broadcasts per thread are half the two-wave version's, the two halves of a row's product meet with one lane
-// exchange, and a workgroup's four waves at 168 registers take a third of a CU where the two at 227 took a quarter -- for 423 instead of 556 us.  Rows and the p / v
-// vectors lie in LDS de-interleaved (even columns | 16 bytes | odd columns: the two parities of a 16-lane group read different banks).
+constexpr int kPairT = 256;
+constexpr int kPairLds = 33 * 1024;  // dynamic LDS of such a workgroup (+ ~2 KiB static): the deflation tables (24 KiB), later the eigenvectors (17 KiB)
 constexpr int kQuadHalf = 68;            // floats from the even half of a row in LDS to its odd half
 template <int kNMax>
 __device__ void tridiagonalize_quad(float *A, int lda, int n, const TriLds &w, float *xb /* LDS, 16-byte aligned, 6 * 136 + 8 floats */)
@@ -1954,17 +1765,49 @@ __global__ __launch_bounds__(kSortThreads) void posemb_sort_kernel(PosMulti m, P
     }
 }
 
+// Workspace slot of a workgroup whose matrix lives in L2: matrix / reflectors [kNMax][kNMax] | expansion records
+template <int kNMax>
+struct DirectSlot {
+    static constexpr int64_t rec = (int64_t)kNMax * kNMax;
+    static constexpr int64_t floats = rec + kTabFloats;
+};
+// ... of a four-wave team: matrix / reflectors [kJMax][kJMax] | expansion records (8 bytes per node) | the LU factors of
+// all 32 inverse iterations | one spare 256-byte line
+struct PairSlot {
+    static constexpr int rec = (int)DirectSlot<kJMax>::rec;
+    static constexpr int lu = rec + kTabFloats / 2;
+    static constexpr int floats = lu + tri_lu_bytes(kJMax, 32) / (int)sizeof(float) + 64;
+};
+// Dynamic LDS of posemb_direct_kernel (byte offsets): the TriLds head | the matrix (LDS-resident classes only) | `rest`.
+// The deflation tables (24 KiB) are built in `rest`, where the eigenvectors (Y [n'][kYld]) and behind them as many LU
+// slots as fit go later; the 8 bytes per node that the expansion at the end needs of the tables (defl_record) go to the
+// workspace: it keeps the mid class at 132 KiB, so that a workgroup of the training step (26 KiB) still fits on the same
+// CU, and the small class at 50 KiB (3 per CU).
+template <int kNMax, int kT, bool kGlobalA, bool kPair>
+struct DirectLds {
+    static constexpr int lda = kGlobalA ? kNMax : kNMax + 1;   // LDS: odd stride; workspace: rows start on 256-byte boundaries
+    static constexpr int head = 0;
+    static constexpr int A = head + (int)sizeof(float) * tri_head_floats(kNMax, 32 * kYld, kT);
+    static constexpr int rest = A + (kGlobalA ? 0 : (int)sizeof(float) * kNMax * lda);
+    static constexpr int y_bytes = (int)sizeof(float) * kNMax * kYld;
+    // LDS-resident classes: room for the eigenvectors and a full batch of 32 LU slots at n' = kNMax
+    static constexpr int bytes = kPair ? kPairLds : kGlobalA ? (kNMax > kGMax ? kBLds : kGLds) : rest + y_bytes + tri_lu_bytes(kNMax, 32);
+    static_assert(bytes - rest >= kNodeMax * kDeflNodeBytes, "the deflation tables overlay the eigenvector / LU region");
+    static_assert(kPair || rest + y_bytes + tri_lu_bytes(kNMax, 4) <= bytes, "eigenvectors + the narrowest LU batch must fit");
+};
+
 template <int kCls, int kNMin, int kNMax, int kT, bool kGlobalA, bool kPair = false>
-__global__ __launch_bounds__(kT, kPair ? (kT == 256 ? GCC_POSEMB_QUAD_OCC : 2) : 1) void posemb_direct_kernel(PosMulti m, PosHead hd)
+__global__ __launch_bounds__(kT, kPair ? GCC_POSEMB_QUAD_OCC : 1) void posemb_direct_kernel(PosMulti m, PosHead hd)
 {
     static_assert(kNMax % 64 == 0 && kT % 64 == 0 && kT >= 64, "size class");
-    static_assert(!kPair || (kGlobalA && kT == kPairT && kNMax == 128), "two- / four-wave teams: the matrix and the reflectors live in the workspace");
+    static_assert(!kPair || (kGlobalA && kT == kPairT && kNMax == kJMax), "four-wave teams: the matrix and the reflectors live in the workspace");
+    using Lds = DirectLds<kNMax, kT, kGlobalA, kPair>;
     DYN_SMEM(smem);
     __shared__ EigShared es;
     __shared__ int colsrc[64];                  // per output column: eigenvector j >= 0, or -(c + 1) for contrast c
     __shared__ int sh_tot[3], sh_na, sh_item;
     constexpr int kNW = kT / 64, kCPL = kNMax / 64;
-    constexpr int lda = kGlobalA ? kNMax : kNMax + 1;   // LDS: odd stride; workspace: rows start on 256-byte boundaries
+    constexpr int lda = Lds::lda;
     const int tid = (int)threadIdx.x, lane = tid & 63, wv = tid >> 6;
     for (;;) {                                     // items of this class
     __syncthreads();
@@ -1982,28 +1825,14 @@ __global__ __launch_bounds__(kT, kPair ? (kT == 256 ? GCC_POSEMB_QUAD_OCC : 2) :
     const int k = min(min(n - 2, a.hidden), kMaxVec);   // data_util.py:278; k >= 1 (classify kernel)
     long long tick_ = m.ticks ? device_ticks() : 0;
     if (m.ticks && tid == 0) atomicAdd((unsigned long long *)&m.ticks[kCls * 16 + 15], 1ull);   // items
-    // ---- LDS carve-up
+    // ---- LDS carve-up (DirectLds)
     TriLds w;
-    w.dg = (float *)smem;
-    w.of = w.dg + kNMax;
-    w.of2 = w.of + kNMax;
-    w.tau = w.of2 + kNMax;
-    w.pbuf = w.tau + kNMax;
-    w.vbuf = w.pbuf + kNMax;
-    w.coef = w.vbuf + kNMax;
-    w.cnt = (int *)(w.coef + 32 * kYld);
-    float *lds_rest = (float *)(w.cnt + kT);
-    Defl d;
-    float *A = nullptr;
-    if (!kGlobalA) {
-        A = lds_rest;
-        lds_rest += kNMax * lda;
-    }
-    // the deflation tables (24 KiB) are built in LDS (the eigenvector arrays overlay them); what the expansion at the end
+    tri_bind_head(w, (float *)(smem + Lds::head), kNMax, 32 * kYld);
+    float *A = kGlobalA ? nullptr : (float *)(smem + Lds::A);
+    float *lds_rest = (float *)(smem + Lds::rest);
+    // the deflation tables are built in LDS (the eigenvector arrays overlay them); what the expansion at the end
     // needs of them goes to the workgroup's table in the workspace once the matrix is filled
-    constexpr int lds_total = kPair ? kPairLds : direct_lds_bytes<kNMax, kT, kGlobalA>();
-    static_assert(lds_total - (int)sizeof(float) * (6 * kNMax + 32 * kYld + kT + (kGlobalA ? 0 : kNMax * (kNMax + 1)))
-                  >= kNodeMax * kDeflNodeBytes, "the deflation tables overlay the eigenvector / LU region");
+    Defl d;
     defl_bind(d, lds_rest, kNodeMax);
     const int32_t *rp = a.row_ptr + n0;
 
@@ -2017,32 +1846,20 @@ __global__ __launch_bounds__(kT, kPair ? (kT == 256 ? GCC_POSEMB_QUAD_OCC : 2) :
     defl_prefix_block<kT>(d, n, sh_tot, w.cnt);    // (w.cnt: kT ints of LDS that are free until the bisection)
     const int nr = sh_tot[0], z = sh_tot[1], zp = sh_tot[2];    // reduced size n', number of twin / stalk contrasts
     if (nr > kNMax || nr < kNMin) continue;        // cannot happen: the classify kernel computed the same size
-    if (kGlobalA) A = kPair ? hd.pslots + (int64_t)blockIdx.x * kPairSlotFloats
+    if (kGlobalA) A = kPair ? hd.pslots + (int64_t)blockIdx.x * PairSlot::floats
                             : kCls == kClsBig ? hd.bslots + (int64_t)blockIdx.x * hd.bslot_floats
                                               : hd.slots + (int64_t)blockIdx.x * hd.slot_floats;   // the workgroup's own slot
     // ---- rest of the carve-up: eigenvectors and as many LU slots as fit
     w.Y = lds_rest;
     w.ldy = kYld;
-    {
-        static_assert(!kGlobalA || (int)sizeof(float) * (6 * kNMax + 32 * kYld + kT + kNMax * kYld) + kNMax * (5 * 8 + 4) <= lds_total,
-                      "eigenvectors + the narrowest LU batch must fit");
-        if constexpr (kPair) {                           // the LU factors of all 32 inverse iterations: in the slot (L2), behind the records
-            w.bw = 32;
-            w.ldu = 33;
-            w.Ud = A + kNMax * lda + kNodeMax * 2;
-            w.Us = w.Ud + kNMax * 33;
-            w.Uf = (uint8_t *)(w.Us + kNMax * 33);
-        } else {
+    if constexpr (kPair) {                               // the LU factors of all 32 inverse iterations: in the slot (L2), behind the records
+        tri_bind_lu(w, A, PairSlot::lu, kNMax, 32);
+    } else {
         const int used = (int)((unsigned char *)(w.Y + nr * kYld) - smem);
-        const int left = lds_total - used;
+        const int left = Lds::bytes - used;
         int bw = 32;
-        while (bw > 4 && nr * ((bw + 1) * 8 + bw) > left) bw >>= 1;
-        w.bw = bw;
-        w.ldu = bw + 1;
-        w.Ud = w.Y + nr * kYld;
-        w.Us = w.Ud + nr * w.ldu;
-        w.Uf = (uint8_t *)(w.Us + nr * w.ldu);
-        }
+        while (bw > 4 && tri_lu_bytes(nr, bw) > left) bw >>= 1;
+        tri_bind_lu(w, w.Y, nr * kYld, nr, bw);
     }
     for (int i = tid; i < nr * lda; i += kT) A[i] = 0.f;
     __syncthreads();
@@ -2059,16 +1876,14 @@ __global__ __launch_bounds__(kT, kPair ? (kT == 256 ? GCC_POSEMB_QUAD_OCC : 2) :
         }
     }
     // what the expansion at the end needs of the tables: 8 bytes per node, in the workgroup's table in the workspace
-    uint16_t *xrec = kGlobalA ? (uint16_t *)(A + (int64_t)kNMax * lda)
-                              : (uint16_t *)(hd.tabs + ((int64_t)(kCls == kClsMid ? 0 : hd.tabs_small_off) + blockIdx.x) * kNodeMax * 4);
+    uint16_t *xrec = kGlobalA ? (uint16_t *)(A + DirectSlot<kNMax>::rec)
+                              : (uint16_t *)(hd.tabs + ((int64_t)(kCls == kClsMid ? 0 : hd.tabs_small_off) + blockIdx.x) * kTabFloats);
     for (int v = tid; v < n; v += kT) defl_record(d, v, rp, a.col_idx, n0, xrec + 4 * v);
     __syncthreads();
 
     PHASE_TICK(0);                                 // deflation + matrix
-    if constexpr (kPair && kT == 256) {
+    if constexpr (kPair) {
         tridiagonalize_quad<kNMax>(A, lda, nr, w, lds_rest);      // (the eigenvector / LU region of the LDS is free until the bisection)
-    } else if constexpr (kPair) {
-        tridiagonalize_pair<kNMax>(A, lda, nr, w, lds_rest);      // (the eigenvector / LU region of the LDS is free until the bisection)
     } else if (kGlobalA) {
         // (the eigenvector / LU region of the LDS is free until the bisection: per-wave column sums and the pivot column)
         float *xcol = lds_rest, *slab = lds_rest + kNMax;
@@ -2116,12 +1931,21 @@ __global__ __launch_bounds__(kT, kPair ? (kT == 256 ? GCC_POSEMB_QUAD_OCC : 2) :
 
 // ---- one subgraph per WAVE (deflated size <= kNMax <= 64, at most kWaveNodes original nodes): kWaveTeams independent
 // teams per workgroup, each with its own LDS carve-up, pulling items from the class list; no workgroup barrier.
+// Dynamic LDS of posemb_wave_kernel: kWaveTeams times (float offsets inside a team's part)
+//   A [kNMax][lda] | Y [kNMax][kYld] | dg, of, of2, tau [kNMax] | nrm [64] | per-node expansion records (8 bytes)
+// The deflation tables of the team's item overlay Y.
 template <int kNMax>
-__host__ __device__ constexpr int wave_team_bytes()
-{
-    // A | Y | dg, of, of2, tau | nrm | per-node expansion records (8 bytes)   [the deflation tables overlay Y]
-    return (int)sizeof(float) * (kNMax * (kNMax + 1) + kNMax * kYld + 4 * kNMax + 64) + kWaveNodes * 8;
-}
+struct WaveLds {
+    static constexpr int lda = kNMax + 1;            // odd: lane = row and lane = column are both conflict free
+    static constexpr int A = 0;
+    static constexpr int Y = A + kNMax * lda;
+    static constexpr int tri = Y + kNMax * kYld;
+    static constexpr int nrm = tri + 4 * kNMax;
+    static constexpr int xinfo = nrm + 64;
+    static constexpr int team_bytes = (int)sizeof(float) * xinfo + kWaveNodes * 8;
+    static constexpr int bytes = kWaveTeams * team_bytes;
+    static_assert(kNMax <= 64 && (tri - Y) * (int)sizeof(float) >= kWaveNodes * kDeflNodeBytes, "the deflation tables overlay Y");
+};
 
 // (register budget: the LU factors of an inverse iteration take 2 kNMax registers per lane; without an occupancy
 //  target the scheduler spreads the unrolled eliminations over all 512)
@@ -2131,22 +1955,23 @@ __host__ __device__ constexpr int wave_team_bytes()
 template <int kCls, int kNMax>
 __global__ __launch_bounds__(kWaveTeams * 64, kNMax <= 48 ? GCC_POSEMB_W48_OCC : 1) void posemb_wave_kernel(PosMulti m, PosHead hd)
 {
-    static_assert(kNMax <= 64 && kNMax * kYld * 4 >= kWaveNodes * kDeflNodeBytes, "the deflation tables overlay Y");
+    using Lds = WaveLds<kNMax>;
     DYN_SMEM(smem);
     __shared__ EigShared es_all[kWaveTeams];
     __shared__ int colsrc_all[kWaveTeams][64];
-    constexpr int lda = kNMax + 1;                   // odd: lane = row and lane = column are both conflict free
+    constexpr int lda = Lds::lda;
     const int lane = lane_id(), team = (int)threadIdx.x >> 6;
-    float *A = (float *)(smem + (size_t)team * wave_team_bytes<kNMax>());
+    float *base = (float *)(smem + (size_t)team * Lds::team_bytes);
+    float *A = base + Lds::A;
     WaveTri w;
-    w.Y = A + kNMax * lda;
+    w.Y = base + Lds::Y;
     w.ldy = kYld;
-    w.dg = w.Y + kNMax * kYld;
+    w.dg = base + Lds::tri;
     w.of = w.dg + kNMax;
     w.of2 = w.of + kNMax;
     w.tau = w.of2 + kNMax;
-    w.nrm = w.tau + kNMax;
-    uint16_t *xinfo = (uint16_t *)(w.nrm + 64);      // [kWaveNodes][4]: defl_record
+    w.nrm = base + Lds::nrm;
+    uint16_t *xinfo = (uint16_t *)(base + Lds::xinfo);   // [kWaveNodes][4]: defl_record
     EigShared &es = es_all[team];
     int *colsrc = colsrc_all[team];
     for (;;) {                                       // items of this class, one per wave
@@ -2198,10 +2023,10 @@ __global__ __launch_bounds__(kWaveTeams * 64, kNMax <= 48 ? GCC_POSEMB_W48_OCC :
     for (int i = lane; i < nr * lda; i += 64) A[i] = 0.f;
     wave_sync();
     // M' = norm * adj * norm on the kept nodes (data_util.py:273-277), group couplings scaled by sqrt(group size)
-#if GCC_POSEMB_EDGE_FILL
     {   // lane = ENTRY of the ego-net's CSR: the entries are split evenly over the lanes (row by bisection over the row
         // pointers, rebased and parked in the record area, which is written only afterwards); with lane = row the lane that
-        // holds the hub walks its 100+ entries one by one while the others idle (15 / 32 us of an item's 38 / 69)
+        // holds the hub walks its 100+ entries one by one while the others idle: 'matrix' 17.2 -> 12.6 us (n' <= 48) / 32.3 -> 20.9 us
+        // (<= 64) of wave time per item against the fill by row (profiles/HISTORY.md, profiles/r4_posemb_phases_protos.txt)
         int32_t *rpl = (int32_t *)xinfo;             // [n + 1] <= kWaveNodes + 1 ints of the 8 * kWaveNodes bytes
         const int e0 = rp[0];
         for (int i = lane; i <= n; i += 64) rpl[i] = rp[i] - e0;
@@ -2228,19 +2053,6 @@ __global__ __launch_bounds__(kWaveTeams * 64, kNMax <= 48 ? GCC_POSEMB_W48_OCC :
         }
         wave_sync();                                 // rpl is done with before the records overwrite it
     }
-#else
-    for (int i = lane; i < n; i += 64) {             // lane = row
-        if (d.ridx[i] == kNone) continue;
-        const int ri = d.ridx[i];
-        const int di = rp[i + 1] - rp[i];
-        for (int e = rp[i]; e < rp[i + 1]; ++e) {
-            const int j = a.col_idx[e] - n0;
-            if (d.ridx[j] == kNone) continue;
-            const int dj = rp[j + 1] - rp[j];
-            A[ri * lda + d.ridx[j]] = defl_coupling(d, i, j) / sqrtf((float)di * (float)dj);   // in_degrees().clip(1) ** -0.5 on both sides
-        }
-    }
-#endif
     // what the expansion at the end needs of the tables, 8 bytes per node
     for (int v = lane; v < n; v += 64) defl_record(d, v, rp, a.col_idx, n0, xinfo + 4 * v);
     wave_sync();
@@ -2268,8 +2080,8 @@ __global__ __launch_bounds__(kWaveTeams * 64, kNMax <= 48 ? GCC_POSEMB_W48_OCC :
         }
     }
     // ---- expand to the n original nodes; x = normalize(u, "l2") row-wise, zero padded (data_util.py:260-262); lane = column
-#if GCC_POSEMB_EXPAND4
-    {   // four nodes per iteration: 16 lanes per node, columns c and c + 16 per lane (half the iterations of the loop below)
+    {   // four nodes per iteration: 16 lanes per node, columns c and c + 16 per lane.  (Two nodes per iteration, 32 lanes each, measured
+        // 'expand' 12.7 against 10.7 us (n' <= 48) / 19.5 against 15.9 us (<= 64) per item: profiles/HISTORY.md.)
         const int c16 = lane & 15, nv = lane >> 4;
         const int src0 = c16 < k ? colsrc[c16] : 0, src1 = c16 + 16 < k ? colsrc[c16 + 16] : 0;
         for (int v0 = 0; v0 < n; v0 += 4) {
@@ -2293,24 +2105,6 @@ __global__ __launch_bounds__(kWaveTeams * 64, kNMax <= 48 ? GCC_POSEMB_W48_OCC :
             }
         }
     }
-#else
-    // (two nodes per iteration: lanes 0-31 write node v, lanes 32-63 node v + 1)
-    const int col = lane & 31, hv = lane >> 5;
-    const int src = col < k ? colsrc[col] : 0;
-    for (int v0 = 0; v0 < n; v0 += 2) {
-        const int v = v0 + hv;
-        const bool valid = v < n;
-        const int vv = valid ? v : 0;
-        const int rsrc = xinfo[4 * vv + 0], o = xinfo[4 * vv + 1], g = xinfo[4 * vv + 2], cb = xinfo[4 * vv + 3];
-        const float val = valid && col < k ? defl_expand(rsrc, o, g, cb, src, w.Y, kYld) : 0.f;
-        const float s2 = half32_sum(val * val);
-        const float inv = s2 > 0.f ? 1.0f / sqrtf(s2) : 1.0f;
-        if (valid && col < a.hidden) {
-            a.pos[(int64_t)(n0 + v) * a.hidden + col] = val * inv;
-            if (a.raw) a.raw[(int64_t)(n0 + v) * a.hidden + col] = val;
-        }
-    }
-#endif
     WAVE_TICK(6);                                    // expansion
     if (m.ticks && lane == 0)
         atomicAdd((unsigned long long *)&m.ticks[kCls * 16 + 14], dense_solve_flops(nr, kq, na, es.diag_its, 4 * 12, n, k));
@@ -2340,10 +2134,29 @@ constexpr int kCsrCap = 10240;        // edges of a subgraph kept in LDS (uint16
 constexpr int kKThreads = 1024;      // 16 waves: the long-vector work is bound by L2 latency, not by FLOPs
 constexpr int kKWaves = kKThreads / 64;
 
+// Dynamic LDS of posemb_krylov_kernel (byte offsets); a function of the run-time vector length ldv:
+//   x, w, dinv [ldv] | TriLds head of the kM x kM Ritz problem | its LU slots, all kVecCap at once | ccol [kCsrCap], crow [ldv] (uint16)
+struct KryLds { int x, w, dinv, tri, lu, ccol, crow, bytes; };
+__host__ __device__ constexpr KryLds kry_lds(int ldv)
+{
+    KryLds l{};
+    l.x = 0;
+    l.w = l.x + (int)sizeof(float) * ldv;
+    l.dinv = l.w + (int)sizeof(float) * ldv;
+    l.tri = l.dinv + (int)sizeof(float) * ldv;
+    l.lu = l.tri + (int)sizeof(float) * tri_head_floats(kM, kVecCap * (kVecCap + 1), kKThreads);
+    l.ccol = l.lu + tri_lu_bytes(kM, kVecCap);
+    l.crow = l.ccol + (int)sizeof(uint16_t) * kCsrCap;
+    l.bytes = l.crow + (int)sizeof(uint16_t) * ldv;
+    return l;
+}
+
+// a workgroup's share of the workspace: two bases of kM + 1 vectors (ping-pong: the restart rotation is out of place)
+__host__ __device__ constexpr int64_t kry_basis_floats(int64_t ldv) { return 2 * (kM + 1) * ldv; }
 struct KryArgs {
     PosMulti m;
     PosHead hd;
-    float *vws;              // [workgroups][2][(kM + 1) * ldv]   ping-pong basis (the restart rotation is out of place)
+    float *vws;              // [workgroups][kry_basis_floats(ldv)]
     int32_t ldv;             // column stride (>= max n, multiple of 64)
 };
 
@@ -2384,27 +2197,17 @@ __global__ __launch_bounds__(kKThreads) void posemb_krylov_kernel(KryArgs ka)
     if (m.ticks && tid == 0) atomicAdd((unsigned long long *)&m.ticks[kCls * 16 + 15], 1ull);   // items
     const int n0 = a.node_off[b], n = a.node_off[b + 1] - n0;
     const int ldv = ka.ldv;
-    float *V = ka.vws + (int64_t)blockIdx.x * 2 * (kM + 1) * ldv;     // the workgroup's own basis storage
+    float *V = ka.vws + (int64_t)blockIdx.x * kry_basis_floats(ldv);  // the workgroup's own basis storage
     float *Valt = V + (int64_t)(kM + 1) * ldv;
-    float *x = (float *)smem, *w = x + ldv, *dinv = w + ldv;
+    const KryLds lds = kry_lds(ldv);
+    float *x = (float *)(smem + lds.x), *w = (float *)(smem + lds.w), *dinv = (float *)(smem + lds.dinv);
     TriLds tw;                                       // Rayleigh-Ritz problem (kM x kM) for the direct solver core
-    tw.dg = dinv + ldv;
-    tw.of = tw.dg + kM;
-    tw.of2 = tw.of + kM;
-    tw.tau = tw.of2 + kM;
-    tw.pbuf = tw.tau + kM;
-    tw.vbuf = tw.pbuf + kM;
-    tw.coef = tw.vbuf + kM;
-    tw.cnt = (int *)(tw.coef + kVecCap * (kVecCap + 1));
+    tri_bind_head(tw, (float *)(smem + lds.tri), kM, kVecCap * (kVecCap + 1));
     tw.Y = Yj;
     tw.ldy = kVecCap + 1;
-    tw.bw = kVecCap;
-    tw.ldu = kVecCap + 1;
-    tw.Ud = (float *)(tw.cnt + kKThreads);
-    tw.Us = tw.Ud + kM * tw.ldu;
-    tw.Uf = (uint8_t *)(tw.Us + kM * tw.ldu);
-    uint16_t *ccol = (uint16_t *)(tw.Uf + kM * kVecCap);    // [kCsrCap] local column ids of the subgraph's CSR
-    uint16_t *crow = ccol + kCsrCap;                        // [ldv] row offsets
+    tri_bind_lu(tw, (float *)(smem + lds.lu), 0, kM, kVecCap);
+    uint16_t *ccol = (uint16_t *)(smem + lds.ccol);         // [kCsrCap] local column ids of the subgraph's CSR
+    uint16_t *crow = (uint16_t *)(smem + lds.crow);         // [ldv] row offsets
     const int k = min(n - 2, a.hidden);
     const int keep = min(k + kKeepExtra, kM - 8);
     const int lda = kM + 1;
@@ -2736,30 +2539,53 @@ constexpr int kChMaxRitz = 5;      // Ritz steps of an item (the first one: valu
 constexpr float kChTol = 2e-5f;      // residual norm of the wanted Ritz pairs
 constexpr double kChShift = 1e-8;
 constexpr float kChAmpLog = 12.9f;  // ln of the largest filter amplification between two re-orthonormalisations (4e5; at 1e7 fp32 loses the guard end and one hub ego-net in 29 misses the strict invariants)
-constexpr int kChLdy = kChP + 1;
 constexpr int kChBw = 32;            // inverse iterations of the Ritz problem per batch
 
 struct LdsYes { static constexpr bool value = true; };
 struct LdsNo { static constexpr bool value = false; };
 
+constexpr int64_t kChBufFloats = (int64_t)kNodeMax * kChP;   // one block buffer; a workgroup has three in the workspace
 struct ChebArgs {
     PosMulti m;
     PosHead hd;
-    float *xws;              // [workgroups][3][kNodeMax * kChP]  the block buffers
-    uint32_t *tabs;          // [workgroups][kNodeMax * 4]        deflation tables once the matrix is built
+    float *xws;              // [workgroups][3][kChBufFloats]     the block buffers
+    uint32_t *tabs;          // [workgroups][kTabFloats]          expansion records once the matrix is built
 };
 
-__host__ __device__ constexpr int cheb_region_bytes()
-{
-    // the largest of: deflation tables (16 KiB) | two fp64 64 x 64 matrices (64 KiB) | the Ritz problem: L, H/C, Y and the
-    // Gram-Schmidt coefficients (64 x 65 each), the solver's vectors, Sturm counts, LU slots
-    constexpr int ritz = (int)sizeof(float) * (4 * kChP * kChLdy + 7 * kChP + kChThreads + 2 * kChP * (kChBw + 1)) + kChP * kChBw;
-    return ritz > 3 * 32768 ? ritz : 3 * 32768;              // ... | three fp64 64 x 64 matrices (G, K, L^-1)
-}
-__host__ __device__ constexpr int cheb_lds_bytes()
-{
-    return 2 * (kNodeMax + 8) + 2 * kChCsrCap + 4 * kNodeMax + 4 * kChSlabFloats + cheb_region_bytes();
-}
+// The Ritz problem of a P-column block in the region of ChebLds (float offsets):
+//   Lf (L^-1, fp32) | Af (H, later C with stride P) | Y [P][P + 1] each | TriLds head | LU slots of kChBw inverse iterations
+template <int P>
+struct ChebRitzLds {
+    static constexpr int Ldy = P + 1;
+    static constexpr int Lf = 0;
+    static constexpr int Af = Lf + P * Ldy;
+    static constexpr int Y = Af + P * Ldy;
+    static constexpr int tri = Y + P * Ldy;
+    static constexpr int lu = tri + tri_head_floats(P, P * Ldy, kChThreads);
+    static constexpr int bytes = (int)sizeof(float) * lu + tri_lu_bytes(P, kChBw);
+};
+// ... and the three fp64 P x P matrices of a round (offsets in doubles): G, K and L^-1 (lower; upper triangle = scratch)
+template <int P>
+struct ChebDenseLds {
+    static constexpr int G = 0, K = G + P * P, Li = K + P * P;
+    static constexpr int bytes = (Li + P * P) * (int)sizeof(double);
+};
+// Dynamic LDS of posemb_cheb_kernel (byte offsets): the deflated CSR, the row scales and the slab of partial sums for the
+// whole item, then one region used by lifetime: the deflation tables | rows of the block while the filter runs | three
+// fp64 P x P matrices (G, K, L^-1) | the Ritz problem
+struct ChebLds {
+    static constexpr int crow = 0;                                                   // [kNodeMax + 1] uint16, padded to + 8
+    static constexpr int ccol = crow + (int)sizeof(uint16_t) * (kNodeMax + 8);       // [kChCsrCap] uint16
+    static constexpr int scale = ccol + (int)sizeof(uint16_t) * kChCsrCap;           // [kNodeMax] float
+    static constexpr int slab = scale + (int)sizeof(float) * kNodeMax;               // [kChSlabFloats] float
+    static constexpr int region = slab + (int)sizeof(float) * kChSlabFloats;
+    static constexpr int dense_bytes = ChebDenseLds<kChP>::bytes;
+    static constexpr int ritz_pad = kChP * (int)sizeof(float);                       // one spare vector behind the Ritz problem (no user)
+    static constexpr int ritz_bytes = ChebRitzLds<kChP>::bytes + ritz_pad;
+    static constexpr int region_bytes = ritz_bytes > dense_bytes ? ritz_bytes : dense_bytes;
+    static constexpr int bytes = region + region_bytes;
+    static_assert(region_bytes >= kNodeMax * kDeflNodeBytes, "the deflation tables overlay the region of the dense matrices");
+};
 
 __global__ __launch_bounds__(kChThreads) GCC_CHEB_REG_CAP void posemb_cheb_kernel(ChebArgs ca)
 {
@@ -2778,11 +2604,11 @@ __global__ __launch_bounds__(kChThreads) GCC_CHEB_REG_CAP void posemb_cheb_kerne
     const PosMulti &m = ca.m;
     const PosHead &hd = ca.hd;
     constexpr int kNW = kChThreads / 64;
-    uint16_t *crow = (uint16_t *)smem;                       // [kNodeMax + 1] row offsets of the deflated CSR
-    uint16_t *ccol = crow + (kNodeMax + 8);                  // [kChCsrCap]
-    float *scale = (float *)(ccol + kChCsrCap);              // [kNodeMax] M' = diag(scale) A' diag(scale)
-    float *slab = scale + kNodeMax;                          // [chunk slots][P] partial sums of the long rows (kChSlabFloats)
-    unsigned char *region = (unsigned char *)(slab + kChSlabFloats);
+    uint16_t *crow = (uint16_t *)(smem + ChebLds::crow);     // [kNodeMax + 1] row offsets of the deflated CSR
+    uint16_t *ccol = (uint16_t *)(smem + ChebLds::ccol);     // [kChCsrCap]
+    float *scale = (float *)(smem + ChebLds::scale);         // [kNodeMax] M' = diag(scale) A' diag(scale)
+    float *slab = (float *)(smem + ChebLds::slab);           // [chunk slots][P] partial sums of the long rows (kChSlabFloats)
+    unsigned char *region = smem + ChebLds::region;
     for (;;) {                                               // items of this class
     __syncthreads();
     if (threadIdx.x == 0) sh_item = atomicAdd(hd.next + kCls, 1);
@@ -2807,7 +2633,7 @@ __global__ __launch_bounds__(kChThreads) GCC_CHEB_REG_CAP void posemb_cheb_kerne
     if (m.ticks && tid == 0) atomicAdd((unsigned long long *)&m.ticks[kCls * 16 + 15], 1ull);
     const int32_t *rp = a.row_ptr + n0;
     // three block buffers in the workspace (L2-resident): X, W = M' X or filter scratch, rotation target
-    float *XA0 = ca.xws + (int64_t)blockIdx.x * 3 * kNodeMax * kChP, *XB0 = XA0 + (int64_t)kNodeMax * kChP, *XC0 = XB0 + (int64_t)kNodeMax * kChP;
+    float *XA0 = ca.xws + (int64_t)blockIdx.x * 3 * kChBufFloats, *XB0 = XA0 + kChBufFloats, *XC0 = XB0 + kChBufFloats;
 
     // ---- twin-leaf and stalk groups (as posemb_direct_kernel)
     Defl d;
@@ -2888,7 +2714,7 @@ __global__ __launch_bounds__(kChThreads) GCC_CHEB_REG_CAP void posemb_cheb_kerne
     }
     __syncthreads();
     // what the expansion at the end needs of the tables -> workspace, 8 bytes per node (the dense matrices overlay the tables)
-    uint16_t *xrec = (uint16_t *)(ca.tabs + (int64_t)blockIdx.x * kNodeMax * 4);
+    uint16_t *xrec = (uint16_t *)(ca.tabs + (int64_t)blockIdx.x * kTabFloats);
     for (int v = tid; v < n; v += kChThreads) defl_record(d, v, rp, a.col_idx, n0, xrec + 4 * v);
     __syncthreads();
     PHASE_TICK(0);                                           // deflation + sparse matrix
@@ -2977,7 +2803,7 @@ __global__ __launch_bounds__(kChThreads) GCC_CHEB_REG_CAP void posemb_cheb_kerne
     // vectors each was measured slower: 1.27 against 0.86 ms of products per item).  Blocks of at most kChLdsRows rows are
     // therefore copied into LDS first (coalesced, once per product: the region of the dense matrices is free while the
     // filter runs) and gathered from there; the result still goes to the L2-resident buffer, coalesced.
-    constexpr int kChLdsRows = cheb_region_bytes() / (P * (int)sizeof(float));
+    constexpr int kChLdsRows = ChebLds::region_bytes / (P * (int)sizeof(float));
     const bool lds_x = nr <= kChLdsRows;                     // block-uniform
     auto gather = [&](auto in_lds, const float *src, int e0, int e1, float *acc) {
         const float *base = decltype(in_lds)::value ? (const float *)region : src;
@@ -3142,7 +2968,8 @@ __global__ __launch_bounds__(kChThreads) GCC_CHEB_REG_CAP void posemb_cheb_kerne
         }
     };
 
-    double *G = (double *)region, *K = G + P * P;            // fp64 [P][P] each
+    using Dense = ChebDenseLds<P>;
+    double *G = (double *)region + Dense::G, *K = (double *)region + Dense::K;   // fp64 [P][P] each
     float cut = 0.2f;
     int deg = 6, remaining = 6, round = 0, nrr = 0;
     unsigned long long flops = 0;                            // executed FLOPs of this item (diagnostics, ticks[class][14])
@@ -3249,7 +3076,7 @@ __global__ __launch_bounds__(kChThreads) GCC_CHEB_REG_CAP void posemb_cheb_kerne
         // ---- small dense algebra, all waves, fp64 in LDS: Jacobi scaling G^ = D G D; shifted Cholesky G^ = L L^T
         //      (right-looking, two barriers per column); Linv = L^-1 by recursive doubling over the diagonal blocks
         //      (inv [A 0; B C] = [A^-1 0; -C^-1 B A^-1  C^-1]: 6 levels); with a Ritz step H = Linv K^ Linv^T
-        double *Li = K + P * P;                                  // [P][P] L^-1 (lower); upper triangle = scratch
+        double *Li = (double *)region + Dense::Li;               // [P][P] L^-1 (lower); upper triangle = scratch
         if (tid < P) {
             const double dd = G[tid * P + tid];
             const double di = dd > 1e-300 ? 1.0 / sqrt(dd) : 0.0;
@@ -3402,7 +3229,8 @@ __global__ __launch_bounds__(kChThreads) GCC_CHEB_REG_CAP void posemb_cheb_kerne
         }
         // ---- LDS region from here on: Lf (Linv, fp32) | Af (H, later C with stride P) | Y | solver arrays.  G, K and Li
         //      are dead once Linv and H have been copied out (through registers: the fp32 copies overlay them)
-        float *Lf = (float *)region, *Af = Lf + P * Ldy;
+        using Ritz = ChebRitzLds<P>;
+        float *Lf = (float *)region + Ritz::Lf, *Af = (float *)region + Ritz::Af;
         {
             float lrow[E], hrow[E];
             const int i = mi, j4 = mj;
@@ -3420,21 +3248,10 @@ __global__ __launch_bounds__(kChThreads) GCC_CHEB_REG_CAP void posemb_cheb_kerne
         }
         PHASE_TICK(7);                                           // triangular inverse, projected matrix
         TriLds tw;
-        tw.Y = Af + P * Ldy;
+        tw.Y = (float *)region + Ritz::Y;
         tw.ldy = Ldy;
-        tw.dg = tw.Y + P * Ldy;
-        tw.of = tw.dg + P;
-        tw.of2 = tw.of + P;
-        tw.tau = tw.of2 + P;
-        tw.pbuf = tw.tau + P;
-        tw.vbuf = tw.pbuf + P;
-        tw.coef = tw.vbuf + P;
-        tw.cnt = (int *)(tw.coef + P * Ldy);
-        tw.bw = kChBw;
-        tw.ldu = kChBw + 1;
-        tw.Ud = (float *)(tw.cnt + kChThreads);
-        tw.Us = tw.Ud + P * tw.ldu;
-        tw.Uf = (uint8_t *)(tw.Us + P * tw.ldu);
+        tri_bind_head(tw, (float *)region + Ritz::tri, P, P * Ldy);
+        tri_bind_lu(tw, (float *)region, Ritz::lu, P, kChBw);
         __syncthreads();
         if (rr) {
             // Ritz problem: all P pairs of H by the dense solver core
@@ -3671,61 +3488,118 @@ extern "C" {
 
 static long long *g_posemb_ticks = nullptr;
 struct PosGrids { int32_t small, mid, slot, kry, big, cheb, w48, w64, pair; };
-static PosGrids posemb_grids(int64_t T, bool gated = false)
+
+// The run-time knobs, read in one place.  The grid caps and the list sort are read ONCE per process (callers cache the
+// workspace size, which depends on the caps); the path switches are read per call (A/B runs and the tests flip them
+// inside one process).
+struct PosKnobs {
+    int caps[9];                     // GCC_POSEMB_GRID_CAPS="small,mid,slot,krylov,big,cheb,w48,w64,pair": workgroups per class
+    int gcaps[2];                    // GCC_POSEMB_GATED_CAPS="mid,cheb": ... of a call behind a gate
+    bool sort;                       // GCC_POSEMB_SORT: work lists longest item first
+    int use_cheb;                    // GCC_POSEMB_CHEB: 0 dense classes only, 1 on; A/B bits, OR-ed in: 2 = the wide block only, 4 = the filter through L2
+    bool use_wave;                   // GCC_POSEMB_WAVE: 0 = the 256-thread small class takes every n' <= 64
+    bool use_stalks;                 // GCC_POSEMB_STALKS: 0 = twin leaves only
+    bool use_pair;                   // GCC_POSEMB_PAIR: 0 = the 65..128 class on 1,024-thread workgroups with the matrix in LDS
+    int fork;                        // GCC_POSEMB_FORK: side streams (posemb_side_streams), unless gcc_posemb_set_fork decided
+};
+static PosKnobs posemb_knobs(void)
 {
-    // fixed grids: enough workgroups for the typical class sizes (~73 % / 19 % / 6 % / 2 % of a batch at rw_hops 256);
-    // larger classes loop.  No class may cover more than half of the 256 CUs (small: 2 workgroups per CU): a solver
-    // workgroup holds most of a CU's LDS for milliseconds, and when every CU has one the training step's kernels whose
-    // workgroups do not fit beside it wait for the whole launch to drain (3-5 ms stalls in the kernel trace).
-    static int caps[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
-    if (caps[0] == 0) {                              // tuning knob: GCC_POSEMB_GRID_CAPS="small,mid,slot,krylov,big,cheb,w48,w64,pair"
-        int c[9] = {256, 64, 128, 64, 64, 96, 128, 64, 192};     // (pair 128 -> 192 once the work lists were sorted, profiles/r6_bench_sorted_lists.txt: the driver's window 0.752 -> 0.740, sustained 0.735 -> 0.742) round 6: the one-wave teams 512 / 128 -> 128 / 64 (their workgroups hold 74 / 111 KiB of LDS each: at two per CU
-                                                                 // no CU had room for a 49 KiB gin_in_kernel workgroup while they ran): sustained 0.776 -> 0.743 ms per step, the
-                                                                 // driver's 20-step window unchanged (0.785 vs 0.788); smaller caps still (64 / 32, or cheb 64) win another 1-2 %
-                                                                 // sustained and LOSE 5-10 % in the 20-step window (profiles/r6_bench_grid_caps.txt)    // the defaults: cheb 96, one-wave teams 512 / 128, pair 128 (scripts/gpu/r3_call4.sh: bench by caps; pair: r5_call10.sh 64: 0.837, 128: 0.836, 256: 0.856 ms per step; the cheb 64 / teams 256, 64 setting of r5_call12.sh measured 0.819 once and inside the spread afterwards: not adopted)
-        const char *e = getenv("GCC_POSEMB_GRID_CAPS");
-        if (e) (void)sscanf(e, "%d,%d,%d,%d,%d,%d,%d,%d,%d", &c[0], &c[1], &c[2], &c[3], &c[4], &c[5], &c[6], &c[7], &c[8]);
-        for (int i = 0; i < 9; ++i) caps[i] = c[i] < 1 ? 1 : c[i];
-    }
+    // Grid caps: enough workgroups for the typical class sizes (~73 % / 19 % / 6 % / 2 % of a batch at rw_hops 256); larger
+    // classes loop.  No class may cover more than half of the 256 CUs (small: 2 workgroups per CU): a solver workgroup holds
+    // most of a CU's LDS for milliseconds, and when every CU has one the training step's kernels whose workgroups do not fit
+    // beside it wait for the whole launch to drain (3-5 ms stalls in the kernel trace).  One-wave teams 128 / 64: their
+    // workgroups hold 74 / 111 KiB of LDS, and at two per CU no CU has room for a 49 KiB workgroup of the training step.
+    // Block class 96 and the rest: smaller caps gain 1-2 % sustained and lose 5-10 % in a 20-step window.  Four-wave teams
+    // 192: what the sorted work lists pay for.  (profiles/r6_bench_grid_caps.txt, profiles/r6_bench_sorted_lists.txt)
+    // Behind a gate the heavy phases of concurrent calls take turns: one call's heavy workgroups may then hold half of the CUs.
+    static const PosKnobs once = [] {
+        PosKnobs k = {{256, 64, 128, 64, 64, 96, 128, 64, 192}, {128, 128}, true, 1, true, true, true, 0};
+        int *c = k.caps, *g = k.gcaps;
+        if (const char *e = getenv("GCC_POSEMB_GRID_CAPS"))
+            (void)sscanf(e, "%d,%d,%d,%d,%d,%d,%d,%d,%d", &c[0], &c[1], &c[2], &c[3], &c[4], &c[5], &c[6], &c[7], &c[8]);
+        if (const char *e = getenv("GCC_POSEMB_GATED_CAPS")) (void)sscanf(e, "%d,%d", &g[0], &g[1]);
+        for (int i = 0; i < 9; ++i) c[i] = c[i] < 1 ? 1 : c[i];
+        for (int i = 0; i < 2; ++i) g[i] = g[i] < 1 ? 1 : g[i];
+        if (const char *e = getenv("GCC_POSEMB_SORT")) k.sort = atoi(e) != 0;
+        return k;
+    }();
+    PosKnobs k = once;
+    if (const char *e = getenv("GCC_POSEMB_CHEB")) k.use_cheb = atoi(e);
+    if (const char *e = getenv("GCC_POSEMB_WAVE")) k.use_wave = atoi(e) != 0;
+    if (const char *e = getenv("GCC_POSEMB_STALKS")) k.use_stalks = atoi(e) != 0;
+    if (const char *e = getenv("GCC_POSEMB_PAIR")) k.use_pair = atoi(e) != 0;
+    if (const char *e = getenv("GCC_POSEMB_FORK")) k.fork = atoi(e);
+    return k;
+}
+
+// fixed grids: min(the class's share of T items, its cap)
+static PosGrids posemb_grids(const PosKnobs &k, int64_t T, bool gated)
+{
+    const int *caps = k.caps;
+    auto lim = [](int64_t want, int cap) { return (int32_t)(want < cap ? want : cap); };
     PosGrids g;
-    g.small = (int32_t)(T < caps[0] ? T : caps[0]);
-    // behind a gate the heavy phases of concurrent calls take turns: one call's heavy workgroups may then hold half of
-    // the CUs (GCC_POSEMB_GATED_CAPS="mid,cheb")
-    static int gcaps[2] = {0, 0};
-    if (gcaps[0] == 0) {
-        int c[2] = {128, 128};
-        const char *e = getenv("GCC_POSEMB_GATED_CAPS");
-        if (e) (void)sscanf(e, "%d,%d", &c[0], &c[1]);
-        gcaps[0] = c[0] < 1 ? 1 : c[0]; gcaps[1] = c[1] < 1 ? 1 : c[1];
-    }
-    const int cap_mid = gated ? gcaps[0] : caps[1], cap_cheb = gated ? gcaps[1] : caps[5];
-    g.mid = (int32_t)((T + 3) / 4 < cap_mid ? (T + 3) / 4 : cap_mid);
-    g.slot = (int32_t)((T + 7) / 8 < caps[2] ? (T + 7) / 8 : caps[2]);
-    g.kry = (int32_t)((T + 15) / 16 < caps[3] ? (T + 15) / 16 : caps[3]);
-    g.big = (int32_t)((T + 15) / 16 < caps[4] ? (T + 15) / 16 : caps[4]);
-    g.cheb = (int32_t)((T + 7) / 8 < cap_cheb ? (T + 7) / 8 : cap_cheb);
-    // one-wave teams: kWaveTeams items in flight per workgroup
-    const int64_t wg = (T + kWaveTeams - 1) / kWaveTeams;
-    g.w48 = (int32_t)(wg < caps[6] ? wg : caps[6]);
-    g.w64 = (int32_t)((wg + 1) / 2 < caps[7] ? (wg + 1) / 2 : caps[7]);
-    const int cap_pair = gated ? 2 * caps[8] : caps[8];
-    g.pair = (int32_t)((T + 1) / 2 < cap_pair ? (T + 1) / 2 : cap_pair);
+    g.small = lim(T, caps[0]);
+    g.mid = lim((T + 3) / 4, gated ? k.gcaps[0] : caps[1]);
+    g.slot = lim((T + 7) / 8, caps[2]);
+    g.kry = lim((T + 15) / 16, caps[3]);
+    g.big = lim((T + 15) / 16, caps[4]);
+    g.cheb = lim((T + 7) / 8, gated ? k.gcaps[1] : caps[5]);
+    const int64_t wg = (T + kWaveTeams - 1) / kWaveTeams;    // one-wave teams: kWaveTeams items in flight per workgroup
+    g.w48 = lim(wg, caps[6]);
+    g.w64 = lim((wg + 1) / 2, caps[7]);
+    g.pair = lim((T + 1) / 2, gated ? 2 * caps[8] : caps[8]);
     return g;
 }
 // workspace sizing: the larger of the two grid sets, so that one workspace serves gated and ungated calls
-static PosGrids posemb_grids_for_sizing(int64_t T)
+static PosGrids posemb_grids_for_sizing(const PosKnobs &k, int64_t T)
 {
-    PosGrids a = posemb_grids(T, false);
-    const PosGrids b = posemb_grids(T, true);
+    PosGrids a = posemb_grids(k, T, false);
+    const PosGrids b = posemb_grids(k, T, true);
     a.mid = a.mid > b.mid ? a.mid : b.mid;
     a.cheb = a.cheb > b.cheb ? a.cheb : b.cheb;
     a.pair = a.pair > b.pair ? a.pair : b.pair;
     return a;
 }
-static int64_t posemb_head_bytes(int64_t T) { return ((16 + kNumCls * T) * 4 + 255) / 256 * 256; }
-static int64_t posemb_slot_floats(void) { return (int64_t)kGMax * kGMax + (int64_t)kNodeMax * 4; }
-static int64_t posemb_bslot_floats(void) { return (int64_t)kBMax * kBMax + (int64_t)kNodeMax * 4; }
 static int64_t posemb_ldv(int32_t batch_size, int64_t node_cap) { return ((node_cap / batch_size + 63) / 64) * 64 + 64; }
+
+// The caller's workspace, stated once: byte offsets of every region (each on a 256-byte boundary of a 256-byte-aligned
+// workspace) and the total.  gcc_posemb_multi_workspace_bytes returns `total`, gcc_posemb_multi_gated binds PosHead,
+// KryArgs and ChebArgs from the same object; the regions are sized by the sizing grids `gs`.
+struct PosWorkLayout {
+    PosGrids gs;
+    int64_t ldv;
+    int64_t head;                    // PosHead: counts [8] | work counters [8] | lists [kNumCls][T]   (int32)
+    int64_t slots;                   // [gs.slot][DirectSlot<kGMax>]
+    int64_t bslots;                  // [gs.big][DirectSlot<kBMax>]
+    int64_t tabs;                    // [gs.mid + gs.small][kTabFloats]     expansion records of the LDS-resident classes
+    int64_t vws;                     // [gs.kry][kry_basis_floats(ldv)]      Krylov bases
+    int64_t xws;                     // [gs.cheb][3][kChBufFloats]           block buffers
+    int64_t ctabs;                   // [gs.cheb][kTabFloats]                the block class's tables
+    int64_t pslots;                  // [gs.pair][PairSlot]
+    int64_t total;
+};
+// Three unused 256-byte lines in front of the last region: earlier versions sized them in, and callers cache the sizes.
+constexpr int64_t kWorkKeptPad = 768;
+static PosWorkLayout posemb_work_layout(const PosKnobs &k, int32_t num_views, int32_t batch_size, int64_t node_cap)
+{
+    const int64_t T = (int64_t)num_views * batch_size, F = (int64_t)sizeof(float);
+    PosWorkLayout l;
+    l.gs = posemb_grids_for_sizing(k, T);
+    l.ldv = posemb_ldv(batch_size, node_cap);
+    int64_t at = 0;
+    auto take = [&at](int64_t bytes) { const int64_t off = at; at = (at + bytes + 255) / 256 * 256; return off; };
+    l.head = take((16 + kNumCls * T) * 4);
+    l.slots = take(l.gs.slot * DirectSlot<kGMax>::floats * F);
+    l.bslots = take(l.gs.big * DirectSlot<kBMax>::floats * F);
+    l.tabs = take((int64_t)(l.gs.mid + l.gs.small) * kTabFloats * F);
+    l.vws = take(l.gs.kry * kry_basis_floats(l.ldv) * F);
+    l.xws = take(l.gs.cheb * 3 * kChBufFloats * F);
+    l.ctabs = take((int64_t)l.gs.cheb * kTabFloats * F);
+    (void)take(kWorkKeptPad);
+    l.pslots = take((int64_t)l.gs.pair * PairSlot::floats * F);
+    l.total = at;
+    return l;
+}
 
 // The solver classes of one call are independent of each other once the classify kernel has written their lists (only the block class
 // hands items on: to the Krylov / workspace classes behind it).  On ONE in-order stream each class's launch waits for the previous one
@@ -3766,14 +3640,7 @@ int64_t gcc_posemb_multi_workspace_bytes(int32_t num_views, int32_t batch_size, 
         snprintf(g_err, kErrLen, "gcc_posemb_multi_workspace_bytes: bad argument");
         return -1;
     }
-    const int64_t T = (int64_t)num_views * batch_size;
-    const PosGrids g = posemb_grids_for_sizing(T);
-    return posemb_head_bytes(T) + g.slot * posemb_slot_floats() * (int64_t)sizeof(float)
-           + g.big * posemb_bslot_floats() * (int64_t)sizeof(float)
-           + (int64_t)(g.mid + g.small) * kNodeMax * 16
-           + (int64_t)g.kry * 2 * (kM + 1) * posemb_ldv(batch_size, node_cap) * (int64_t)sizeof(float)
-           + (int64_t)g.cheb * (3 * (int64_t)kNodeMax * kChP * (int64_t)sizeof(float) + (int64_t)kNodeMax * 16) + 512
-           + (int64_t)g.pair * kPairSlotFloats * (int64_t)sizeof(float) + 256;
+    return posemb_work_layout(posemb_knobs(), num_views, batch_size, node_cap).total;
 }
 
 int64_t gcc_posemb_workspace_bytes(int32_t batch_size, int64_t node_cap, int32_t hidden)
@@ -3797,9 +3664,10 @@ int32_t gcc_posemb_multi_gated(const gcc_posemb_view *views, int32_t num_views, 
         snprintf(g_err, kErrLen, "gcc_posemb_multi: bad argument");
         return -1;
     }
-    const int64_t need = gcc_posemb_multi_workspace_bytes(num_views, batch_size, node_cap, hidden);
-    if (!workspace || workspace_bytes < need) {
-        snprintf(g_err, kErrLen, "gcc_posemb: workspace %lld < %lld bytes", (long long)workspace_bytes, (long long)need);
+    const PosKnobs knobs = posemb_knobs();
+    const PosWorkLayout wl = posemb_work_layout(knobs, num_views, batch_size, node_cap);
+    if (!workspace || workspace_bytes < wl.total) {
+        snprintf(g_err, kErrLen, "gcc_posemb: workspace %lld < %lld bytes", (long long)workspace_bytes, (long long)wl.total);
         return -3;
     }
     PosMulti m;
@@ -3811,87 +3679,75 @@ int32_t gcc_posemb_multi_gated(const gcc_posemb_view *views, int32_t num_views, 
     m.nviews = num_views; m.B = batch_size; m.hidden = hidden; m.seed = seed; m.status = status;
     m.ticks = g_posemb_ticks;
     const int64_t T = (int64_t)num_views * batch_size;
-    const PosGrids g = posemb_grids(T, heavy_wait != nullptr || heavy_record != nullptr);
-    const PosGrids gs = posemb_grids_for_sizing(T);     // the workspace is carved up by the sizing grids
+    const PosGrids g = posemb_grids(knobs, T, heavy_wait != nullptr || heavy_record != nullptr);
     hipStream_t s = (hipStream_t)stream;
+    char *const ws = (char *)workspace;
     PosHead hd;
-    hd.count = (int32_t *)workspace;
+    hd.count = (int32_t *)(ws + wl.head);
     hd.next = hd.count + 8;
     hd.list = hd.count + 16;
-    hd.slots = (float *)((char *)workspace + posemb_head_bytes(T));
-    hd.bslots = hd.slots + gs.slot * posemb_slot_floats();
-    hd.bslot_floats = posemb_bslot_floats();
-    hd.tabs = hd.bslots + gs.big * posemb_bslot_floats();
-    hd.tabs_small_off = gs.mid;
+    hd.slots = (float *)(ws + wl.slots);
+    hd.slot_floats = DirectSlot<kGMax>::floats;
+    hd.bslots = (float *)(ws + wl.bslots);
+    hd.bslot_floats = DirectSlot<kBMax>::floats;
+    hd.tabs = (float *)(ws + wl.tabs);
+    hd.tabs_small_off = wl.gs.mid;
+    hd.pslots = (float *)(ws + wl.pslots);
     hd.T = (int32_t)T;
-    hd.slot_floats = posemb_slot_floats();
-    hd.ldv = (int32_t)posemb_ldv(batch_size, node_cap);
-    {
-        const char *e = getenv("GCC_POSEMB_CHEB");
-        hd.use_cheb = e ? atoi(e) : 1;             // 0: dense classes only, 1: on; A/B knobs, OR-ed in: 2 = the wide block only, 4 = the filter through L2 (7 = rounds 2-4)
-        const char *ew = getenv("GCC_POSEMB_WAVE");   // 0: the 256-thread small class takes every n' <= 64 (A/B runs)
-        hd.use_wave = ew ? atoi(ew) != 0 : 1;
-        const char *es = getenv("GCC_POSEMB_STALKS");  // 0: twin leaves only (A/B runs)
-        hd.use_stalks = es ? atoi(es) != 0 : 1;
-        const char *ep = getenv("GCC_POSEMB_PAIR");    // 0: the 65..128 class on 1,024-thread workgroups with the matrix in LDS (A/B runs)
-        hd.use_pair = ep ? atoi(ep) != 0 : 1;
-    }
-    {   // the register-resident class's slots: the tail of the workspace
-        char *end = (char *)workspace + need;
-        hd.pslots = (float *)(((uintptr_t)(end - (int64_t)gs.pair * kPairSlotFloats * (int64_t)sizeof(float))) & ~(uintptr_t)255);
-    }
-    constexpr int lds_small = direct_lds_bytes<kJSmall, kSmallT, false>();
-    constexpr int lds_big = direct_lds_bytes<kJMax, kMidT, false>();
-#ifndef GCC_AMD_HIPEMU
-    static bool attr_set = false;
-    if (!attr_set) {
-        (void)hipFuncSetAttribute((const void *)posemb_direct_kernel<kClsSmall, 0, kJSmall, kSmallT, false>,
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, lds_small);
-        (void)hipFuncSetAttribute((const void *)posemb_direct_kernel<kClsMid, kJSmall + 1, kJMax, kMidT, false>,
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, lds_big);
-        (void)hipFuncSetAttribute((const void *)posemb_direct_kernel<kClsSlot, kJMax + 1, kGMax, 1024, true>,
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, kGLds);
-        (void)hipFuncSetAttribute((const void *)posemb_direct_kernel<kClsBig, kGMax + 1, kBMax, 1024, true>,
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, kBLds);
-        (void)hipFuncSetAttribute((const void *)posemb_wave_kernel<kClsW48, 48>,
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, kWaveTeams * wave_team_bytes<48>());
-        (void)hipFuncSetAttribute((const void *)posemb_wave_kernel<kClsW64, 64>,
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, kWaveTeams * wave_team_bytes<64>());
-        attr_set = true;
-    }
-#endif
-    prof_mark(prof, 0, s);
-    (void)hipMemsetAsync(workspace, 0, 64, s);       // class counts + work counters
-    hipLaunchKernelGGL(posemb_classify_kernel, dim3((unsigned)((T + 3) / 4)), dim3(kClsThreads), 0, s, m, hd);
-    static const bool sort_lists = [] { const char *e = getenv("GCC_POSEMB_SORT"); return !e || atoi(e) != 0; }();
-    if (sort_lists) hipLaunchKernelGGL(posemb_sort_kernel, dim3(kNumCls), dim3(kSortThreads), 0, s, m, hd);
+    hd.ldv = (int32_t)wl.ldv;
+    hd.use_cheb = knobs.use_cheb;
+    hd.use_wave = knobs.use_wave;
+    hd.use_stalks = knobs.use_stalks;
+    hd.use_pair = knobs.use_pair;
     KryArgs ka;
     ka.m = m;
     ka.hd = hd;
-    ka.vws = hd.tabs + (int64_t)(gs.mid + gs.small) * kNodeMax * 4;
-    ka.ldv = (int32_t)posemb_ldv(batch_size, node_cap);
-    // longest items first
-    const size_t lds_kry = (size_t)3 * ka.ldv * sizeof(float)
-                           + sizeof(float) * (6 * kM + kVecCap * (kVecCap + 1) + kKThreads + 2 * kM * (kVecCap + 1)) + kM * kVecCap
-                           + sizeof(uint16_t) * ((size_t)kCsrCap + ka.ldv);
+    ka.vws = (float *)(ws + wl.vws);
+    ka.ldv = (int32_t)wl.ldv;
+    ChebArgs ca;
+    ca.m = m;
+    ca.hd = hd;
+    ca.xws = (float *)(ws + wl.xws);
+    ca.tabs = (uint32_t *)(ws + wl.ctabs);
+    using SmallLds = DirectLds<kJSmall, kSmallT, false, false>;
+    using MidLds = DirectLds<kJMax, kMidT, false, false>;
+    using PairLds = DirectLds<kJMax, kPairT, true, true>;
+    using SlotLds = DirectLds<kGMax, 1024, true, false>;
+    using BigLds = DirectLds<kBMax, 1024, true, false>;
+    const int lds_kry = kry_lds(ka.ldv).bytes;
 #ifndef GCC_AMD_HIPEMU
-    static size_t kry_lds_opt_in = 0;
-    if (lds_kry > kry_lds_opt_in) {                  // more than 64 KiB of dynamic LDS has to be opted into
-        (void)hipFuncSetAttribute((const void *)posemb_krylov_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_kry);
-        kry_lds_opt_in = lds_kry;
+    // more than 64 KiB of dynamic LDS has to be opted into: once per process, Krylov's whenever ldv has grown
+    static std::once_flag lds_opted_in;
+    std::call_once(lds_opted_in, [] {
+        auto opt_in = [](const void *kernel, int bytes) { (void)hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes); };
+        opt_in((const void *)posemb_direct_kernel<kClsSmall, 0, kJSmall, kSmallT, false>, SmallLds::bytes);
+        opt_in((const void *)posemb_direct_kernel<kClsMid, kJSmall + 1, kJMax, kMidT, false>, MidLds::bytes);
+        opt_in((const void *)posemb_direct_kernel<kClsSlot, kJMax + 1, kGMax, 1024, true>, SlotLds::bytes);
+        opt_in((const void *)posemb_direct_kernel<kClsBig, kGMax + 1, kBMax, 1024, true>, BigLds::bytes);
+        opt_in((const void *)posemb_wave_kernel<kClsW48, 48>, WaveLds<48>::bytes);
+        opt_in((const void *)posemb_wave_kernel<kClsW64, 64>, WaveLds<64>::bytes);
+        opt_in((const void *)posemb_cheb_kernel, ChebLds::bytes);
+    });
+    {
+        static std::mutex kry_mu;
+        static int kry_lds_opt_in = 0;
+        std::lock_guard<std::mutex> lk(kry_mu);
+        if (lds_kry > kry_lds_opt_in) {
+            (void)hipFuncSetAttribute((const void *)posemb_krylov_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds_kry);
+            kry_lds_opt_in = lds_kry;
+        }
     }
 #endif
+    prof_mark(prof, 0, s);
+    (void)hipMemsetAsync(hd.count, 0, 64, s);        // class counts + work counters
+    hipLaunchKernelGGL(posemb_classify_kernel, dim3((unsigned)((T + 3) / 4)), dim3(kClsThreads), 0, s, m, hd);
+    if (knobs.sort) hipLaunchKernelGGL(posemb_sort_kernel, dim3(kNumCls), dim3(kSortThreads), 0, s, m, hd);
     // the light classes (one-wave teams, the 256-thread small class) and the four-wave 65..128 class on the side streams, the block class and
     // what it may hand items on to on the caller's stream, behind the caller's gate (see gcc_posemb_multi_gated in the header)
     hipStream_t s1 = s, s2 = s;
 #ifndef GCC_AMD_HIPEMU
-    PosSide *side = nullptr;
-    int fork_mode = 0;
-    {
-        const char *ef = getenv("GCC_POSEMB_FORK");
-        fork_mode = g_posemb_fork >= 0 ? g_posemb_fork : (ef ? atoi(ef) : 0);
-        if (fork_mode) side = posemb_side_streams(s);
-    }
+    const int fork_mode = g_posemb_fork >= 0 ? g_posemb_fork : knobs.fork;
+    PosSide *side = fork_mode ? posemb_side_streams(s) : nullptr;
     if (side) {
         s1 = side->side[0]; s2 = fork_mode == 2 ? s1 : side->side[1];    // 2: ONE side stream for everything but the block class
         (void)hipEventRecord(side->fork, s);
@@ -3900,35 +3756,19 @@ int32_t gcc_posemb_multi_gated(const gcc_posemb_view *views, int32_t num_views, 
     }
 #endif
     if (heavy_wait) (void)hipStreamWaitEvent(s, (hipEvent_t)heavy_wait, 0);
-    if (hd.use_cheb) {
-        ChebArgs ca;
-        ca.m = m;
-        ca.hd = hd;
-        char *after_kry = (char *)(ka.vws + (int64_t)gs.kry * 2 * (kM + 1) * ka.ldv);
-        after_kry = (char *)(((uintptr_t)after_kry + 255) & ~(uintptr_t)255);
-        ca.xws = (float *)after_kry;
-        ca.tabs = (uint32_t *)(ca.xws + (int64_t)gs.cheb * 3 * kNodeMax * kChP);
-#ifndef GCC_AMD_HIPEMU
-        static bool cheb_attr = false;
-        if (!cheb_attr) {
-            (void)hipFuncSetAttribute((const void *)posemb_cheb_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, cheb_lds_bytes());
-            cheb_attr = true;
-        }
-#endif
-        hipLaunchKernelGGL(posemb_cheb_kernel, dim3(g.cheb), dim3(kChThreads), cheb_lds_bytes(), s, ca);
-    }
-    hipLaunchKernelGGL((posemb_direct_kernel<kClsSmall, 0, kJSmall, kSmallT, false>), dim3(g.small), dim3(kSmallT), lds_small, s1, m, hd);
+    if (hd.use_cheb) hipLaunchKernelGGL(posemb_cheb_kernel, dim3(g.cheb), dim3(kChThreads), ChebLds::bytes, s, ca);
+    hipLaunchKernelGGL((posemb_direct_kernel<kClsSmall, 0, kJSmall, kSmallT, false>), dim3(g.small), dim3(kSmallT), SmallLds::bytes, s1, m, hd);
     if (hd.use_wave) {
-        hipLaunchKernelGGL((posemb_wave_kernel<kClsW64, 64>), dim3(g.w64), dim3(kWaveTeams * 64), kWaveTeams * wave_team_bytes<64>(), s1, m, hd);
-        hipLaunchKernelGGL((posemb_wave_kernel<kClsW48, 48>), dim3(g.w48), dim3(kWaveTeams * 64), kWaveTeams * wave_team_bytes<48>(), s1, m, hd);
+        hipLaunchKernelGGL((posemb_wave_kernel<kClsW64, 64>), dim3(g.w64), dim3(kWaveTeams * 64), WaveLds<64>::bytes, s1, m, hd);
+        hipLaunchKernelGGL((posemb_wave_kernel<kClsW48, 48>), dim3(g.w48), dim3(kWaveTeams * 64), WaveLds<48>::bytes, s1, m, hd);
     }
     if (hd.use_pair)
-        hipLaunchKernelGGL((posemb_direct_kernel<kClsMid, kJSmall + 1, kJMax, kPairT, true, true>), dim3(g.pair), dim3(kPairT), kPairLds, s2, m, hd);
+        hipLaunchKernelGGL((posemb_direct_kernel<kClsMid, kJSmall + 1, kJMax, kPairT, true, true>), dim3(g.pair), dim3(kPairT), PairLds::bytes, s2, m, hd);
     else
-        hipLaunchKernelGGL((posemb_direct_kernel<kClsMid, kJSmall + 1, kJMax, kMidT, false>), dim3(g.mid), dim3(kMidT), lds_big, s2, m, hd);
+        hipLaunchKernelGGL((posemb_direct_kernel<kClsMid, kJSmall + 1, kJMax, kMidT, false>), dim3(g.mid), dim3(kMidT), MidLds::bytes, s2, m, hd);
     hipLaunchKernelGGL(posemb_krylov_kernel, dim3(g.kry), dim3(kKThreads), lds_kry, s, ka);
-    hipLaunchKernelGGL((posemb_direct_kernel<kClsBig, kGMax + 1, kBMax, 1024, true>), dim3(g.big), dim3(1024), kBLds, s, m, hd);
-    hipLaunchKernelGGL((posemb_direct_kernel<kClsSlot, kJMax + 1, kGMax, 1024, true>), dim3(g.slot), dim3(1024), kGLds, s, m, hd);
+    hipLaunchKernelGGL((posemb_direct_kernel<kClsBig, kGMax + 1, kBMax, 1024, true>), dim3(g.big), dim3(1024), BigLds::bytes, s, m, hd);
+    hipLaunchKernelGGL((posemb_direct_kernel<kClsSlot, kJMax + 1, kGMax, 1024, true>), dim3(g.slot), dim3(1024), SlotLds::bytes, s, m, hd);
 #ifndef GCC_AMD_HIPEMU
     if (side) {
         (void)hipEventRecord(side->join[0], s1);

@@ -4,6 +4,7 @@
 #include <execinfo.h>
 #include <signal.h>
 #include <unistd.h>
+#include <cstring>
 #include <vector>
 
 namespace hipemu {
@@ -141,8 +142,13 @@ void launch(Dim3 grid, Dim3 block, size_t smem, const std::function<void()> &bod
         fibers.resize(nthreads);
         for (size_t i = old; i < nthreads; ++i) fibers[i].stack = (char *)malloc(kStack);
     }
-    std::vector<unsigned char> dyn(smem + 64);
+    // a guard band behind the dynamic LDS: a kernel whose carve-up is larger than the size its host passed writes into it
+    constexpr size_t kGuard = 256;
+    constexpr unsigned char kGuardByte = 0xC7;
+    std::vector<unsigned char> dyn(smem + 64 + kGuard);
     g_dyn_smem = (unsigned char *)(((uintptr_t)dyn.data() + 63) & ~(uintptr_t)63);
+    unsigned char *guard = g_dyn_smem + smem;
+    memset(guard, kGuardByte, kGuard);
     g_blockDim = block;
     g_gridDim = grid;
     body_fn = &body;
@@ -186,6 +192,8 @@ void launch(Dim3 grid, Dim3 block, size_t smem, const std::function<void()> &bod
             }
             if (!progressed) die("deadlock: no fiber can make progress");
         }
+        for (size_t i = 0; i < kGuard; ++i)
+            if (guard[i] != kGuardByte) die("write past the end of the dynamic LDS");
     }
     body_fn = nullptr;
     g_dyn_smem = nullptr;

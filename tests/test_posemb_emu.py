@@ -202,15 +202,11 @@ def test_large_subgraphs_workspace_resident_direct_path(cheb, monkeypatch):
     _check(view, x, evals, raw)
 
 
-@pytest.mark.parametrize("cheb", ["0", "1"])
-def test_krylov_fallback_above_the_direct_limit(cheb, monkeypatch):
-    """Deflated size > 704 (no twin leaves at all).  cheb=0: thick-restart Krylov-Schur (single vector, ARPACK-like
-    invariants); cheb=1: the sparse block class is tried first and hands this (dense) graph on."""
+def skewed_dense_graph(n, seed=1):
+    """A connected graph of n nodes with skewed degrees, like an ego-net, and no twin leaves -> scipy CSR"""
     import scipy.sparse as sp
 
-    monkeypatch.setenv("GCC_POSEMB_CHEB", cheb)
-    rng = np.random.RandomState(1)
-    n = 760
+    rng = np.random.RandomState(seed)
     w = 1.0 / np.arange(1, n + 1) ** 0.5                        # skewed degrees, like an ego-net
     pr = np.minimum(1.0, 6.0 * np.outer(w, w) / w.mean())
     up = np.triu(rng.rand(n, n) < pr, 1)
@@ -219,6 +215,16 @@ def test_krylov_fallback_above_the_direct_limit(cheb, monkeypatch):
     a.sort_indices()
     deg = np.diff(a.indptr)
     assert (deg >= 2).all() or np.bincount(a.indices[a.indptr[:-1][deg == 1]]).max() < 2
+    return a
+
+
+@pytest.mark.parametrize("cheb", ["0", "1"])
+def test_krylov_fallback_above_the_direct_limit(cheb, monkeypatch):
+    """Deflated size > 704 (no twin leaves at all).  cheb=0: thick-restart Krylov-Schur (single vector, ARPACK-like
+    invariants); cheb=1: the sparse block class is tried first and hands this (dense) graph on."""
+    monkeypatch.setenv("GCC_POSEMB_CHEB", cheb)
+    n = 760
+    a = skewed_dense_graph(n)
     view = dict(node_off=torch.tensor([0, n]), row_ptr=torch.from_numpy(a.indptr.astype(np.int64)),
                 col_idx=torch.from_numpy(a.indices.astype(np.int64)))
     x, evals, raw = _run(view)
@@ -464,3 +470,78 @@ def test_dense_ego_nets_without_anything_to_deflate():
     for view in dense_views():
         x, evals, raw = _run(view)
         _check(view, x, evals, raw)
+
+
+def test_workspace_sizes_are_the_recorded_ones(monkeypatch):
+    """Callers cache gcc_posemb_multi_workspace_bytes: the sizes recorded before the workspace got its one layout
+    (tests/golden/make_posemb_workspace_golden.py, default grid caps) are the sizes it returns."""
+    import json
+    import os
+
+    monkeypatch.delenv("GCC_POSEMB_GRID_CAPS", raising=False)
+    monkeypatch.delenv("GCC_POSEMB_GATED_CAPS", raising=False)
+    rows = json.load(open(os.path.join(os.path.dirname(__file__), "golden", "posemb_workspace_bytes.json")))
+    assert [(r["views"], r["batch_size"], r["node_cap"]) for r in rows] == [
+        (1, 6, 6 * 257), (1, 8, 8 * 1025), (3, 4, 4 * 257), (16, 256, 256 * 257)]
+    lib = emu_lib()
+    for r in rows:
+        assert lib.gcc_posemb_multi_workspace_bytes(r["views"], r["batch_size"], r["node_cap"], HID) == r["bytes"], r
+
+
+GUARD = 4096
+
+
+def guarded_workspace(pe, device):
+    """Puts ``pe``'s workspace into a 256-byte-aligned slice of exactly the advertised size inside a buffer filled with
+    0xA5, at least GUARD bytes of it on either side -> a function that asserts both bands are still intact."""
+    buf = torch.full((pe.nbytes + 2 * GUARD + 256,), 0xA5, dtype=torch.uint8, device=device)
+    off = GUARD + (-(buf.data_ptr() + GUARD)) % 256
+    pe.workspace = buf[off:off + pe.nbytes]
+    assert pe.workspace.data_ptr() % 256 == 0 and pe.workspace.numel() == pe.nbytes
+
+    def intact():
+        assert bool((buf[:off] == 0xA5).all()), "write in front of the workspace"
+        assert bool((buf[off + pe.nbytes:] == 0xA5).all()), "write past the advertised workspace size"
+    return intact
+
+
+def big_and_krylov_view():
+    """Two dense graphs without twin leaves: deflated size 400 (with GCC_POSEMB_CHEB=0 the 385..704 class) and 760 (Krylov)."""
+    import scipy.sparse as sp
+
+    a = sp.block_diag([skewed_dense_graph(400, seed=2), skewed_dense_graph(760)], format="csr")
+    a.sort_indices()
+    view = dict(node_off=torch.tensor([0, 400, 1160]), row_ptr=torch.from_numpy(a.indptr.astype(np.int64)),
+                col_idx=torch.from_numpy(a.indices.astype(np.int64)))
+    red = reduced_sizes(view)
+    assert SLOT_MAX < red[0] <= DIRECT_MAX < red[1], red
+    return view
+
+
+@pytest.mark.parametrize("case,cheb", [("stalky", "1"), ("stalky", "0"), ("big+krylov", "0")])
+def test_writes_stay_inside_the_advertised_workspace(case, cheb, monkeypatch):
+    """Every solver class carves its slots, tables and buffers out of the one workspace layout: a call touches nothing
+    outside the size gcc_posemb_multi_workspace_bytes advertised.  stalky_view() reaches the one-wave teams, the four-wave
+    65..128 class, the block class and (cheb=0) the 129..384 slot class; the third case the 385..704 class and Krylov
+    (the emulator's slowest kind of item: its restarts on 760 nodes are most of this case's ~14 s)."""
+    monkeypatch.setenv("GCC_POSEMB_CHEB", cheb)
+    view = stalky_view()[0] if case == "stalky" else big_and_krylov_view()
+    sizes = np.diff(view["node_off"].numpy())
+    b = CpuBatch(dict(view, pos_undirected=torch.zeros(int(view["node_off"][-1]), HID)),
+                 node_cap=len(sizes) * (int(sizes.max()) + 1))      # the Krylov class sizes its vectors as node_cap / batch_size
+    pe = DevicePosEmb(b.batch_size, b.parent_nid.numel(), HID, device="cpu", lib=emu_lib(),
+                      ptr=lambda t: 0 if t is None else t.data_ptr())
+    intact = guarded_workspace(pe, "cpu")
+    evals = torch.zeros(b.batch_size, HID)
+    raw = torch.zeros(b.parent_nid.numel(), HID)
+    pe(b, evals=evals, raw=raw)
+    intact()
+    assert int(pe.status[0]) == 0
+    n = int(view["node_off"][-1])
+    x = b.pos_undirected[:n].numpy()
+    if case == "stalky":
+        assert int(pe.status[2]) == 0
+        _check(view, x, evals.numpy(), raw[:n].numpy())
+    else:
+        assert int(pe.status[2]) > 0                                           # Arnoldi steps: the Krylov class ran
+        check_by_path(view, x, evals.numpy(), raw[:n].numpy())

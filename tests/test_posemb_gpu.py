@@ -204,3 +204,31 @@ def test_ego_nets_that_were_flagged_on_the_device_only(name, item):
             continue
         _check(view, q.pos_undirected[:n].cpu().numpy(), evals.cpu().numpy(), raw.cpu().numpy())
     assert not bad, "status words of the flagged runs: " + "; ".join(f"seed {s}: {st}" for s, st in bad)
+
+
+@pytest.mark.parametrize("cheb", ["1", "0"])
+def test_writes_stay_inside_the_advertised_workspace_on_device(cheb, monkeypatch):
+    """The guard-band check of the emulator tier on the device: the workspace is a 256-byte-aligned slice of exactly the
+    advertised size with 0xA5 bands around it; stalky_view() reaches the one-wave teams, the four-wave 65..128 class, the
+    block class and (cheb=0) the 129..384 slot class.  Bands intact, status 0, STRICT invariants."""
+    from gcc_amd.posemb import DevicePosEmb
+    from gcc_amd.sampler import BatchedCSR
+    from tests.test_posemb_emu import _check, guarded_workspace, stalky_view
+
+    monkeypatch.setenv("GCC_POSEMB_CHEB", cheb)
+    view, _, _ = stalky_view()
+    no, rp, ci = (view[k].numpy() for k in ("node_off", "row_ptr", "col_idx"))
+    B, n = len(no) - 1, int(no[-1])
+    q = BatchedCSR(B, torch.from_numpy(no.astype(np.int32)).cuda(), torch.from_numpy(rp[no].astype(np.int32)).cuda(),
+                   torch.zeros(n, dtype=torch.int32, device="cuda"),
+                   torch.from_numpy(np.repeat(np.arange(B), np.diff(no)).astype(np.int32)).cuda(),
+                   torch.from_numpy(rp.astype(np.int32)).cuda(), torch.from_numpy(ci.astype(np.int32)).cuda())
+    pe = DevicePosEmb(B, n, HID, device="cuda", seed=7)
+    intact = guarded_workspace(pe, "cuda")
+    evals = torch.zeros(B, HID, device="cuda")
+    raw = torch.zeros(n, HID, device="cuda")
+    pe(q, evals=evals, raw=raw)
+    torch.cuda.synchronize()
+    intact()
+    assert int(pe.status[0].item()) == 0 and int(pe.status[2].item()) == 0
+    _check(view, q.pos_undirected[:n].cpu().numpy(), evals.cpu().numpy(), raw[:n].cpu().numpy())
