@@ -151,6 +151,53 @@ def test_subgraphs_over_128_nodes_run_block_by_block(sizes, deg, L, pack):
             assert np.array_equal(rows[lo:hi], plain_rows[lo:hi]) and np.array_equal(pooled[b], plain_pooled[b])
 
 
+@pytest.mark.parametrize("pack", [False, True])
+def test_big_subgraphs_layer_by_layer_equal_one_call(pack):
+    """three one-layer calls, each fed the rows of the one before, against one three-layer call: 129 nodes = one full row
+    block + one row, 257 = two full + one row, a small subgraph in between; every layer count takes another ping-pong
+    buffer / x_out choice.  Same stages, same rounding points: rows and pooled sums (the input pooling included) bit for bit."""
+    rng = np.random.default_rng(23)
+    layers = bits_layers(random_layers(rng, 3))
+    node_off, row_ptr, col_idx = random_batch(rng, [129, 40, 257], 5)
+    x = ow.to_bf16_bits(rng.standard_normal((int(node_off[-1]), D)).astype(np.float32))
+    rows, pooled, status = emu_ginw_forward(node_off, row_ptr, col_idx, x, layers, pack=pack, scratch=True)
+    assert status == 0
+    step = x
+    for i in range(3):
+        step, p, status = emu_ginw_forward(node_off, row_ptr, col_idx, step, layers[i:i + 1], pack=pack, scratch=True)
+        assert status == 0
+        if i == 0:
+            assert np.array_equal(p[:, 0], pooled[:, 0])
+        assert np.array_equal(p[:, 1], pooled[:, i + 1]), i
+    assert np.array_equal(step, rows)
+
+
+def bad_edge_in_the_lone_row(rng):
+    """[20, 130] nodes, 4 in-neighbours: the first in-neighbour of local row 129 of the second subgraph (the lone row of
+    its second row block) becomes node 3 of the first subgraph.  Returns the CSR with that edge and with it removed."""
+    node_off, row_ptr, col_idx = random_batch(rng, [20, 130], 4)
+    e = int(row_ptr[20 + 129])
+    bad = col_idx.copy()
+    bad[e] = 3
+    cut_ptr = row_ptr.copy()
+    cut_ptr[20 + 129 + 1:] -= 1
+    return node_off, (row_ptr, bad), (cut_ptr, np.delete(col_idx, e))
+
+
+def test_bad_edge_inside_a_big_subgraph_is_flagged_once_and_skipped():
+    """the row block sees the edge in both of its column blocks: flagged in the first only (status is the bad-edge bit and
+    nothing else), skipped in both -- results are those of the CSR without the edge, bit for bit"""
+    rng = np.random.default_rng(29)
+    layers = bits_layers(random_layers(rng, 2))
+    node_off, (bad_ptr, bad_col), (cut_ptr, cut_col) = bad_edge_in_the_lone_row(rng)
+    x = ow.to_bf16_bits(rng.standard_normal((int(node_off[-1]), D)).astype(np.float32))
+    rows, pooled, status = emu_ginw_forward(node_off, bad_ptr, bad_col, x, layers, scratch=True)
+    assert status == 64
+    want_rows, want_pooled, want_status = emu_ginw_forward(node_off, cut_ptr, cut_col, x, layers, scratch=True)
+    assert want_status == 0
+    assert np.array_equal(rows, want_rows) and np.array_equal(pooled, want_pooled)
+
+
 def test_input_pooling_and_refusals():
     rng = np.random.default_rng(7)
     layers = random_layers(rng, 1)

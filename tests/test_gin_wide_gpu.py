@@ -4,7 +4,7 @@ import pytest
 import torch
 
 from oracle import gin_wide as ow
-from tests.test_gin_wide_emu import D, random_batch, random_layers, rel_err
+from tests.test_gin_wide_emu import D, bad_edge_in_the_lone_row, random_batch, random_layers, rel_err
 
 pytestmark = pytest.mark.gpu
 
@@ -149,3 +149,65 @@ def test_subgraphs_of_129_to_1024_nodes_run_block_by_block():
         if 0 < n <= 128:
             lo, hi = node_off[b], node_off[b + 1]
             assert np.array_equal(r0[lo:hi], got[lo:hi]) and np.array_equal(pooled0[b].cpu().numpy(), pooled[b])
+
+
+def _net(layers, pack=True):
+    from gcc_amd.gin_wide import FoldedWideGIN
+
+    net = FoldedWideGIN([{k: torch.from_numpy(v) for k, v in ly.items()} for ly in layers], torch.device("cuda:0"))
+    if not pack:                                         # row-major weights only: the kernels' other instantiation
+        for d in net.layers:
+            del d["w0_frag"], d["w1_frag"]
+    return net
+
+
+@pytest.mark.parametrize("pack", [False, True])
+def test_big_subgraphs_layer_by_layer_equal_one_call(pack):
+    """three one-layer calls, each fed the rows of the one before, against one three-layer call: 129 nodes = one full row
+    block + one row, 257 = two full + one row, a small subgraph in between; every layer count takes another ping-pong
+    buffer / x_out choice.  Rows bit for bit.  Pooled sums bit for bit where at most two row blocks add up (fp32 addition
+    commutes); the 257-node subgraph's three add in arrival order, so both ways are held to the oracle at 2e-3."""
+    sizes = [129, 40, 257]
+    rng = np.random.default_rng(23)
+    layers = random_layers(rng, 3)
+    node_off, row_ptr, col_idx = random_batch(rng, sizes, 5)
+    x = ow.bf16_round(rng.standard_normal((int(node_off[-1]), D)).astype(np.float32))
+    net = _net(layers, pack)
+    t = lambda a: torch.from_numpy(a).to(net.device)
+    csr = (t(node_off), t(row_ptr), t(col_idx))
+    xd = t(x).to(torch.bfloat16)
+    rows, pooled = net.forward(*csr, xd)
+    step, parts = xd, []
+    for i in range(3):
+        step, p = net.forward(*csr, step, num_layers=1, first_layer=i)
+        parts.append(p if i == 0 else p[:, 1:])
+    torch.cuda.synchronize()
+    assert net.check_status() == 0
+    assert torch.equal(step, rows)
+    split = torch.cat(parts, dim=1).cpu().numpy()
+    pooled = pooled.cpu().numpy()
+    np.testing.assert_array_equal(split[:2], pooled[:2])
+    _, want_pooled = ow.gin_wide_forward(node_off, row_ptr, col_idx, x, layers, bf16=True)
+    errs = rel_err(pooled[2], want_pooled[2]), rel_err(split[2], want_pooled[2])
+    print("257 nodes, pooled vs bf16 oracle: one call %.2e, layer by layer %.2e" % errs)
+    assert max(errs) < 2e-3
+
+
+def test_bad_edge_inside_a_big_subgraph_is_flagged_once_and_skipped():
+    """the row block sees the edge in both of its column blocks: flagged in the first only (status is the bad-edge bit and
+    nothing else), skipped in both -- results are those of the CSR without the edge, bit for bit"""
+    rng = np.random.default_rng(29)
+    layers = random_layers(rng, 2)
+    node_off, bad, cut = bad_edge_in_the_lone_row(rng)
+    x = ow.bf16_round(rng.standard_normal((int(node_off[-1]), D)).astype(np.float32))
+    net = _net(layers)
+    t = lambda a: torch.from_numpy(a).to(net.device)
+    xd = t(x).to(torch.bfloat16)
+    rows, pooled = net.forward(t(node_off), t(bad[0]), t(bad[1]), xd)
+    torch.cuda.synchronize()
+    assert int(net.status[0].item()) == 64               # (check_status() raises on it)
+    net.status.zero_()
+    want_rows, want_pooled = net.forward(t(node_off), t(cut[0]), t(cut[1]), xd)
+    torch.cuda.synchronize()
+    assert net.check_status() == 0
+    assert torch.equal(rows, want_rows) and torch.equal(pooled, want_pooled)

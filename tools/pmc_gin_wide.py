@@ -1,6 +1,6 @@
 """Summarise `rocprofv3 --output-format csv --pmc SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_WAIT_INST_LDS
 SQ_ACTIVE_INST_ANY SQ_VALU_MFMA_BUSY_CYCLES SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE --kernel-trace -d DIR -o g --
-python tools/gin_roofline.py --iters 2 --warmup 1` for the fused 8-layer launch of gin_wide_kernel (the longest
+python tools/gin_roofline.py --iters 2 --warmup 1` for the fused 8-layer launch of gin_wide2_kernel (the longest
 dispatches) into a JSON with the derived shares (MI355X_MICROARCH.md, rocprofv3 PMC slots).
 
     python tools/pmc_gin_wide.py DIR out.json
@@ -33,7 +33,7 @@ def main():
     dur = sum(v["dur"] for v in fused) / len(fused) / 1e3
     wc = c.get("SQ_WAVE_CYCLES", 0.0) or 1.0
     src = open(os.path.join(ROOT, "gcc_amd", "csrc", "gin_wide.hip"), "rb").read()
-    rec = dict(kernel="gin_wide2_kernel (default shape), fused 8-layer launch (the longest dispatches of tools/gin_roofline.py)",
+    rec = dict(kernel="gin_wide2_kernel, fused 8-layer launch (the longest dispatches of tools/gin_roofline.py)",
                source_sha256=hashlib.sha256(src).hexdigest(), dispatches=len(fused), duration_us_under_profiler=dur, counters=c,
                derived=dict(parked_on_waitcnt_or_barrier=c.get("SQ_WAIT_ANY", 0) / wc, issue_stalled=c.get("SQ_WAIT_INST_ANY", 0) / wc,
                             issuing=c.get("SQ_ACTIVE_INST_ANY", 0) / wc,
