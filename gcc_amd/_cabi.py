@@ -172,6 +172,27 @@ class GccGinwArgs(ctypes.Structure):
     ]
 
 
+class GccGinwEmbedArgs(ctypes.Structure):     # gcc_ginw_embed_args: the eval-mode embedding of a wide GIN encoder (csrc/gin_wide.hip)
+    _fields_ = [
+        ("num_views", ctypes.c_int32), ("batch_size", ctypes.c_int32), ("num_layers", ctypes.c_int32),
+        ("pos_dim", ctypes.c_int32), ("deg_emb_dim", ctypes.c_int32), ("max_degree", ctypes.c_int32),
+        ("edge_multiplicity", ctypes.c_int32), ("hidden", ctypes.c_int32), ("out_dim", ctypes.c_int32),
+        ("normalize", ctypes.c_int32), ("norm_eps", ctypes.c_float),
+        ("node_cap", ctypes.c_int64),
+        ("node_off", _VP * 2), ("row_ptr", _VP * 2), ("col_idx", _VP * 2), ("seed_local", _VP * 2), ("pos", _VP * 2),
+        ("degree_embedding", _VP),
+        ("layers", GccGinwLayer * 8),
+        ("pred_w", _VP * (GIN_MAX_LAYERS + 1)), ("pred_b", _VP * (GIN_MAX_LAYERS + 1)),
+        ("pooled", _VP * 2), ("out", _VP),
+        ("workspace", _VP), ("workspace_bytes", ctypes.c_int64),
+    ]
+
+
+STATUS_GINW_TOO_LARGE = 32
+STATUS_GINW_BAD_EDGE = 64
+STATUS_GINW_COUNT_OVERFLOW = 128
+
+
 class GccClsHeadArgs(ctypes.Structure):      # gcc_cls_head_args: the fine-tuning head (csrc/cls_head.hip)
     _fields_ = [
         ("feat", _VP), ("W", _VP), ("b", _VP), ("labels", _VP),
@@ -320,6 +341,8 @@ SIGNATURES = {
     "gcc_queue_enqueue_scalars": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int32,
                                                    ctypes.c_void_p, ctypes.c_void_p]),
     "gcc_ginw_scratch_bytes": (ctypes.c_int64, [ctypes.c_int64, ctypes.c_int32]),
+    "gcc_ginw_embed_workspace_bytes": (ctypes.c_int64, [ctypes.c_int64, ctypes.c_int32]),
+    "gcc_ginw_embed": (ctypes.c_int32, [ctypes.POINTER(GccGinwEmbedArgs), ctypes.c_void_p, ctypes.c_void_p]),
     "gcc_gin_eval_debug_ticks": (None, [ctypes.c_void_p]),
     "gcc_gin_eval_fused": (ctypes.c_int32, [ctypes.POINTER(GccGinPass), ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p]),
     "gcc_step_scalars_fill": (None, [ctypes.c_void_p, ctypes.c_float, ctypes.c_float, ctypes.c_float, ctypes.c_int32,

@@ -26,7 +26,8 @@
 //
 // The stages of a layer are written once, as the inline functions below; two kernels call them: gin_wide2_kernel (a
 // subgraph of at most 128 nodes, all layers in one launch) and gin_wide_big_kernel (a 128-row block of a larger one,
-// one layer per launch).
+// one layer per launch).  gcc_ginw_embed puts them between a feature kernel and a readout kernel: the eval-mode embedding
+// of a wide GIN encoder (GraphEncoder.resident_eval), one call per batch.
 #include "host_common.h"
 
 #include <mutex>
@@ -58,6 +59,7 @@ struct WideArgs {
     uint16_t *big0, *big1;
     int32_t *big_work;
     int32_t big_cap;                 // pairs the work list holds
+    int32_t mult;                    // copies of every CSR entry in the graph the model saw (gcc_ginw_forward: 1; gcc_ginw_embed: edge_multiplicity)
 };
 
 long long *g_ticks = nullptr;
@@ -172,9 +174,12 @@ __device__ __forceinline__ void store_rows_transposed(const unsigned char *P, ui
 // consecutive edges per thread: one bisection of the row pointers per run, then the row advances with the edges (a
 // bisection per edge was 9.8 us per subgraph).  A neighbour outside the subgraph is skipped in every column block and
 // flagged in the first; one inside it but outside this column block belongs to another pass.  self_loop: + h_v itself
-// (the column block that holds the rows' own nodes).
+// (the column block that holds the rows' own nodes); it counts once, a CSR entry `mult` times (the edge multiplicity of the
+// multigraph the CSR stands for).  A counter is 16 bits wide: a row with 65,536 / mult or more copies of ONE neighbour is
+// outside the contract (it would carry into the next counter, or out of the word, unseen); what exceeds 256 below that
+// is caught by flag_count_overflow.
 __device__ __forceinline__ void count_neighbours(unsigned char *Q, const int32_t *rp, const int32_t *col_idx, int32_t *status, int n0,
-                                                 int n, int nrows, int cblk, bool self_loop, int tid)
+                                                 int n, int nrows, int cblk, bool self_loop, uint32_t mult, int tid)
 {
     const int e0 = rp[0], e1 = rp[nrows];
     for (int eb = e0 + 16 * tid; eb < e1; eb += 16 * kT) {
@@ -192,7 +197,7 @@ __device__ __forceinline__ void count_neighbours(unsigned char *Q, const int32_t
             while (rp[lo + 1] <= eb + j) ++lo;       // (empty rows are skipped)
             const int ug = cols[j] - n0, u = ug - cblk * kNodes;
             if ((unsigned)ug >= (unsigned)n) { if (cblk == 0) atomicOr(status, (int32_t)GCC_STATUS_GINW_BAD_EDGE); }
-            else if ((unsigned)u < (unsigned)kNodes) atomicAdd((uint32_t *)(Q + lo * kStrT + (u >> 1) * 4), (u & 1) ? 0x10000u : 1u);
+            else if ((unsigned)u < (unsigned)kNodes) atomicAdd((uint32_t *)(Q + lo * kStrT + (u >> 1) * 4), (u & 1) ? mult << 16 : mult);
         }
     }
     if (self_loop && tid < nrows) atomicAdd((uint32_t *)(Q + tid * kStrT + (tid >> 1) * 4), (tid & 1) ? 0x10000u : 1u);
@@ -203,6 +208,21 @@ __device__ __forceinline__ float input_channel_sum(const unsigned char *P, int t
 {
     for (int j = 0; j < kNodes / 8; ++j) s += sum8_bf16(lds16(P + tid * kStrT + j * 16));
     return s;
+}
+
+// A count above kMaxCount has no exact bf16 value: it is reported (GCC_STATUS_GINW_COUNT_OVERFLOW), never left to round.
+// A pass of its own over the finished counters (the padding bytes of a row are zeros), nine 16-byte reads per thread: in
+// adjacency_fragments the test cost the block kernel 31 more spilled registers.
+constexpr uint32_t kMaxCount = 256;          // integers up to 2^8 are exact in bf16 (8 significant bits)
+__device__ __forceinline__ void flag_count_overflow(const unsigned char *Q, int32_t *status, int tid)
+{
+    uint32_t over = 0;
+    for (int i = tid; i < kNodes * kStrT / 16; i += kT) {
+        const u32x4 c = lds16(Q + i * 16);
+#pragma unroll
+        for (int q = 0; q < 4; ++q) over |= (uint32_t)((c[q] & 0xFFFFu) > kMaxCount) | (uint32_t)((c[q] >> 16) > kMaxCount);
+    }
+    if (over) atomicOr(status, (int32_t)GCC_STATUS_GINW_COUNT_OVERFLOW);
 }
 
 // this wave's share of ADJ (its node half nh: 64 nodes x the block's 128 columns) as bf16 B fragments, from the counters in Q
@@ -427,9 +447,10 @@ __global__ __launch_bounds__(kT) void gin_wide2_kernel(WideArgs a)
         load_rows_transposed(P, a.x_in, n0, n, tid);
         __syncthreads();
         phase_tick(a.ticks, 0, tick);                        // rows in
-        count_neighbours(Q, rp, a.col_idx, a.status, n0, n, n, 0, true, tid);
+        count_neighbours(Q, rp, a.col_idx, a.status, n0, n, n, 0, true, (uint32_t)a.mult, tid);
         __syncthreads();
         phase_tick(a.ticks, 1, tick);                        // neighbour counts
+        flag_count_overflow(Q, a.status, tid);
         if (a.pooled) a.pooled[((int64_t)b * (L + 1)) * kD + tid] = input_channel_sum(P, tid, 0.f);
         u32x4 adj[4][4];                                     // kept in registers for every layer
         adjacency_fragments(adj, Q, nh, lr, lg);
@@ -536,8 +557,9 @@ __global__ __launch_bounds__(kT) void gin_wide_big_kernel(WideArgs a, int layer,
             if (tid <= nr) rp[tid] = a.row_ptr[row0 + tid];
             load_rows_transposed(P, hin, col0, nc, tid);     // H_c^T
             __syncthreads();
-            count_neighbours(Q, rp, a.col_idx, a.status, n0, n, nr, c, c == r, tid);
+            count_neighbours(Q, rp, a.col_idx, a.status, n0, n, nr, c, c == r, (uint32_t)a.mult, tid);
             __syncthreads();
+            if (layer == 0) flag_count_overflow(Q, a.status, tid);                               // (uniform; every layer sees the same counts)
             if (layer == 0 && r == 0 && a.pooled) pool0 = input_channel_sum(P, tid, pool0);      // (uniform)
             u32x4 adj[4][4];
             adjacency_fragments(adj, Q, nh, lr, lg);
@@ -576,6 +598,199 @@ WideScratchLayout wide_scratch_layout(int64_t num_nodes, int32_t batch_size)
     return l;
 }
 
+
+// =====================================================================================================================
+// The eval-mode embedding of a wide GIN encoder (gcc_ginw_embed): feature rows in, the layers above, the readout out.
+
+// The feature rows of one view (graph_encoder.py:152-165): positional embedding | degree embedding | seed flag, as bf16 rows
+// of kD channels; columns d_in.. are zero.  One subgraph per workgroup at a time, 8 channels (one 16-byte store) per work
+// item; degree and seed flag as ginx_feat_kernel has them.  Rows from node_off[B] on are neither read nor written.
+__global__ __launch_bounds__(kT) void ginw_feat_kernel(const int32_t *node_off, const int32_t *row_ptr, const int32_t *seed_local,
+                                                       const float *pos, const float *emb, int B, int pos_dim, int de, int max_degree,
+                                                       int mult, int node_cap, uint16_t *x)
+{
+    const int d_in = pos_dim + de + 1;
+    for (int b = blockIdx.x; b < B; b += gridDim.x) {
+        const int n0 = max(node_off[b], 0), n1 = min(node_off[b + 1], node_cap);
+        const int seed = node_off[b] + (seed_local ? seed_local[b] : 0);
+        for (int i = (int)threadIdx.x; i < (n1 - n0) * (kD / 8); i += kT) {
+            const int v = n0 + (i >> 5), c0 = (i & 31) * 8;
+            int d = (row_ptr[v + 1] - row_ptr[v]) * mult;
+            d = d < 0 ? 0 : (d > max_degree ? max_degree : d);
+            float val[8];
+#pragma unroll
+            for (int e = 0; e < 8; ++e) {
+                const int c = c0 + e;
+                if (c < pos_dim) val[e] = pos[(int64_t)v * pos_dim + c];
+                else if (c < pos_dim + de) val[e] = emb[(int64_t)d * de + (c - pos_dim)];
+                else val[e] = (c == d_in - 1 && v == seed) ? 1.f : 0.f;
+            }
+            u32x4 o;
+#pragma unroll
+            for (int q = 0; q < 4; ++q) o[q] = pack2_bf16(val[2 * q], val[2 * q + 1]);
+            *(u32x4 *)(x + (int64_t)v * kD + c0) = o;
+        }
+    }
+}
+
+// score[b] = sum_i (pred_w[i] pooled[b][i][:k_i] + pred_b[i]) per view (gin.py:226-230 in eval mode: dropout is the identity),
+// normalised (graph_encoder.py:196), then the mean of the views (generate.py:52).  A workgroup of 16 waves takes kRoGraphs
+// subgraphs, BOTH views at once, so that a prediction weight fetched from L2 feeds 2 x kRoGraphs accumulators.  A wave owns an
+// output channel at a time: its lanes stride over (i, k) -- a hidden layer's row of up to 256 weights is ONE 16-byte load
+// per lane when the rows are 16-byte aligned, so a channel's loads are all in flight together -- with one f32 accumulator
+// per (view, subgraph), summed over the wave in a fixed order.  (The first shape, 4 waves x 64 channels each with scalar
+// loads in a rolled loop, was a chain of ~2,000 L2 latencies per wave: 0.8 ms of a 1 ms call.)
+constexpr int kRoGraphs = 2, kRoT = 1024;
+struct ReadoutArgs {
+    const float *pooled[2];
+    const float *pred_w[GCC_GIN_MAX_LAYERS + 1], *pred_b[GCC_GIN_MAX_LAYERS + 1];
+    float *out;
+    int32_t B, L, d_in, hidden, out_dim, num_views, normalize;
+    float norm_eps;
+};
+__global__ __launch_bounds__(kRoT) void ginw_readout_kernel(ReadoutArgs a)
+{
+    __shared__ __attribute__((aligned(16))) float P[2][kRoGraphs][(GCC_GIN_MAX_LAYERS + 1) * kD];   // 36 KiB: the pooled sums of this group
+    __shared__ float S[2][kRoGraphs][kD];                                // scores per view
+    __shared__ float R[2][kRoGraphs];                                    // max(||score||, eps), or 1
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const int per = (a.L + 1) * kD;
+    // (uniform) rows of the hidden layers' weights as 16-byte pieces: the row length and every base address allow it
+    bool vec = (a.hidden & 3) == 0;
+    for (int i = 1; i <= a.L; ++i) vec = vec && (((uintptr_t)a.pred_w[i]) & 15u) == 0;
+    for (int g0 = (int)blockIdx.x * kRoGraphs; g0 < a.B; g0 += (int)gridDim.x * kRoGraphs) {
+        __syncthreads();                                                 // the previous group is done with P, S and R
+        for (int idx = tid; idx < 2 * kRoGraphs * per; idx += kRoT) {
+            const int vg = idx / per, r = idx - vg * per, view = vg / kRoGraphs, g = vg - view * kRoGraphs;
+            P[view][g][r] = (view < a.num_views && g0 + g < a.B) ? a.pooled[view][(int64_t)(g0 + g) * per + r] : 0.f;
+        }
+        __syncthreads();
+        for (int o = w; o < a.out_dim; o += kRoT / 64) {                 // (wave-uniform)
+            float acc[2][kRoGraphs], bias = 0.f;
+#pragma unroll
+            for (int v = 0; v < 2; ++v)
+#pragma unroll
+                for (int g = 0; g < kRoGraphs; ++g) acc[v][g] = 0.f;
+            for (int i = 0; i <= a.L; ++i) {
+                const int ki = i == 0 ? a.d_in : a.hidden;
+                const float *wrow = a.pred_w[i] + (int64_t)o * ki;
+                if (i > 0 && vec) {
+                    for (int k = 4 * lane; k < ki; k += 256) {
+                        const float4 wv = *(const float4 *)(wrow + k);
+#pragma unroll
+                        for (int v = 0; v < 2; ++v)
+#pragma unroll
+                            for (int g = 0; g < kRoGraphs; ++g) {
+                                const float4 pv = *(const float4 *)&P[v][g][i * kD + k];
+                                acc[v][g] = fmaf(wv.x, pv.x, fmaf(wv.y, pv.y, fmaf(wv.z, pv.z, fmaf(wv.w, pv.w, acc[v][g]))));
+                            }
+                    }
+                } else {
+#pragma unroll 4
+                    for (int k = lane; k < ki; k += 64) {
+                        const float wv = wrow[k];
+#pragma unroll
+                        for (int v = 0; v < 2; ++v)
+#pragma unroll
+                            for (int g = 0; g < kRoGraphs; ++g) acc[v][g] = fmaf(wv, P[v][g][i * kD + k], acc[v][g]);
+                    }
+                }
+                bias += a.pred_b[i][o];
+            }
+#pragma unroll
+            for (int v = 0; v < 2; ++v)
+#pragma unroll
+                for (int g = 0; g < kRoGraphs; ++g) {
+                    const float t = wave_sum(acc[v][g]);
+                    if (lane == 0) S[v][g][o] = t + bias;
+                }
+        }
+        __syncthreads();
+        for (int pr = w; pr < a.num_views * kRoGraphs; pr += kRoT / 64) {   // (wave-uniform) one wave per (view, subgraph)
+            const int view = pr / kRoGraphs, g = pr - view * kRoGraphs;
+            float ss = 0.f;
+            for (int o = lane; o < a.out_dim; o += 64) ss = fmaf(S[view][g][o], S[view][g][o], ss);
+            ss = wave_sum(ss);
+            if (lane == 0) R[view][g] = a.normalize ? fmaxf(sqrtf(ss), a.norm_eps) : 1.f;
+        }
+        __syncthreads();
+        for (int idx = tid; idx < kRoGraphs * a.out_dim; idx += kRoT) {
+            const int g = idx / a.out_dim, o = idx - g * a.out_dim;
+            if (g0 + g >= a.B) break;
+            float f = S[0][g][o] / R[0][g];
+            if (a.num_views == 2) f = (f + S[1][g][o] / R[1][g]) / 2;
+            a.out[(int64_t)(g0 + g) * a.out_dim + o] = f;
+        }
+    }
+}
+
+// the layers of one batch from x_in: the fused launch for subgraphs of at most kNodes nodes, then -- with scratch -- the
+// work list and one launch per layer for the larger ones (nothing to do, a few microseconds per launch, when there are none)
+void launch_layers(const WideArgs &a, bool frag, const uint16_t *x_in, uint16_t *x_out, hipStream_t s)
+{
+#ifndef GCC_AMD_HIPEMU
+    static std::once_flag lds_opt_in;                        // more than 64 KiB of dynamic LDS has to be opted into
+    std::call_once(lds_opt_in, [] {
+        for (const void *k : {(const void *)gin_wide2_kernel<false>, (const void *)gin_wide2_kernel<true>,
+                              (const void *)gin_wide_big_kernel<false>, (const void *)gin_wide_big_kernel<true>})
+            (void)hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, kLds);
+    });
+#endif
+    // one workgroup per CU (137 KB of LDS each), walking the subgraphs with a stride of the grid
+    const dim3 grid(min(a.batch_size, 256)), block(kT);
+    if (frag) hipLaunchKernelGGL((gin_wide2_kernel<true>), grid, block, kLds, s, a);
+    else hipLaunchKernelGGL((gin_wide2_kernel<false>), grid, block, kLds, s, a);
+    if (a.big_work) {
+        hipLaunchKernelGGL(ginw_classify_kernel, dim3(1), dim3(256), 0, s, a);
+        const uint16_t *hin = x_in;
+        for (int l = 0; l < a.num_layers; ++l) {
+            uint16_t *hout = (l == a.num_layers - 1 && x_out) ? x_out : ((l & 1) ? a.big1 : a.big0);
+            if (frag) hipLaunchKernelGGL((gin_wide_big_kernel<true>), dim3(256), dim3(kT), kLds, s, a, l, hin, hout);
+            else hipLaunchKernelGGL((gin_wide_big_kernel<false>), dim3(256), dim3(kT), kLds, s, a, l, hin, hout);
+            hin = hout;
+        }
+    }
+}
+
+// the layer parameters into a.layers; returns through `frag` whether every layer carries the fragment-major copies.
+// -1: a layer has a NULL parameter (its index in `bad`)
+int bind_layers(WideArgs &a, const gcc_ginw_layer *layers, int num_layers, bool &frag, int &bad)
+{
+    frag = true;
+    for (int i = 0; i < GCC_GIN_MAX_LAYERS; ++i) {
+        a.layers[i] = layers[i];
+        const gcc_ginw_layer &l = layers[i];
+        if (i < num_layers && (!l.w0 || !l.w1 || !l.s0 || !l.t0 || !l.s1 || !l.t1 || !l.s2 || !l.t2)) { bad = i; return -1; }
+        if (i < num_layers) frag = frag && l.w0_frag && l.w1_frag;
+    }
+    return 0;
+}
+
+void bind_scratch(WideArgs &a, void *scratch, const WideScratchLayout &sl)
+{
+    char *base = (char *)scratch;
+    a.big0 = (uint16_t *)(base + sl.rows[0]);
+    a.big1 = (uint16_t *)(base + sl.rows[1]);
+    a.big_work = (int32_t *)(base + sl.work);
+    a.big_cap = (int32_t)sl.cap;
+}
+
+// gcc_ginw_embed's workspace: the feature rows of the view in flight ([node_cap][256] bf16; the views run one after the
+// other on the stream and share it), then the scratch of the layers
+struct EmbedLayout {
+    int64_t x, scratch, total;
+    WideScratchLayout sl;
+};
+EmbedLayout embed_layout(int64_t node_cap, int32_t batch_size)
+{
+    EmbedLayout l;
+    l.x = 0;
+    l.scratch = node_cap * kD * 2;                           // (a multiple of 512: the scratch stays 16-byte aligned)
+    l.sl = wide_scratch_layout(node_cap, batch_size);
+    l.total = l.scratch + l.sl.total;
+    return l;
+}
+
 }  // namespace
 
 extern "C" void gcc_ginw_debug_ticks(long long *device_ticks64) { g_ticks = device_ticks64; }
@@ -605,6 +820,7 @@ extern "C" int32_t gcc_ginw_forward(const gcc_ginw_args *g, int32_t *status, gcc
     a.batch_size = g->batch_size; a.num_layers = g->num_layers;
     a.ticks = g_ticks;
     a.big0 = a.big1 = nullptr; a.big_work = nullptr; a.big_cap = 0;
+    a.mult = 1;
     if (g->scratch) {
         const WideScratchLayout sl = wide_scratch_layout(g->num_nodes, g->batch_size);
         if (g->num_nodes < 1 || g->scratch_bytes < sl.total || ((uintptr_t)g->scratch & 15u)) {
@@ -612,48 +828,17 @@ extern "C" int32_t gcc_ginw_forward(const gcc_ginw_args *g, int32_t *status, gcc
                      (long long)sl.total, (long long)g->num_nodes);
             return -3;
         }
-        char *base = (char *)g->scratch;
-        a.big0 = (uint16_t *)(base + sl.rows[0]);
-        a.big1 = (uint16_t *)(base + sl.rows[1]);
-        a.big_work = (int32_t *)(base + sl.work);
-        a.big_cap = (int32_t)sl.cap;
+        bind_scratch(a, g->scratch, sl);
     }
-    bool frag = true;                                        // every layer carries the fragment-major copies?
-    for (int i = 0; i < GCC_GIN_MAX_LAYERS; ++i) {
-        a.layers[i] = g->layers[i];
-        const gcc_ginw_layer &l = g->layers[i];
-        if (i < g->num_layers && (!l.w0 || !l.w1 || !l.s0 || !l.t0 || !l.s1 || !l.t1 || !l.s2 || !l.t2)) {
-            snprintf(g_err, kErrLen, "gcc_ginw_forward: layer %d has a NULL parameter", i);
-            return -1;
-        }
-        if (i < g->num_layers) frag = frag && l.w0_frag && l.w1_frag;
+    bool frag;
+    int bad = 0;
+    if (bind_layers(a, g->layers, g->num_layers, frag, bad) != 0) {
+        snprintf(g_err, kErrLen, "gcc_ginw_forward: layer %d has a NULL parameter", bad);
+        return -1;
     }
     hipStream_t s = (hipStream_t)stream;
-#ifndef GCC_AMD_HIPEMU
-    static std::once_flag lds_opt_in;                        // more than 64 KiB of dynamic LDS has to be opted into
-    std::call_once(lds_opt_in, [] {
-        for (const void *k : {(const void *)gin_wide2_kernel<false>, (const void *)gin_wide2_kernel<true>,
-                              (const void *)gin_wide_big_kernel<false>, (const void *)gin_wide_big_kernel<true>})
-            (void)hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, kLds);
-    });
-#endif
     prof_mark(prof, 0, s);
-    // one workgroup per CU (137 KB of LDS each), walking the subgraphs with a stride of the grid
-    const dim3 grid(min(g->batch_size, 256)), block(kT);
-    if (frag) hipLaunchKernelGGL((gin_wide2_kernel<true>), grid, block, kLds, s, a);
-    else hipLaunchKernelGGL((gin_wide2_kernel<false>), grid, block, kLds, s, a);
-    if (a.big_work) {
-        // subgraphs over 128 nodes: (subgraph, row block) work list, then one launch per layer (the fused launch above left
-        // them alone; nothing to do -- a few microseconds per launch -- when the batch has none)
-        hipLaunchKernelGGL(ginw_classify_kernel, dim3(1), dim3(256), 0, s, a);
-        const uint16_t *hin = g->x_in;
-        for (int l = 0; l < g->num_layers; ++l) {
-            uint16_t *hout = (l == g->num_layers - 1 && g->x_out) ? g->x_out : ((l & 1) ? a.big1 : a.big0);
-            if (frag) hipLaunchKernelGGL((gin_wide_big_kernel<true>), dim3(256), dim3(kT), kLds, s, a, l, hin, hout);
-            else hipLaunchKernelGGL((gin_wide_big_kernel<false>), dim3(256), dim3(kT), kLds, s, a, l, hin, hout);
-            hin = hout;
-        }
-    }
+    launch_layers(a, frag, g->x_in, g->x_out, s);
     prof_mark(prof, 1, s);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) { snprintf(g_err, kErrLen, "gcc_ginw_forward: %s", hipGetErrorString(e)); return -10; }
@@ -664,4 +849,78 @@ extern "C" int64_t gcc_ginw_scratch_bytes(int64_t num_nodes, int32_t batch_size)
 {
     if (num_nodes < 1 || batch_size < 1) return -1;
     return wide_scratch_layout(num_nodes, batch_size).total;
+}
+
+extern "C" int64_t gcc_ginw_embed_workspace_bytes(int64_t node_cap, int32_t batch_size)
+{
+    if (node_cap < 1 || node_cap > INT32_MAX || batch_size < 1) {
+        snprintf(g_err, kErrLen, "gcc_ginw_embed_workspace_bytes: bad argument");
+        return -1;
+    }
+    return embed_layout(node_cap, batch_size).total;
+}
+
+extern "C" int32_t gcc_ginw_embed(const gcc_ginw_embed_args *e, int32_t *status, void *stream)
+{
+    if (!e || !status || e->num_views < 1 || e->num_views > 2 || e->batch_size < 1 || e->num_layers < 1 ||
+        e->num_layers > GCC_GIN_MAX_LAYERS || e->pos_dim < 0 || e->deg_emb_dim < 0 || e->max_degree < 0 || e->edge_multiplicity < 1 ||
+        e->node_cap < 1 || e->node_cap > INT32_MAX || !e->out || (e->deg_emb_dim > 0 && !e->degree_embedding)) {
+        snprintf(g_err, kErrLen, "gcc_ginw_embed: bad argument");
+        return -1;
+    }
+    const int d_in = e->pos_dim + e->deg_emb_dim + 1;
+    if (d_in > kD || e->hidden < 1 || e->hidden > kD || e->out_dim < 1 || e->out_dim > kD) {
+        snprintf(g_err, kErrLen, "gcc_ginw_embed: input / hidden / output widths of 1..%d are served (got %d / %d / %d)", kD, d_in,
+                 e->hidden, e->out_dim);
+        return -1;
+    }
+    for (int v = 0; v < e->num_views; ++v)
+        if (!e->node_off[v] || !e->row_ptr[v] || !e->col_idx[v] || !e->pooled[v] || (e->pos_dim > 0 && !e->pos[v])) {
+            snprintf(g_err, kErrLen, "gcc_ginw_embed: view %d has a NULL member", v);
+            return -1;
+        }
+    for (int i = 0; i <= e->num_layers; ++i)
+        if (!e->pred_w[i] || !e->pred_b[i]) {
+            snprintf(g_err, kErrLen, "gcc_ginw_embed: prediction layer %d has a NULL parameter", i);
+            return -1;
+        }
+    const EmbedLayout el = embed_layout(e->node_cap, e->batch_size);
+    if (!e->workspace || e->workspace_bytes < el.total || ((uintptr_t)e->workspace & 15u)) {
+        snprintf(g_err, kErrLen, "gcc_ginw_embed: workspace of %lld bytes (16-byte aligned) needed for %lld rows", (long long)el.total,
+                 (long long)e->node_cap);
+        return -3;
+    }
+    WideArgs a;
+    bool frag;
+    int bad = 0;
+    if (bind_layers(a, e->layers, e->num_layers, frag, bad) != 0) {
+        snprintf(g_err, kErrLen, "gcc_ginw_embed: layer %d has a NULL parameter", bad);
+        return -1;
+    }
+    uint16_t *x = (uint16_t *)((char *)e->workspace + el.x);
+    a.x_in = x; a.x_out = nullptr; a.status = status;
+    a.batch_size = e->batch_size; a.num_layers = e->num_layers;
+    a.ticks = g_ticks;
+    a.mult = e->edge_multiplicity;
+    bind_scratch(a, (char *)e->workspace + el.scratch, el.sl);
+    hipStream_t s = (hipStream_t)stream;
+    ReadoutArgs r;
+    for (int v = 0; v < e->num_views; ++v) {
+        hipLaunchKernelGGL(ginw_feat_kernel, dim3(min(e->batch_size, 1024)), dim3(kT), 0, s, e->node_off[v], e->row_ptr[v], e->seed_local[v],
+                           e->pos[v], e->degree_embedding, (int)e->batch_size, (int)e->pos_dim, (int)e->deg_emb_dim, (int)e->max_degree,
+                           (int)e->edge_multiplicity, (int)e->node_cap, x);
+        a.node_off = e->node_off[v]; a.row_ptr = e->row_ptr[v]; a.col_idx = e->col_idx[v];
+        a.pooled = e->pooled[v];
+        launch_layers(a, frag, x, nullptr, s);
+        r.pooled[v] = e->pooled[v];
+    }
+    if (e->num_views == 1) r.pooled[1] = nullptr;
+    for (int i = 0; i <= GCC_GIN_MAX_LAYERS; ++i) { r.pred_w[i] = e->pred_w[i]; r.pred_b[i] = e->pred_b[i]; }
+    r.out = e->out;
+    r.B = e->batch_size; r.L = e->num_layers; r.d_in = d_in; r.hidden = e->hidden; r.out_dim = e->out_dim;
+    r.num_views = e->num_views; r.normalize = e->normalize; r.norm_eps = e->norm_eps;
+    hipLaunchKernelGGL(ginw_readout_kernel, dim3(min((e->batch_size + kRoGraphs - 1) / kRoGraphs, 1024)), dim3(kRoT), 0, s, r);
+    hipError_t err = hipGetLastError();
+    if (err != hipSuccess) { snprintf(g_err, kErrLen, "gcc_ginw_embed: %s", hipGetErrorString(err)); return -10; }
+    return 0;
 }

@@ -417,8 +417,10 @@ class GraphEncoder(nn.Module):
         self.hidden, self.output_dim = int(node_hidden_dim), int(output_dim)
         self._pad_ptrs = {}          # name -> data_ptr of the tensor's padded home (ensure_padded)
         self.fused_eval = True       # eval-mode forward as one launch (gcc_gin_eval_fused); False: the 15-launch chain
+        self.resident_eval = False   # wide models: embed_views as ONE gcc_ginw_embed call (bf16, LDS-resident; gcc_amd/gin_wide.py)
         self._engine = None
         self._wide_engine = None
+        self._resident_engine = None
         self._slot = id(self)
         self._calls = 0
 
@@ -456,8 +458,10 @@ class GraphEncoder(nn.Module):
         self.num_heads, self.num_step_set2set = int(num_heads), int(num_step_set2set)
         self._pad_ptrs = {}
         self.fused_eval = False      # generate.py: model(q), model(k) and their mean (embed_views)
+        self.resident_eval = False   # (a wide-GIN path: embed_views refuses it for this backbone)
         self._engine = None
         self._wide_engine = None
+        self._resident_engine = None
         self._slot = id(self)
         self._calls = 0
 
@@ -554,6 +558,13 @@ class GraphEncoder(nn.Module):
             self._wide_engine = WideGinEngine()
         return self._wide_engine
 
+    def resident_engine(self):
+        if self._resident_engine is None:
+            from .gin_wide import WideResidentEngine
+
+            self._resident_engine = WideResidentEngine()
+        return self._resident_engine
+
     def needs_backward(self, params) -> bool:
         """An API-path forward can be backpropagated: grad enabled, some parameter requires it, batch statistics."""
         return torch.is_grad_enabled() and self.bn_training() and any(p.requires_grad for p in params)
@@ -576,7 +587,15 @@ class GraphEncoder(nn.Module):
 
     def embed_views(self, graph_q, graph_k):
         """generate.py:45-52 in one launch: ``(model(graph_q) + model(graph_k)) / 2`` in eval mode (both views' subgraphs
-        as workgroups of the same gcc_gin_eval_fused call, the mean taken on the device).  -> [B, output_dim]"""
+        as workgroups of the same gcc_gin_eval_fused call, the mean taken on the device).  -> [B, output_dim]
+        Wide models run two passes of the one-launch-per-operator chain and a torch mean -- or, with ``resident_eval``, one
+        gcc_ginw_embed call on the LDS-resident bf16 layers (its rounding rule: DESIGN.md section 7b; the status word is read
+        by ``resident_engine().check_status()``)."""
+        if self.resident_eval:
+            from .gin_wide import WideResidentEngine
+
+            WideResidentEngine.refuse(self)                                        # (before anything is built or loaded)
+            return self.resident_engine().embed(self, [graph_q] if graph_k is graph_q else [graph_q, graph_k])
         if self.bn_training():
             raise RuntimeError("embed_views is the eval-mode path (generate.py:38 calls model.eval())")
         if self.wide or self.gnn_model == "gat":                                   # two eval passes and their mean (generate.py:48-52 as written)

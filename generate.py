@@ -6,7 +6,9 @@ node of a graph as (f(q) + f(k)) / 2 over its two RWR views with the eval-mode e
 everything runs on the GPU (sampler, positional embedding, encoder).
 
 Extra flags (not in the reference): --edgelist / --nodelabel / --graph-npz / --graphs-npz / --tudataset / --edge-multiplicity /
---batch-size.  Graph-classification datasets (entire_graph=True, generate.py:75-82) come as ``--graphs-npz``: node_off
+--batch-size / --wide-eval.  ``--wide-eval resident`` embeds with a wide GIN checkpoint (--hidden-size above 64, f32- or
+bf16-trained) through one gcc_ginw_embed call per batch: bf16 layers resident in LDS, f32 readout (DESIGN.md section 7b has
+the rounding rule the flag opts into); the default, ``chain``, is the any-width eval chain.  Graph-classification datasets (entire_graph=True, generate.py:75-82) come as ``--graphs-npz``: node_off
 [G+1], row_ptr [N+1] (per-graph offsets restarting at 0 are rebuilt from node_off), col_idx (local ids)."""
 import argparse
 import os
@@ -15,12 +17,38 @@ import numpy as np
 import torch
 
 
-def main(args_test):
+class DevicePipeline:
+    """Where the sampler, the positional embedding and the encoder run: the GPU.  The emulator tests pass main() an object
+    with the same four members (device, node_dataset, posemb, place) that builds them on the emulator library instead."""
+
+    def __init__(self, gpu):
+        assert torch.cuda.is_available(), "the device pipeline needs a GPU"
+        self.gpu = 0 if gpu is None else gpu
+        print("Use GPU: {} for generation".format(self.gpu))
+        self.device = torch.device("cuda", self.gpu)
+        torch.cuda.set_device(self.device)
+
+    def node_dataset(self, **kw):
+        """-> (NodeClassificationDataset on the device sampler, its node capacity, its status check)"""
+        from gcc_amd.datasets import NodeClassificationDataset
+
+        ds = NodeClassificationDataset(device=self.device, **kw)
+        return ds, ds.sampler.node_cap, ds.sampler.check_status
+
+    def posemb(self, batch_size, node_cap, size, seed):
+        from gcc_amd.posemb import DevicePosEmb
+
+        return DevicePosEmb(batch_size, node_cap, size, device=self.device, seed=seed, max_views=2, num_buffers=2)
+
+    def place(self, model):
+        return model.to(self.device)
+
+
+def main(args_test, pipeline=None):
     from gcc_amd import ingest
-    from gcc_amd.datasets import GraphClassificationDataset, NodeClassificationDataset
+    from gcc_amd.datasets import GraphClassificationDataset
     from gcc_amd.encoder import encoder_from_opt
     from gcc_amd.generate import test_moco
-    from gcc_amd.posemb import DevicePosEmb
 
     if os.path.isfile(args_test.load_path):
         print("=> loading checkpoint '{}'".format(args_test.load_path))
@@ -29,11 +57,16 @@ def main(args_test):
     else:
         raise SystemExit("=> no checkpoint found at '{}'".format(args_test.load_path))
     args = checkpoint["opt"]
-    assert torch.cuda.is_available(), "the device pipeline needs a GPU"
-    args.gpu = 0 if args_test.gpu is None else args_test.gpu
-    print("Use GPU: {} for generation".format(args.gpu))
-    args.device = torch.device("cuda", args.gpu)
-    torch.cuda.set_device(args.device)
+    if pipeline is None:
+        pipeline = DevicePipeline(args_test.gpu)
+        args.gpu = pipeline.gpu
+    args.device = pipeline.device
+    model = encoder_from_opt(args)                                   # generate.py:102-118
+    if getattr(args_test, "wide_eval", "chain") == "resident":       # (refused before anything is read or built)
+        if getattr(model, "gnn_model", None) != "gin" or not model.wide:
+            raise SystemExit("--wide-eval resident serves wide GIN checkpoints (--model gin with --hidden-size above 64); this one is "
+                             "--model {} --hidden-size {}: drop the flag".format(args.model, args.hidden_size))
+        model.resident_eval = True
 
     graphs = None
     if args_test.tudataset:
@@ -61,22 +94,20 @@ def main(args_test):
             graphs=graphs, edge_multiplicity=mult, batch_size=args_test.batch_size, device=args.device)
         node_cap = train_dataset.node_cap
     else:
-        train_dataset = NodeClassificationDataset(                   # generate.py:84-91
+        train_dataset, node_cap, check_sampler = pipeline.node_dataset(      # generate.py:84-91
             dataset=args_test.dataset, rw_hops=args.rw_hops, subgraph_size=args.subgraph_size,
             restart_prob=args.restart_prob, positional_embedding_size=args.positional_embedding_size,
-            graph=graph, edge_multiplicity=mult, batch_size=args_test.batch_size, run_seed=getattr(args, "seed", 0),
-            device=args.device)
-        node_cap = train_dataset.sampler.node_cap
-    model = encoder_from_opt(args)                                   # generate.py:102-118
-    model = model.to(args.device)
+            graph=graph, edge_multiplicity=mult, batch_size=args_test.batch_size, run_seed=getattr(args, "seed", 0))
+    model = pipeline.place(model)
     model.load_state_dict(checkpoint["model"])
     del checkpoint
-    posemb = DevicePosEmb(args_test.batch_size, node_cap, args.positional_embedding_size,
-                          device=args.device, seed=getattr(args, "seed", 0), max_views=2, num_buffers=2)
+    posemb = pipeline.posemb(args_test.batch_size, node_cap, args.positional_embedding_size, getattr(args, "seed", 0))
     emb = test_moco(train_dataset, model, posemb, args)
     if graphs is None:
-        train_dataset.sampler.check_status()
+        check_sampler()
     posemb.check_status()
+    if model.resident_eval:
+        model.resident_engine().check_status()                       # (before anything is written)
     os.makedirs(args.model_folder, exist_ok=True)
     out = os.path.join(args.model_folder, args_test.dataset)
     np.save(out, emb.numpy())
@@ -97,6 +128,7 @@ if __name__ == "__main__":
     parser.add_argument("--tudataset", type=str, default=None, help="folder with the raw TU files <NAME>_A.txt, <NAME>_graph_indicator.txt, <NAME>_graph_labels.txt of --dataset (imdb-binary, imdb-multi, rdt-b, rdt-5k, collab)")
     parser.add_argument("--edge-multiplicity", type=int, default=0, help="copies of every edge in the reference's DGL graph (edge lists: detected; npz: default 2)")
     parser.add_argument("--batch-size", type=int, default=256)
+    parser.add_argument("--wide-eval", choices=["chain", "resident"], default="chain", help="wide GIN checkpoints: the any-width eval chain (f32 or the checkpoint's --encoder-dtype), or one LDS-resident bf16 call per batch (gcc_ginw_embed; f32 readout)")
     # fmt: on
     a = parser.parse_args()
     if a.graph_npz and not a.edge_multiplicity:

@@ -529,6 +529,44 @@ int32_t gcc_ginw_pack_weights(const uint16_t *w, uint16_t *w_frag, int32_t which
  * Linear, second Linear, rows out; [15] = subgraphs); NULL switches it off. */
 void gcc_ginw_debug_ticks(long long *device_ticks64);
 
+/* The eval-mode embedding of a wide GIN encoder in one call: generate.py:45-52, (f(graph_q) + f(graph_k)) / 2 (or f(graph_q)
+ * with one view), on the resident layers above.  Per view:
+ *     x      = bf16(positional embedding | degree embedding | seed flag), zero-padded to 256 columns (graph_encoder.py:152-165;
+ *              in-degree = row length * edge_multiplicity, clamped to max_degree; seed = seed_local[b] or node 0)
+ *     pooled = the SumPooling of x and of every layer's output, as gcc_ginw_forward computes them on the multigraph in which
+ *              every CSR entry stands for edge_multiplicity edges (the self loop of GINConv counts once)
+ *     score  = sum_i (pred_w[i] pooled[., i, :k_i] + pred_b[i]) in f32, k_0 = pos_dim + deg_emb_dim + 1, k_i = hidden;
+ *              with `normalize`, score / max(||score||_2, norm_eps)                      (gin.py:226-230 in eval mode, graph_encoder.py:196)
+ * The model's widths (input, hidden, output) are at most 256; `layers` holds the folded layer stack zero-padded to 256
+ * channels (a padded channel has scale 0 and shift 0 and stays exactly 0), layer 0's [hidden, k_0] weight in the top left
+ * corner of its [256, 256] block.  The rounding points are those of gcc_ginw_forward plus the rounding of x; the readout is f32.
+ * Row counts are read on the device (node_off[batch_size]); nothing is read back by the host.  A count of one neighbour
+ * (edge_multiplicity * copies in the CSR, + 1 on the diagonal) above 256 has no exact bf16 value: it is reported, never rounded --
+ * up to the width of the 16-bit counters: a count of 65,536 or more wraps unseen, such a CSR is outside the contract. */
+#define GCC_STATUS_GINW_COUNT_OVERFLOW 128   /* a neighbour occurs more than 256 times in one row: the results of its subgraph are wrong */
+typedef struct gcc_ginw_embed_args {
+    int32_t num_views;                   /* 1 or 2                                                               */
+    int32_t batch_size, num_layers;      /* subgraphs per view; 1 <= num_layers <= GCC_GIN_MAX_LAYERS            */
+    int32_t pos_dim, deg_emb_dim, max_degree, edge_multiplicity;
+    int32_t hidden, out_dim;             /* 1..256 each, as pos_dim + deg_emb_dim + 1                            */
+    int32_t normalize;
+    float norm_eps;
+    int64_t node_cap;                    /* rows the workspace is sized for: node_off[batch_size] <= node_cap    */
+    const int32_t *node_off[2], *row_ptr[2], *col_idx[2];   /* per view, as gcc_ginw_args                        */
+    const int32_t *seed_local[2];        /* device [B] or NULL (node 0 of every subgraph)                        */
+    const float *pos[2];                 /* device [>= N, pos_dim]                                               */
+    const float *degree_embedding;       /* device [max_degree + 1, deg_emb_dim]                                 */
+    gcc_ginw_layer layers[GCC_GIN_MAX_LAYERS];
+    const float *pred_w[GCC_GIN_MAX_LAYERS + 1], *pred_b[GCC_GIN_MAX_LAYERS + 1];   /* [out_dim, k_i], [out_dim] */
+    float *pooled[2];                    /* device [B, num_layers + 1, 256] per view (written, then read by the readout) */
+    float *out;                          /* device [B, out_dim]                                                  */
+    void *workspace;                     /* device, 16-byte aligned, gcc_ginw_embed_workspace_bytes(node_cap, batch_size) */
+    int64_t workspace_bytes;
+} gcc_ginw_embed_args;
+int64_t gcc_ginw_embed_workspace_bytes(int64_t node_cap, int32_t batch_size);
+/* status: device int32[1], OR of GCC_STATUS_GINW_* (zeroed by the caller). */
+int32_t gcc_ginw_embed(const gcc_ginw_embed_args *a, int32_t *status, void *stream);
+
 /* ------------------------------------------------------- MoCo / InfoNCE head ---
  * MemoryMoCo.forward (gcc/contrastive/memory_moco.py:26-63, use_softmax=True) fused
  * with NCESoftmaxLoss (gcc/contrastive/criterions.py:12-17), and the E2E variant
