@@ -72,6 +72,19 @@ class GccBatchOut(ctypes.Structure):
     ]
 
 
+class GccGraphCorpus(ctypes.Structure):      # gcc_graph_corpus: every graph of a whole-graph dataset (csrc/graph_batch.hip)
+    _fields_ = [
+        ("num_graphs", ctypes.c_int32), ("pos_dim", ctypes.c_int32),
+        ("node_first", ctypes.c_void_p), ("row_ptr", ctypes.c_void_p), ("col_idx", ctypes.c_void_p),
+        ("seed_local", ctypes.c_void_p), ("labels", ctypes.c_void_p), ("pos", ctypes.c_void_p),
+    ]
+
+
+PACK_GRAPHS_MAX_BATCH = 1024
+STATUS_PACK_NODE_OVERFLOW = 1                # gcc_pack_graphs' own status word
+STATUS_PACK_EDGE_OVERFLOW = 2
+STATUS_PACK_BAD_INDEX = 4
+
 GIN_MAX_LAYERS = 8
 GIN_HIDDEN = 64
 _VP = ctypes.c_void_p
@@ -364,6 +377,9 @@ SIGNATURES = {
     "gcc_adam_clipvalue_step": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                                  ctypes.c_int64, ctypes.c_float, ctypes.c_float, ctypes.c_float, ctypes.c_float,
                                                  ctypes.c_float, ctypes.c_int32, ctypes.c_float, ctypes.c_float, ctypes.c_void_p]),
+    "gcc_pack_graphs": (ctypes.c_int32, [ctypes.POINTER(GccGraphCorpus), ctypes.c_void_p, ctypes.c_int32,
+                                         ctypes.POINTER(GccBatchOut), ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                         ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p]),
 }
 # symbols declared in the header but not built yet are listed here while the build is in progress
 PENDING = set()

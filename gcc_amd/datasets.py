@@ -8,12 +8,152 @@ is padded with node 0 and reports ``valid`` rows.
 ``GraphClassificationDataset`` (:306-330): one item per GRAPH of a list of small graphs, ``entire_graph=True``: the
 "subgraph" is the whole graph in its own node order, the seed flag marks ``out_degrees().argmax()``
 (data_util.py:228-237) and both views are identical (the random walk's result is discarded), so batches are
-assembled without the sampler."""
+assembled without the sampler: on the device by gcc_pack_graphs from a resident corpus (``batcher="device"``, what
+``"auto"`` picks on a GPU), or by the host loop (``batcher="host"``, the yardstick the device batcher is tested against)."""
 from __future__ import annotations
+
+import ctypes
+import functools
 
 import numpy as np
 
 from .graph import max_nodes_out_degree_table
+
+
+def resolve_batcher(batcher, device):
+    """``"auto"`` -> ``"device"`` on a GPU and ``"host"`` otherwise; ``"device"`` off the GPU is refused by name"""
+    import torch
+
+    if batcher not in ("auto", "host", "device"):
+        raise ValueError(f'batcher must be "auto", "host" or "device" (got {batcher!r})')
+    on_gpu = torch.device(device).type == "cuda"
+    if batcher == "device" and not on_gpu:
+        raise ValueError(f'batcher="device" needs a GPU device (got {device!r}): gcc_pack_graphs has no CPU path, '
+                         'use batcher="host"')
+    return "device" if batcher == "device" or (batcher == "auto" and on_gpu) else "host"
+
+
+class DeviceGraphCorpus:
+    """Every graph of a whole-graph dataset, concatenated and resident on the device (gcc_graph_corpus), plus a ring of
+    ``num_buffers`` output buffer sets; :meth:`pack` issues one gcc_pack_graphs call into the next set.  A set is rewritten
+    ``num_buffers`` calls later, so a consumer that keeps ``k`` batches in flight needs ``k + 1`` sets (LabeledProducer:
+    ``depth + 2``).  ``lib`` / ``ptr`` are injectable for the emulator tests only."""
+
+    _BITS = ((1, "node capacity"), (2, "edge capacity"), (4, "graph index out of range"))
+
+    def __init__(self, graphs, batch_size, labels=None, pos_dim=0, expand=1, device="cuda", num_buffers=3, node_cap=None,
+                 edge_cap=None, placeholder=True, lib=None, ptr=None):
+        import torch
+
+        from . import _cabi
+
+        self.lib = lib if lib is not None else _cabi.load()
+        self.ptr = ptr if ptr is not None else _cabi.dev_ptr
+        self.device, self.batch_size, self.pos_dim, self.expand = device, int(batch_size), int(pos_dim), max(int(expand), 1)
+        if not 1 <= self.batch_size <= _cabi.PACK_GRAPHS_MAX_BATCH:
+            raise ValueError(f"the device batcher packs 1..{_cabi.PACK_GRAPHS_MAX_BATCH} graphs per batch "
+                             f"(GCC_PACK_GRAPHS_MAX_BATCH), got batch_size {self.batch_size}; use batcher=\"host\"")
+        if self.pos_dim and (self.pos_dim < 2 or self.pos_dim % 2):
+            raise ValueError(f"positional rows must have an even size of at least 2 (got {self.pos_dim})")
+        self.sizes = np.array([len(rp) - 1 for rp, _ in graphs], dtype=np.int64)
+        self.entries = np.array([len(ci) for _, ci in graphs], dtype=np.int64)       # live col_idx length of a batch: a host sum
+        self.first = np.concatenate([[0], np.cumsum(self.sizes)])
+        efirst = np.concatenate([[0], np.cumsum(self.entries)])
+        if self.first[-1] >= 2 ** 31 - 1 or efirst[-1] >= 2 ** 31 - 1:
+            raise ValueError("the corpus does not fit int32 offsets")
+        G = len(graphs)
+        row_ptr = np.zeros(int(self.first[-1]) + 1, dtype=np.int32)
+        seed_local = np.zeros(G, dtype=np.int32)
+        for g, (rp, _) in enumerate(graphs):
+            rp = np.asarray(rp, dtype=np.int64)
+            row_ptr[self.first[g] + 1: self.first[g + 1] + 1] = rp[1:] + efirst[g]
+            if len(rp) > 1:
+                seed_local[g] = int(np.argmax(np.diff(rp)))             # out_degrees().argmax(), first maximum (_convert_idx)
+        col_idx = (np.concatenate([np.asarray(ci, dtype=np.int32) for _, ci in graphs]) if G and efirst[-1]
+                   else np.zeros(1, dtype=np.int32))
+        up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(device)          # noqa: E731
+        self.node_first = up(self.first.astype(np.int32))
+        self.row_ptr, self.col_idx, self.seed_local = up(row_ptr), up(col_idx), up(seed_local)
+        self.labels = up(np.asarray(labels).astype(np.int32)) if labels is not None else None
+        self.pos = None
+        self.c = _cabi.GccGraphCorpus(num_graphs=G, pos_dim=self.pos_dim, node_first=self.ptr(self.node_first),
+                                      row_ptr=self.ptr(self.row_ptr), col_idx=self.ptr(self.col_idx),
+                                      seed_local=self.ptr(self.seed_local),
+                                      labels=self.ptr(self.labels) if self.labels is not None else None, pos=None)
+        B = self.batch_size
+        largest, most = int(self.sizes.max()) if G else 0, int(self.entries.max()) if G else 0
+        self.node_cap = int(node_cap) if node_cap is not None else B * (largest + 1)   # (the eigensolver's convention)
+        self.edge_cap = int(edge_cap) if edge_cap is not None else max(B * most * self.expand, 1)
+        i32 = dict(dtype=torch.int32, device=device)
+        self.status = torch.zeros(1, **i32)
+        self.parent_nid = torch.zeros(self.node_cap, **i32)              # never written: the zero buffer of the host batches
+        # col_idx of an edge-free batch: the host's one-element placeholder, repeated like every entry
+        self._placeholder = torch.zeros(self.expand, **i32) if placeholder else None
+        self._ring = []
+        for _ in range(max(int(num_buffers), 1)):
+            slot = dict(node_off=torch.zeros(B + 1, **i32), edge_off=torch.zeros(B + 1, **i32),
+                        graph_id=torch.zeros(self.node_cap, **i32), row_ptr=torch.zeros(self.node_cap + 1, **i32),
+                        col_idx=torch.zeros(self.edge_cap, **i32), seed_local=torch.zeros(B, **i32),
+                        labels=torch.full((B,), -1, **i32))
+            if self.pos_dim:
+                slot["pos"] = torch.zeros(self.node_cap, self.pos_dim, dtype=torch.float32, device=device)
+            self._ring.append(slot)
+        self._next = 0
+
+    def set_pos(self, pos):
+        """the table of every graph's positional rows [sum of nodes, pos_dim] (float32, on the device), once it exists"""
+        import torch
+
+        if pos is self.pos:
+            return
+        if pos.dtype != torch.float32 or tuple(pos.shape) != (int(self.first[-1]), self.pos_dim) or not pos.is_contiguous():
+            raise ValueError(f"the positional table must be contiguous float32 [{int(self.first[-1])}, {self.pos_dim}]")
+        self.pos = pos
+        self.c.pos = self.ptr(pos)
+
+    def index_tensor(self, idx):
+        """graph indices -> int32 device tensor padded with -1 to a multiple of the batch size (one upload)"""
+        import torch
+
+        idx = np.asarray(idx, dtype=np.int64)
+        B = self.batch_size
+        padded = np.full(max((len(idx) + B - 1) // B, 1) * B, -1, dtype=np.int32)
+        padded[: len(idx)] = idx
+        return torch.from_numpy(padded).to(self.device)
+
+    def pack(self, idx_dev, live_entries, expand=None, with_pos=True):
+        """One gcc_pack_graphs call: ``idx_dev`` int32 [batch_size] on the device (-1 = padding), ``live_entries`` the sum of
+        the selected graphs' entry counts (known on the host: ``entries[idx].sum()``).  -> (BatchedCSR, labels int32 [B])"""
+        from . import _cabi
+        from .sampler import BatchedCSR
+
+        B = self.batch_size
+        expand = self.expand if expand is None else int(expand)
+        assert idx_dev.numel() == B and 1 <= expand <= self.expand
+        slot = self._ring[self._next]
+        self._next = (self._next + 1) % len(self._ring)
+        e = int(live_entries) * expand
+        col = slot["col_idx"][:e] if e or self._placeholder is None else self._placeholder[:expand]
+        g = BatchedCSR(B, slot["node_off"], slot["edge_off"], self.parent_nid, slot["graph_id"], slot["row_ptr"], col)
+        out = _cabi.GccBatchOut(node_off=self.ptr(slot["node_off"]), edge_off=self.ptr(slot["edge_off"]),
+                                parent_nid=self.ptr(self.parent_nid), graph_id=self.ptr(slot["graph_id"]),
+                                row_ptr=self.ptr(slot["row_ptr"]), col_idx=self.ptr(slot["col_idx"]),
+                                node_cap=self.node_cap, edge_cap=self.edge_cap)
+        pos = slot["pos"] if with_pos and self.pos is not None else None
+        _cabi.call(self.lib, "gcc_pack_graphs", ctypes.byref(self.c), self.ptr(idx_dev), B, ctypes.byref(out),
+                   self.ptr(pos) if pos is not None else None, self.ptr(slot["seed_local"]), self.ptr(slot["labels"]), expand,
+                   self.ptr(self.status), _cabi.raw_stream(self.device))
+        g.seed_local = slot["seed_local"]
+        if pos is not None:
+            g.pos_undirected = pos
+        return g, slot["labels"]
+
+    def check_status(self) -> None:
+        """Synchronising check of the batcher's status word (raises on any bit, never truncates silently)."""
+        s = int(self.status.item())
+        if s:
+            raise RuntimeError("gcc_pack_graphs: " + ", ".join(n for b, n in self._BITS if s & b) +
+                               " -- the batch was cut at a graph boundary")
 
 
 class NodeClassificationDataset:
@@ -75,9 +215,12 @@ class NodeClassificationDataset:
 
 class GraphClassificationDataset:
     def __init__(self, dataset=None, rw_hops=64, subgraph_size=64, restart_prob=0.8, positional_embedding_size=32,
-                 step_dist=(1.0, 0.0, 0.0), graphs=None, edge_multiplicity=1, batch_size=256, device="cuda"):
+                 step_dist=(1.0, 0.0, 0.0), graphs=None, edge_multiplicity=1, batch_size=256, device="cuda", batcher="auto",
+                 num_buffers=2):
         """``graphs``: list of (row_ptr, col_idx) of simple symmetric graphs (what TUDataset holds for
-        imdb-binary / imdb-multi / rdt-b / rdt-5k / collab); the dataset files themselves are not bundled."""
+        imdb-binary / imdb-multi / rdt-b / rdt-5k / collab); the dataset files themselves are not bundled.
+        ``batcher``: ``"device"`` (gcc_pack_graphs from a resident corpus into a ring of ``num_buffers`` buffer sets; what
+        ``"auto"`` means on a GPU) or ``"host"`` (the NumPy loop below; ``"auto"`` off the GPU)."""
         if list(step_dist) != [1.0, 0.0, 0.0]:
             raise NotImplementedError("step_dist other than [1, 0, 0]")
         assert positional_embedding_size > 1
@@ -94,9 +237,22 @@ class GraphClassificationDataset:
         # capacity convention of the pipeline (as DeviceRWRSampler: B * (largest subgraph + 1)): the eigensolver sizes its
         # per-subgraph workspace as node_cap / batch_size
         self.node_cap = self.batch_size * (max(len(rp) - 1 for rp, _ in self.graphs) + 1)
+        self.batcher = resolve_batcher(batcher, device)
+        self.num_buffers = int(num_buffers)
+        self._corpus = None                                           # DeviceGraphCorpus, uploaded on first use
 
     def __len__(self):
         return self.length
+
+    def _device_corpus(self):
+        if self._corpus is None:
+            self._corpus = DeviceGraphCorpus(self.graphs, self.batch_size, device=self.device, num_buffers=self.num_buffers,
+                                             node_cap=self.node_cap, placeholder=False)
+        return self._corpus
+
+    def check_status(self):
+        if self._corpus is not None:
+            self._corpus.check_status()
 
     def _convert_idx(self, idx):                                      # :326-329
         rp, _ = self.graphs[idx]
@@ -135,9 +291,22 @@ class GraphClassificationDataset:
         return g
 
     def __iter__(self):
+        if self.batcher == "device":
+            yield from self._iter_device()
+            return
         for lo in range(0, self.length, self.batch_size):
             g = self._batch(lo, min(lo + self.batch_size, self.length))
             yield g, g                                                # graph_q and graph_k are the same whole graph
+
+    def _iter_device(self):
+        corpus, B = self._device_corpus(), self.batch_size
+        order = corpus.index_tensor(np.arange(self.length))           # one upload; every batch passes a slice of it
+        for lo in range(0, self.length, B):
+            hi = min(lo + B, self.length)
+            g, _ = corpus.pack(order[lo:lo + B], corpus.entries[lo:hi].sum(), expand=1, with_pos=False)
+            g.edge_multiplicity = self.edge_multiplicity              # (kept on the batch, as the host batches do)
+            g.valid = hi - lo
+            yield g, g
 
 
 # ------------------------------------------------------------------------------------------------ labelled (--finetune)
@@ -239,10 +408,12 @@ class GraphClassificationDatasetLabeled(GraphClassificationDataset):
     first use, in batches over all graphs -- and gathered into each batch afterwards."""
 
     def __init__(self, dataset=None, rw_hops=64, subgraph_size=64, restart_prob=0.8, positional_embedding_size=32,
-                 graphs=None, labels=None, edge_multiplicity=1, batch_size=32, run_seed=0, device="cuda"):
+                 graphs=None, labels=None, edge_multiplicity=1, batch_size=32, run_seed=0, device="cuda", batcher="auto",
+                 num_buffers=3):
         super().__init__(dataset=dataset, rw_hops=rw_hops, subgraph_size=subgraph_size, restart_prob=restart_prob,
                          positional_embedding_size=positional_embedding_size, graphs=graphs,
-                         edge_multiplicity=edge_multiplicity, batch_size=batch_size, device=device)
+                         edge_multiplicity=edge_multiplicity, batch_size=batch_size, device=device, batcher=batcher,
+                         num_buffers=num_buffers)
         if labels is None:
             raise ValueError("pass labels (graph_labels of the TU dataset)")
         self.labels = np.asarray(labels).astype(np.int64)
@@ -254,6 +425,13 @@ class GraphClassificationDatasetLabeled(GraphClassificationDataset):
         self._pos = None                                               # [sum of nodes, P] on the device, every graph once
         self.posemb = None
 
+    def _device_corpus(self):
+        if self._corpus is None:
+            self._corpus = DeviceGraphCorpus(self.graphs, self.batch_size, labels=self.labels,
+                                             pos_dim=self.positional_embedding_size, expand=self.edge_multiplicity,
+                                             device=self.device, num_buffers=self.num_buffers, node_cap=self.node_cap)
+        return self._corpus
+
     def _embed_all(self):
         import torch
 
@@ -261,6 +439,18 @@ class GraphClassificationDatasetLabeled(GraphClassificationDataset):
 
         self.posemb = DevicePosEmb(self.batch_size, self.node_cap, self.positional_embedding_size, device=self.device,
                                    seed=self.run_seed, num_buffers=1)
+        if self.batcher == "device":                                   # the same batches, idx = arange, simple CSR
+            corpus, B = self._device_corpus(), self.batch_size
+            order = corpus.index_tensor(np.arange(self.length))
+            table = torch.zeros(int(self.first[-1]), self.positional_embedding_size, dtype=torch.float32, device=self.device)
+            for lo in range(0, self.length, B):
+                hi = min(lo + B, self.length)
+                g, _ = corpus.pack(order[lo:lo + B], corpus.entries[lo:hi].sum(), expand=1, with_pos=False)
+                self.posemb(g)
+                a, b = int(self.first[lo]), int(self.first[hi])
+                table[a:b].copy_(g.pos_undirected[: b - a])
+            self._pos = table
+            return
         parts = []
         for lo in range(0, self.length, self.batch_size):
             idx = np.arange(lo, min(lo + self.batch_size, self.length))
@@ -303,9 +493,42 @@ class GraphClassificationDatasetLabeled(GraphClassificationDataset):
         g.valid = len(idx)
         return g
 
+    def _device_batch(self, idx_dev, idx, ready=None):
+        """the batch of the graphs ``idx`` whose indices are already on the device (``idx_dev``: int32 [B], -1 = padding)"""
+        import torch
+
+        if self._pos is None:
+            self._embed_all()
+        corpus = self._device_corpus()
+        corpus.set_pos(self._pos)
+        if ready is not None:                                          # the upload may have been issued on another stream
+            torch.cuda.current_stream(self.device).wait_event(ready)
+        g, lab = corpus.pack(idx_dev, corpus.entries[idx].sum())       # entries repeated edge_multiplicity times in place
+        g.edge_multiplicity = 1
+        g.valid = len(idx)
+        return g, lab
+
+    def batch_calls(self, order):
+        """one callable per batch of ``order``; the device batcher uploads the whole order once (padded with -1) and every
+        call passes a slice of it, so a batch costs no host-to-device copy"""
+        import torch
+
+        order = np.asarray(order, dtype=np.int64)
+        chunks = [order[lo:lo + self.batch_size] for lo in range(0, len(order), self.batch_size)]
+        if self.batcher != "device":
+            return [functools.partial(self.make_batch, c) for c in chunks]
+        B = self.batch_size
+        order_dev = self._device_corpus().index_tensor(order)
+        ready = torch.cuda.Event()
+        ready.record(torch.cuda.current_stream(self.device))
+        return [functools.partial(self._device_batch, order_dev[i * B:(i + 1) * B], c, ready) for i, c in enumerate(chunks)]
+
     def make_batch(self, idx):
         import torch
 
+        if self.batcher == "device":
+            idx = np.asarray(idx, dtype=np.int64)
+            return self._device_batch(self._device_corpus().index_tensor(idx), idx)
         if self._pos is None:
             self._embed_all()
         idx = np.asarray(idx, dtype=np.int64)
@@ -321,10 +544,15 @@ class GraphClassificationDatasetLabeled(GraphClassificationDataset):
         return g, torch.from_numpy(lab).to(self.device)
 
     def batches(self, order):
+        if self.batcher == "device":
+            for call in self.batch_calls(order):
+                yield call()
+            return
         order = np.asarray(order, dtype=np.int64)
         for lo in range(0, len(order), self.batch_size):
             yield self.make_batch(order[lo:lo + self.batch_size])
 
     def check_status(self):
+        super().check_status()
         if self.posemb is not None:
             self.posemb.check_status()

@@ -209,9 +209,12 @@ class LabeledProducer:
         order = np.asarray(order, dtype=np.int64)
         B = self.ds.batch_size
         chunks = [order[lo:lo + B] for lo in range(0, len(order), B)]
+        # a dataset that can upload the epoch's order once hands out one call per batch (GraphClassificationDatasetLabeled)
+        calls = self.ds.batch_calls(order) if hasattr(self.ds, "batch_calls") else [
+            (lambda c=c: self.ds.make_batch(c)) for c in chunks]
         if not self.prefetch:
-            for c in chunks:
-                yield self.ds.make_batch(c)
+            for call in calls:
+                yield call()
             return
         pending = []
         main = torch.cuda.current_stream(self.dev)
@@ -219,7 +222,7 @@ class LabeledProducer:
         def launch(i):
             with torch.cuda.stream(self.side):
                 self.side.wait_stream(main) if not self._released else self.side.wait_event(self._released[0])
-                q, lab = self.ds.make_batch(chunks[i])
+                q, lab = calls[i]()
                 ev = torch.cuda.Event()
                 ev.record(self.side)
             pending.append((q, lab, ev))

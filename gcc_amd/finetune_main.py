@@ -32,7 +32,7 @@ def apply_resume(args, checkpoint_opt):
     """train.py:487-505: the checkpoint's options, with these of the command line"""
     pretrain_args = checkpoint_opt
     for name in ("fold_idx", "gpu", "finetune", "resume", "cv", "dataset", "epochs", "num_workers", "batch_size",
-                 "edgelist", "nodelabel", "tudataset", "graphs_npz", "edge_multiplicity", "no_prefetch"):
+                 "edgelist", "nodelabel", "tudataset", "graphs_npz", "edge_multiplicity", "no_prefetch", "graph_batcher"):
         setattr(pretrain_args, name, getattr(args, name, None))
     if args.dataset in GRAPH_CLASSIFICATION_DSETS:
         pretrain_args.num_workers = 0           # train.py:500-502
@@ -60,7 +60,8 @@ def load_labelled(args, device):
             raise SystemExit(f"--finetune on {args.dataset} (graph classification) needs --tudataset <folder> or --graphs-npz "
                              "(dataset files are not bundled)")
         return GraphClassificationDatasetLabeled(graphs=graphs, labels=labels, edge_multiplicity=max(mult, 1),
-                                                 run_seed=args.seed, **kw)
+                                                 run_seed=args.seed, batcher=getattr(args, "graph_batcher", None) or "auto",
+                                                 **kw)
     if not getattr(args, "edgelist", None) or not getattr(args, "nodelabel", None):
         raise SystemExit(f"--finetune on {args.dataset} (node classification) needs --edgelist data/<name>/<name>.edgelist and "
                          "--nodelabel data/<name>/<name>.nodelabel (dataset files are not bundled)")

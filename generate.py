@@ -6,7 +6,7 @@ node of a graph as (f(q) + f(k)) / 2 over its two RWR views with the eval-mode e
 everything runs on the GPU (sampler, positional embedding, encoder).
 
 Extra flags (not in the reference): --edgelist / --nodelabel / --graph-npz / --graphs-npz / --tudataset / --edge-multiplicity /
---batch-size / --wide-eval.  ``--wide-eval resident`` embeds with a wide GIN checkpoint (--hidden-size above 64, f32- or
+--batch-size / --wide-eval / --graph-batcher.  ``--wide-eval resident`` embeds with a wide GIN checkpoint (--hidden-size above 64, f32- or
 bf16-trained) through one gcc_ginw_embed call per batch: bf16 layers resident in LDS, f32 readout (DESIGN.md section 7b has
 the rounding rule the flag opts into); the default, ``chain``, is the any-width eval chain.  Graph-classification datasets (entire_graph=True, generate.py:75-82) come as ``--graphs-npz``: node_off
 [G+1], row_ptr [N+1] (per-graph offsets restarting at 0 are rebuilt from node_off), col_idx (local ids)."""
@@ -91,7 +91,8 @@ def main(args_test, pipeline=None):
         train_dataset = GraphClassificationDataset(                  # generate.py:75-82
             dataset=args_test.dataset, rw_hops=args.rw_hops, subgraph_size=args.subgraph_size,
             restart_prob=args.restart_prob, positional_embedding_size=args.positional_embedding_size,
-            graphs=graphs, edge_multiplicity=mult, batch_size=args_test.batch_size, device=args.device)
+            graphs=graphs, edge_multiplicity=mult, batch_size=args_test.batch_size, device=args.device,
+            batcher=getattr(args_test, "graph_batcher", None) or "auto")
         node_cap = train_dataset.node_cap
     else:
         train_dataset, node_cap, check_sampler = pipeline.node_dataset(      # generate.py:84-91
@@ -105,6 +106,8 @@ def main(args_test, pipeline=None):
     emb = test_moco(train_dataset, model, posemb, args)
     if graphs is None:
         check_sampler()
+    else:
+        train_dataset.check_status()
     posemb.check_status()
     if model.resident_eval:
         model.resident_engine().check_status()                       # (before anything is written)
@@ -128,6 +131,7 @@ if __name__ == "__main__":
     parser.add_argument("--tudataset", type=str, default=None, help="folder with the raw TU files <NAME>_A.txt, <NAME>_graph_indicator.txt, <NAME>_graph_labels.txt of --dataset (imdb-binary, imdb-multi, rdt-b, rdt-5k, collab)")
     parser.add_argument("--edge-multiplicity", type=int, default=0, help="copies of every edge in the reference's DGL graph (edge lists: detected; npz: default 2)")
     parser.add_argument("--batch-size", type=int, default=256)
+    parser.add_argument("--graph-batcher", choices=["auto", "host", "device"], default="auto", help="--graphs-npz / --tudataset: assemble batches on the device (gcc_pack_graphs; auto on a GPU) or with the host loop")
     parser.add_argument("--wide-eval", choices=["chain", "resident"], default="chain", help="wide GIN checkpoints: the any-width eval chain (f32 or the checkpoint's --encoder-dtype), or one LDS-resident bf16 call per batch (gcc_ginw_embed; f32 readout)")
     # fmt: on
     a = parser.parse_args()

@@ -771,6 +771,43 @@ int64_t gcc_gat_backward_workspace_bytes(const gcc_gat_weights *w, int32_t node_
 int32_t gcc_gat_backward(const gcc_gat_pass *p, const gcc_gat_weights *w, const float *dout, const gcc_gat_grads *g,
                          int32_t accumulate, void *workspace, int64_t workspace_bytes, void *stream);
 
+/* ------------------------------------------------------ whole-graph batches ---
+ * GraphClassificationDataset / GraphClassificationDatasetLabeled of the reference (graph_dataset.py:306-385,
+ * entire_graph=True): an item is a whole small graph in its own node order, a batch is dgl.batch of the selected graphs.
+ * The corpus (every graph of the dataset, concatenated) is uploaded once; gcc_pack_graphs writes the batch of the graphs
+ * idx[0..B) into caller-owned buffers -- what the host loop of gcc_amd/datasets.py (_batch_of, the positional-row gather,
+ * _expand_multiplicity) assembles, bit for bit. */
+typedef struct gcc_graph_corpus {
+    int32_t num_graphs;          /* G                                                                        */
+    int32_t pos_dim;             /* P: columns of pos, even and >= 2 (read only when pos is given)            */
+    const int32_t *node_first;   /* device [G + 1]: first node of every graph in the concatenation            */
+    const int32_t *row_ptr;      /* device [N_tot + 1]: GLOBAL entry offsets; graph g's own row_ptr is
+                                    row_ptr[node_first[g] ..] - row_ptr[node_first[g]]                        */
+    const int32_t *col_idx;      /* device [E_tot]: node ids local to their graph                             */
+    const int32_t *seed_local;   /* device [G]: out_degrees().argmax(), first maximum (data_util.py:228-237)  */
+    const int32_t *labels;       /* device [G] or NULL                                                        */
+    const float *pos;            /* device [N_tot][P] or NULL: every graph's positional embedding; may be set
+                                    after the eigensolver has run over all graphs                             */
+} gcc_graph_corpus;
+#define GCC_PACK_GRAPHS_MAX_BATCH 1024     /* graphs per call (one workgroup forms the batch offsets)          */
+/* bits of gcc_pack_graphs' status word (a word of its own, not the sampler's) */
+#define GCC_STATUS_PACK_NODE_OVERFLOW 1    /* the selected graphs have more than node_cap nodes                */
+#define GCC_STATUS_PACK_EDGE_OVERFLOW 2    /* ... more than edge_cap entries (after `expand`)                  */
+#define GCC_STATUS_PACK_BAD_INDEX     4    /* an index outside [-1, G): treated as padding                     */
+/* idx: device [B], 1 <= B <= GCC_PACK_GRAPHS_MAX_BATCH; -1 = padding row (an empty graph, seed_local_out 0, labels_out -1);
+ * an index may occur several times.  Written: out->node_off / edge_off [B + 1], and for the n = node_off[B] live rows
+ * graph_id [n], row_ptr [n + 1] (batched entry offsets), col_idx [edge_off[B]] (batched node ids); out->parent_nid is not
+ * touched.  pos_out (device [node_cap][P], or NULL): rows 0..n-1 = the graphs' rows of corpus->pos, when both are given.
+ * seed_local_out device [B]; labels_out device [B] or NULL (-1 everywhere when the corpus has no labels).
+ * expand >= 1: every entry is written `expand` times in a row and row_ptr / edge_off are multiplied by it (a uniform
+ * multigraph as simple CSR).  Rows and entries past the live extents are unspecified.
+ * Capacity: the leading graphs that fit node_cap and edge_cap form the batch, the others become empty graphs and
+ * status (device int32[1], OR-ed, zeroed by the caller) reports why; nothing is written past either capacity.
+ * Two launches (batch offsets; rows and entries by tiles), no workspace. */
+int32_t gcc_pack_graphs(const gcc_graph_corpus *corpus, const int32_t *idx, int32_t B, const gcc_batch_out *out,
+                        float *pos_out, int32_t *seed_local_out, int32_t *labels_out, int32_t expand, int32_t *status,
+                        void *stream);
+
 #ifdef __cplusplus
 }
 #endif

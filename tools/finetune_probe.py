@@ -110,7 +110,8 @@ def main():
         node = NodeClassificationDatasetLabeled(graph=(rp, ci), labels=labels, rw_hops=256, batch_size=B, device=dev,
                                                 num_buffers=8)
         run_case("node", node, 4, B, a.steps, dev)
-        grp = GraphClassificationDatasetLabeled(graphs=graphs, labels=glabels, rw_hops=256, batch_size=B, device=dev)
+        grp = GraphClassificationDatasetLabeled(graphs=graphs, labels=glabels, rw_hops=256, batch_size=B, device=dev,
+                                                num_buffers=8)
         run_case("graph", grp, 2, B, a.steps, dev)
 
 

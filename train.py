@@ -132,6 +132,7 @@ def parse_option(argv=None):
     parser.add_argument("--graphs-npz", type=str, default=None, help="--finetune, graph classification: npz with node_off/row_ptr/col_idx/graph_labels")
     parser.add_argument("--edge-multiplicity", type=int, default=0, help="copies of every edge in the reference's DGL graph (edge lists: detected)")
     parser.add_argument("--no-prefetch", action="store_true", help="--finetune: make each batch on the step's stream")
+    parser.add_argument("--graph-batcher", choices=["auto", "host", "device"], default="auto", help="--finetune on graph-classification datasets: assemble batches on the device (gcc_pack_graphs; auto on a GPU) or with the host loop")
     # fmt: on
 
     opt = parser.parse_args(argv)
