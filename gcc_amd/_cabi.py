@@ -217,6 +217,23 @@ class GccClsHeadArgs(ctypes.Structure):      # gcc_cls_head_args: the fine-tunin
     ]
 
 
+class GccSimArgs(ctypes.Structure):          # gcc_sim_args: similarity search (csrc/simsearch.hip)
+    _fields_ = [
+        ("emb_q", _VP), ("rows_q", ctypes.c_int64), ("ld_q", ctypes.c_int64),
+        ("emb_c", _VP), ("rows_c", ctypes.c_int64), ("ld_c", ctypes.c_int64),
+        ("q_idx", _VP), ("c_idx", _VP), ("target", _VP),
+        ("mq", ctypes.c_int32), ("mc", ctypes.c_int32), ("D", ctypes.c_int32), ("k", ctypes.c_int32),
+        ("normalize", ctypes.c_int32), ("splits", ctypes.c_int32),
+        ("greater", _VP), ("equal_before", _VP), ("target_score", _VP), ("topk_col", _VP), ("topk_score", _VP),
+    ]
+
+
+SIM_MAX_DIM = 256
+SIM_MAX_K = 64
+SIM_MAX_SPLITS = 64
+STATUS_SIM_ZERO_ROW = 1                      # gcc_sim_search's own status word
+STATUS_SIM_BAD_INDEX = 2
+
 CLS_HEAD_MAX_CLASSES = 64
 CLS_HEAD_MAX_DIM = 256
 
@@ -380,6 +397,9 @@ SIGNATURES = {
     "gcc_pack_graphs": (ctypes.c_int32, [ctypes.POINTER(GccGraphCorpus), ctypes.c_void_p, ctypes.c_int32,
                                          ctypes.POINTER(GccBatchOut), ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                          ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p]),
+    "gcc_sim_workspace_bytes": (ctypes.c_int64, [ctypes.c_int32] * 5),
+    "gcc_sim_search": (ctypes.c_int32, [ctypes.POINTER(GccSimArgs), ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p,
+                                        ctypes.c_void_p]),
 }
 # symbols declared in the header but not built yet are listed here while the build is in progress
 PENDING = set()

@@ -8,6 +8,8 @@ inserts every pair in both directions (data_util.py:84-85) and its dataset class
 uniform multiplicity (gcc_gin_pass.edge_multiplicity); files whose pairs repeat a non-uniform number of times, and self
 loops, are rejected rather than approximated.
 
+``read_ss_graph``: the ``<name>.graph`` / ``<name>.dict`` pairs of the similarity-search task (data_util.py:145-191).
+
 ``read_tudataset``: the raw TU Dortmund collection layout (``<NAME>_A.txt``, ``<NAME>_graph_indicator.txt``,
 ``<NAME>_graph_labels.txt``) that DGL's ``TUDataset`` downloads for ``create_graph_classification_dataset``
 (data_util.py:47-58: imdb-binary, imdb-multi, rdt-b, rdt-5k, collab) -> the list of small graphs
@@ -72,6 +74,40 @@ def read_edgelist(edgelist_path: str, nodelabel_path: str = None, hindex: bool =
         y[nodes, labels] = 1
         out["y"] = y
     return out
+
+
+def read_ss_graph(graph_path: str, dict_path: str):
+    """``<name>.graph`` / ``<name>.dict`` of the similarity-search datasets (data/panther) as ``SSDataset._preprocess`` reads
+    them (data_util.py:159-191): the first line of the graph file is a header; every other line is ``x y t``, a co-author pair
+    and the number of joint papers, with ids re-indexed in order of first appearance; the dict file holds ``name<TAB>id``
+    lines, and an id that no edge mentions gets the next free index.
+    -> dict(node2id, name_dict {name: index}, pairs int64 [m, 2], weights int64 [m], num_nodes).  The reference's edge list
+    is every pair ``weights`` times in both directions.  No CSR is built: these weighted networks need a non-uniform edge
+    multiplicity, which ``csr_from_pairs`` refuses."""
+    node2id, pairs, weights = {}, [], []
+    with open(graph_path) as f:
+        f.readline()
+        for line in f:
+            if not line.strip():
+                continue
+            x, y, t = (int(v) for v in line.split()[:3])
+            for n in (x, y):
+                if n not in node2id:
+                    node2id[n] = len(node2id)
+            pairs.append((node2id[x], node2id[y]))
+            weights.append(t)
+    name_dict = {}
+    with open(dict_path) as f:
+        for line in f:
+            if not line.strip():
+                continue
+            name, x = line.rstrip("\n").rsplit("\t", 1)
+            x = int(x)
+            if x not in node2id:
+                node2id[x] = len(node2id)
+            name_dict[name] = node2id[x]
+    return dict(node2id=node2id, name_dict=name_dict, pairs=np.asarray(pairs, dtype=np.int64).reshape(-1, 2),
+                weights=np.asarray(weights, dtype=np.int64), num_nodes=len(node2id))
 
 
 TU_NAMES = {"imdb-binary": "IMDB-BINARY", "imdb-multi": "IMDB-MULTI", "rdt-b": "REDDIT-BINARY",

@@ -808,6 +808,48 @@ int32_t gcc_pack_graphs(const gcc_graph_corpus *corpus, const int32_t *idx, int3
                         float *pos_out, int32_t *seed_local_out, int32_t *labels_out, int32_t expand, int32_t *status,
                         void *stream);
 
+/* -------------------------------------------------------- similarity search ---
+ * gcc/tasks/similarity_search.py:41-69 of the reference: the rows of two embedding tables are divided by their L2 norm,
+ * every selected row of the first (the queries) is scored against every selected row of the second (the candidates),
+ * and the rank of each query's true match decides Recall@k.  One call gives the rank counts and the k best candidates
+ * of every query; the [mq, mc] score matrix is never stored.
+ * Scores: s_ij = <q_i, c_j>, exact-f32 products and sums on v_mfma_f32_16x16x4_f32.
+ * Order of a query's candidates: score descending, then column ascending (the reference's argsort leaves ties open).
+ *   greater[i]      = #{j : s_ij > s_it}              t = target[i]
+ *   equal_before[i] = #{j < t : s_ij == s_it}         query i is a hit at k  <=>  greater + equal_before < k
+ *   target_score[i] = s_it, the very value the counts compare against (NaN without a target)
+ *   topk_col / topk_score [i]: the first min(k, mc) candidates in that order, then -1 / -inf
+ * Rows without a target (target NULL, -1 or refused) get greater = equal_before = -1.  Candidates and queries whose
+ * index is refused are absent: an absent candidate is neither counted nor listed, an absent query has no target and an
+ * empty list; a target that is refused, or that names an absent candidate, is no target (the list is still written).
+ * Inputs are expected to be finite. */
+#define GCC_SIM_MAX_DIM 256
+#define GCC_SIM_MAX_K   64
+#define GCC_SIM_MAX_SPLITS 64
+#define GCC_STATUS_SIM_ZERO_ROW  1   /* normalize != 0 and a selected row has norm 0: it scores 0 against everything */
+#define GCC_STATUS_SIM_BAD_INDEX 2   /* a q_idx / c_idx entry outside its table, or a target outside [-1, mc): row treated as absent */
+typedef struct gcc_sim_args {
+    const float *emb_q; int64_t rows_q, ld_q;   /* device [rows_q, ld_q], ld_q >= D */
+    const float *emb_c; int64_t rows_c, ld_c;
+    const int32_t *q_idx;      /* device [mq] rows of emb_q, or NULL = 0..mq-1; repeats allowed */
+    const int32_t *c_idx;      /* device [mc] rows of emb_c, or NULL; repeats allowed */
+    const int32_t *target;     /* device [mq]: candidate COLUMN (0..mc-1) of query i's true match, -1 = none; NULL = none */
+    int32_t mq, mc, D, k;      /* 1 <= D <= 256; 0 <= k <= 64 (0: no lists) */
+    int32_t normalize;         /* 1: rows divided by their L2 norm (similarity_search.py:49-50); 0: raw dot products */
+    int32_t splits;            /* candidate ranges that are searched by separate workgroups and merged (at most
+                                  GCC_SIM_MAX_SPLITS, and at most one per 16 candidates); 0 = chosen by the library */
+    int32_t *greater, *equal_before;   /* device [mq] out, or NULL */
+    float   *target_score;             /* device [mq] out, or NULL */
+    int32_t *topk_col; float *topk_score;   /* device [mq, k] out, or NULL */
+} gcc_sim_args;
+/* bytes of workspace for a call of these sizes: O((mq + mc) * Dpad + splits * mq * k); negative on a bad size */
+int64_t gcc_sim_workspace_bytes(int32_t mq, int32_t mc, int32_t D, int32_t k, int32_t splits);
+/* status: device int32[1], OR-ed, zeroed by the caller.  D, k, splits or a size out of range, a NULL table, ld < D,
+ * mq / mc beyond the table without an index list and a short workspace return rc < 0, name the member in
+ * gcc_last_error() and launch nothing.  mq == 0 or mc == 0: rc 0, no launch, nothing written.  Four launches (gather
+ * and normalise; target scores; tiles; merge of the splits), no host synchronisation. */
+int32_t gcc_sim_search(const gcc_sim_args *a, void *workspace, int64_t workspace_bytes, int32_t *status, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
