@@ -316,35 +316,78 @@ __global__ void ginx_feat_kernel(const int32_t *node_off, const int32_t *row_ptr
     x0[(int64_t)v * d_in + c] = val;
 }
 
-// d degree_embedding[clamp(deg(v))][c] += dx0[v][pos_dim + c]   (the gradient of nn.Embedding: a scatter-add).  Most nodes share a
-// handful of small degrees: one global atomic per (node, column) queued 25 k nodes on a few cache lines (382 us at bsz 256).  A
-// workgroup now adds its kFeatRows rows into an LDS copy of the table first and flushes the entries it touched.
-constexpr int kFeatRows = 1024, kFeatMaxElems = 10240;     // rows per workgroup; (max_degree + 1) * de floats of LDS (40 KiB)
+// d degree_embedding[clamp(deg(v))][c] += dx0[v][pos_dim + c]   (the gradient of nn.Embedding: a scatter-add), in a FIXED order, so
+// that two backward passes of one model give the same bits.  A workgroup adds its kFeatRows rows into an LDS copy of the table
+// without atomics: entry (d, c) belongs to ONE thread -- class lane d % CL, column lane c % cw -- which walks the rows in
+// ascending order (their degrees and their de columns of dx0 are staged in LDS first), and writes the whole copy to its slab of
+// `part`; ginx_feat_reduce_kernel then adds the slabs of the live row blocks in block order.
+constexpr int kFeatRows = 256, kFeatMaxElems = 10240, kFeatStage = 4096;    // rows per workgroup; table floats in LDS (40 KiB); staged dx0 floats
 __global__ __launch_bounds__(256) void ginx_feat_bwd_kernel(const int32_t *node_off, const int32_t *row_ptr, int B, int pos_dim, int de, int max_degree,
-                                                             const float *dx0, float *demb)
+                                                             const float *dx0, float *part /* [row blocks][(max_degree + 1) * de] */)
 {
     __shared__ float E[kFeatMaxElems];
+    __shared__ float X[kFeatStage];
+    __shared__ int Dg[kFeatRows];
     const int d_in = pos_dim + de + 1;
     const int N = node_off[B];
     const int r0 = (int)blockIdx.x * kFeatRows, r1 = min(N, r0 + kFeatRows);
-    if (r0 >= N) return;
-    const int elems = (max_degree + 1) * de;
-    const bool lds = elems <= kFeatMaxElems;                 // (block-uniform; larger tables: straight to global memory)
-    if (lds) {
-        for (int i = (int)threadIdx.x; i < elems; i += 256) E[i] = 0.f;
-        __syncthreads();
+    if (r0 >= N) return;                                     // (block-uniform)
+    const int elems = (max_degree + 1) * de;                 // <= kFeatMaxElems, de <= kFeatStage (the host's choice of this kernel)
+    const int tid = (int)threadIdx.x;
+    for (int i = tid; i < elems; i += 256) E[i] = 0.f;
+    for (int i = tid; i < r1 - r0; i += 256) {
+        int d = row_ptr[r0 + i + 1] - row_ptr[r0 + i];
+        Dg[i] = d < 0 ? 0 : (d > max_degree ? max_degree : d);
     }
+    const int cw = de < 256 ? de : 256, CL = 256 / cw;       // column lanes, degree-class lanes
+    const int j = tid / cw, c0 = tid % cw;
+    const int rp = kFeatStage / de;                          // rows staged per round (>= 1)
+    for (int s0 = r0; s0 < r1; s0 += rp) {
+        const int s1 = min(r1, s0 + rp);
+        __syncthreads();                                     // E, Dg written; the previous round's X consumed
+        for (int i = tid; i < (s1 - s0) * de; i += 256) X[i] = dx0[(int64_t)(s0 + i / de) * d_in + pos_dim + i % de];
+        __syncthreads();
+        if (j < CL)
+            for (int v = s0; v < s1; ++v) {
+                const int d = Dg[v - r0];
+                if (d % CL == j)
+                    for (int c = c0; c < de; c += cw) E[d * de + c] += X[(v - s0) * de + c];
+            }
+    }
+    __syncthreads();
+    for (int i = tid; i < elems; i += 256) part[(int64_t)blockIdx.x * elems + i] = E[i];
+}
+
+__global__ __launch_bounds__(256) void ginx_feat_reduce_kernel(const int32_t *node_off, int B, int elems, const float *part, float *demb)
+{
+    __shared__ float S[4][64];                               // four threads per entry add a quarter of the blocks each, in block order
+    const int ci = (int)threadIdx.x & 63, seg = (int)threadIdx.x >> 6;
+    const int i = (int)blockIdx.x * 64 + ci;
+    const int nb = (node_off[B] + kFeatRows - 1) / kFeatRows;
+    const int per = (nb + 3) / 4, b0 = seg * per, b1 = min(nb, b0 + per);
+    float s = 0.f;
+    if (i < elems) {
+#pragma unroll 8
+        for (int b = b0; b < b1; ++b) s += part[(int64_t)b * elems + i];
+    }
+    S[seg][ci] = s;
+    __syncthreads();
+    if (seg == 0 && i < elems) demb[i] = ((S[0][ci] + S[1][ci]) + S[2][ci]) + S[3][ci];
+}
+
+// tables too large for LDS: one global atomic per (node, column) into the zeroed gradient (arrival order: not bit-reproducible)
+__global__ __launch_bounds__(256) void ginx_feat_bwd_atomic_kernel(const int32_t *node_off, const int32_t *row_ptr, int B, int pos_dim, int de,
+                                                                    int max_degree, const float *dx0, float *demb)
+{
+    const int d_in = pos_dim + de + 1;
+    const int N = node_off[B];
+    const int r0 = (int)blockIdx.x * 1024, r1 = min(N, r0 + 1024);
+    if (r0 >= N) return;
     for (int64_t i = (int64_t)r0 * de + threadIdx.x; i < (int64_t)r1 * de; i += 256) {
         const int v = (int)(i / de), c = (int)(i % de);
         int d = row_ptr[v + 1] - row_ptr[v];
         d = d < 0 ? 0 : (d > max_degree ? max_degree : d);
-        const float g = dx0[(int64_t)v * d_in + pos_dim + c];
-        if (lds) atomicAdd(&E[d * de + c], g); else atomicAdd(&demb[(int64_t)d * de + c], g);
-    }
-    if (lds) {
-        __syncthreads();
-        for (int i = (int)threadIdx.x; i < elems; i += 256)
-            if (E[i] != 0.f) atomicAdd(&demb[i], E[i]);
+        atomicAdd(&demb[(int64_t)d * de + c], dx0[(int64_t)v * d_in + pos_dim + c]);
     }
 }
 
@@ -404,17 +447,19 @@ __global__ __launch_bounds__(256) void ginx_spmm_kernel(const int32_t *node_off,
     }
 }
 
-// column sums over the live rows, fp64: sums[0][c] += sum_v f(v, c), sums[1][c] += sum_v g(v, c)
+// column sums over the live rows, fp64, per 128-row block: part[block][0][c] = sum_v f(v, c), part[block][1][c] = sum_v g(v, c);
+// ginx_colsum_reduce_kernel adds the live blocks in a fixed order (no atomics: two passes of one model give the same bits)
 //   mode 0 (BatchNorm forward statistics):  f = x, g = x^2
 //   mode 1 (BatchNorm + ReLU backward):     gr = dy * (y > 0);  f = gr,  g = gr * xhat,  xhat = (x - mean) * rstd
 //   mode 2 (bias gradient):                 f = x              (sums[1] untouched)
 __global__ __launch_bounds__(256) void ginx_colsum_kernel(const int32_t *node_off, int B, int fixed_rows, int mode, const float *x,
                                                            const float *y, const float *dy, const float *mr /* [2][D] mean, rstd */,
-                                                           int D, double *sums)
+                                                           int D, double *part)
 {
     const int N = fixed_rows > 0 ? fixed_rows : node_off[B];
     const int r0 = (int)blockIdx.x * 128, r1 = min(N, r0 + 128);
     if (r0 >= N) return;
+    double *sums = part + (int64_t)blockIdx.x * (mode == 2 ? 1 : 2) * D;
     for (int c = (int)threadIdx.x; c < D; c += 256) {
         double s0 = 0.0, s1 = 0.0;
         // (eight rows requested per round: a row at a time was a chain of 128 dependent-latency loads, 60 us per call)
@@ -454,8 +499,39 @@ __global__ __launch_bounds__(256) void ginx_colsum_kernel(const int32_t *node_of
                     if (r + u < r1) s0 += (double)v[u];
             }
         }
-        atomicAdd(&sums[c], s0);
-        if (mode != 2) atomicAdd(&sums[D + c], s1);
+        sums[c] = s0;
+        if (mode != 2) sums[D + c] = s1;
+    }
+}
+
+// sums[j] = sum over the live 128-row blocks b of part[b][j], j < n (= D or 2 D): 32 threads per entry add a thirty-second of the
+// blocks each, in block order, and thread 0 of the entry adds the 32 in order -- the same association on every run.  g0 / g1
+// (optional): the fp32 parameter gradients that sums[0 .. D) / sums[D .. 2 D) are, written in the same launch
+constexpr int kRedEntries = 8, kRedSegs = 32;
+__global__ __launch_bounds__(256) void ginx_colsum_reduce_kernel(const int32_t *node_off, int B, int fixed_rows, const double *part, int n, int D,
+                                                                  double *sums, float *g0, float *g1)
+{
+    __shared__ double S[kRedSegs][kRedEntries];
+    const int N = fixed_rows > 0 ? fixed_rows : node_off[B];
+    const int nb = (N + 127) / 128;
+    const int cj = (int)threadIdx.x % kRedEntries, seg = (int)threadIdx.x / kRedEntries;
+    const int j = (int)blockIdx.x * kRedEntries + cj;
+    const int per = (nb + kRedSegs - 1) / kRedSegs;
+    const int b0 = seg * per, b1 = min(nb, b0 + per);
+    double s = 0.0;
+    if (j < n) {
+#pragma unroll 8
+        for (int b = b0; b < b1; ++b) s += part[(int64_t)b * n + j];
+    }
+    S[seg][cj] = s;
+    __syncthreads();
+    if (seg == 0 && j < n) {
+        double t = 0.0;
+#pragma unroll
+        for (int i = 0; i < kRedSegs; ++i) t += S[i][cj];
+        sums[j] = t;
+        if (j < D) { if (g0) g0[j] = (float)t; }
+        else if (g1) g1[j - D] = (float)t;
     }
 }
 
@@ -737,6 +813,8 @@ struct XLayout {                         // float offsets inside the pass's work
     int64_t pooled[GCC_GIN_MAX_LAYERS + 1], y, score;
     int64_t da, db, dc, dpool, dy, dscore;      // backward scratch: three [N, Wmax] buffers, [B, Wmax] x 3
     int64_t sums;                        // doubles: [2][Wmax] scratch of the statistics kernels (offset in FLOATS, 8-byte aligned)
+    int64_t sums_part;                   // doubles: [128-row blocks][2][Wmax] per-block column sums, added in block order into `sums`
+    int64_t feat_part;                   // floats: [kFeatRows-row blocks][kFeatMaxElems] per-block degree-embedding gradients
     int64_t wg64;                        // doubles: [Wmax][Wmax] accumulator of a weight gradient
     int64_t total;
 };
@@ -759,6 +837,8 @@ XLayout ginx_layout(int64_t N, int B, int L, int d_in, int W, int O)
     x.da = take(N * Wm); x.db = take(N * Wm); x.dc = take(N * Wm);
     x.dpool = take((int64_t)B * Wm); x.dy = take((int64_t)B * O); x.dscore = take((int64_t)B * O);
     x.sums = take(4 * Wm + 16);
+    x.sums_part = take(((N > B ? N : B) + 127) / 128 * 4 * Wm + 16);
+    x.feat_part = take((N + kFeatRows - 1) / kFeatRows * kFeatMaxElems);
     x.wg64 = take(2 * Wm * Wm + 16);
     x.total = o;
     return x;
@@ -783,6 +863,15 @@ void gemm(hipStream_t s, const float *A, int64_t sam, int64_t sak, const float *
 }
 
 inline unsigned blocks(int64_t n, int t = 256) { return (unsigned)((n + t - 1) / t); }
+
+// column sums of `cap` rows (the live ones: fixed_rows, or node_off[B]) into sums[0 .. D) (mode 2) or sums[0 .. 2 D)
+void colsum(hipStream_t s, const int32_t *node_off, int B, int64_t cap, int fixed_rows, int mode, const float *x, const float *y, const float *dy,
+            const float *mr, int D, double *part, double *sums, float *g0 = nullptr, float *g1 = nullptr)
+{
+    const int n = (mode == 2 ? 1 : 2) * D;
+    hipLaunchKernelGGL(ginx_colsum_kernel, dim3(blocks(cap, 128)), dim3(256), 0, s, node_off, B, fixed_rows, mode, x, y, dy, mr, D, part);
+    hipLaunchKernelGGL(ginx_colsum_reduce_kernel, dim3(blocks(n, kRedEntries)), dim3(256), 0, s, node_off, B, fixed_rows, (const double *)part, n, D, sums, g0, g1);
+}
 
 }  // namespace
 
@@ -829,7 +918,7 @@ int32_t gcc_ginx_forward(const gcc_ginx_pass *p, void *stream)
     const int64_t N = p->node_cap;
     const XLayout x = ginx_layout(N, B, L, d_in, W, O);
     float *ws = (float *)p->workspace;
-    double *sums = (double *)(ws + x.sums);
+    double *sums = (double *)(ws + x.sums), *sums_part = (double *)(ws + x.sums_part);
     const int32_t *rows = p->node_off + B;                   // the live row count, on the device
     const int dt = p->gemm_dtype;                            // the per-node Linears; the [B, .] readout Linears stay f32
     hipLaunchKernelGGL(ginx_feat_kernel, dim3(blocks(N * d_in)), dim3(256), 0, s, p->node_off, p->row_ptr, p->graph_id, p->seed_local, p->pos,
@@ -838,9 +927,7 @@ int32_t gcc_ginx_forward(const gcc_ginx_pass *p, void *stream)
     int D = d_in;
     auto bn = [&](const float *in, const gcc_bn &m, int64_t mr_off, float *out) {          // statistics -> (mean, rstd) -> y
         if (p->training) {
-            (void)hipMemsetAsync(sums, 0, sizeof(double) * 2 * W, s);
-            hipLaunchKernelGGL(ginx_colsum_kernel, dim3(blocks(N, 128)), dim3(256), 0, s, p->node_off, B, 0, 0, in, (const float *)nullptr,
-                               (const float *)nullptr, (const float *)nullptr, W, sums);
+            colsum(s, p->node_off, B, N, 0, 0, in, nullptr, nullptr, nullptr, W, sums_part, sums);
         }
         hipLaunchKernelGGL(ginx_bn_prepare_kernel, dim3(blocks(W)), dim3(256), 0, s, p->node_off, B, sums, W, w.bn_eps, w.bn_momentum, p->training,
                            p->update_running_stats, m.running_mean, m.running_var, m.num_batches_tracked, ws + mr_off);
@@ -888,7 +975,7 @@ int32_t gcc_ginx_backward(const gcc_ginx_pass *p, const float *dfeat, const gcc_
     const int64_t N = p->node_cap;
     const XLayout x = ginx_layout(N, B, L, d_in, W, O);
     float *ws = (float *)p->workspace;
-    double *sums = (double *)(ws + x.sums);
+    double *sums = (double *)(ws + x.sums), *sums_part = (double *)(ws + x.sums_part);
     const int32_t *rows = p->node_off + B;
     const int dt = p->gemm_dtype;                            // the per-node Linears' data and weight gradients; the readout's stay f32
     float *dA = ws + x.da, *dB_ = ws + x.db, *dC = ws + x.dc;
@@ -901,27 +988,18 @@ int32_t gcc_ginx_backward(const gcc_ginx_pass *p, const float *dfeat, const gcc_
         hipLaunchKernelGGL(ginx_mask_acc_kernel, dim3(blocks((int64_t)B * O)), dim3(256), 0, s, ws + x.dscore, keep, 1.0f / (1.0f - w.dropout_p), B * O,
                            ws + x.dy, 1);
         gemm(s, ws + x.dy, 1, O, ws + x.pooled[l], Dl, 1, gr->pred_w[l], Dl, O, Dl, B, nullptr, nullptr, 0, 0);         // dWp [O, Dl] = dy^T pooled
-        (void)hipMemsetAsync(sums, 0, sizeof(double) * O, s);
-        hipLaunchKernelGGL(ginx_colsum_kernel, dim3(blocks(B, 128)), dim3(256), 0, s, p->node_off, B, B, 2, ws + x.dy, (const float *)nullptr,
-                           (const float *)nullptr, (const float *)nullptr, O, sums);
-        hipLaunchKernelGGL(ginx_sums_to_grad_kernel, dim3(blocks(O)), dim3(256), 0, s, sums, O, gr->pred_b[l], 0);
+        colsum(s, p->node_off, B, B, B, 2, ws + x.dy, nullptr, nullptr, nullptr, O, sums_part, sums, gr->pred_b[l]);
         gemm(s, ws + x.dy, O, 1, w.pred_w[l], Dl, 1, dpool, Dl, B, Dl, O, nullptr, nullptr, 0, 0);                        // dpooled [B, Dl] = dy Wp
     };
     // BatchNorm + ReLU backward: (x, y, dy) -> dx in place of dy's buffer `dx`; gamma / beta gradients from the two column sums
     auto bn_bwd = [&](const float *xin, const float *y, const float *dy, const gcc_bn &m, int64_t mr_off, float *dx, float *dgamma, float *dbeta) {
-        (void)hipMemsetAsync(sums, 0, sizeof(double) * 2 * W, s);
-        hipLaunchKernelGGL(ginx_colsum_kernel, dim3(blocks(N, 128)), dim3(256), 0, s, p->node_off, B, 0, 1, xin, y, dy, (const float *)(ws + mr_off), W, sums);
-        hipLaunchKernelGGL(ginx_sums_to_grad_kernel, dim3(blocks(W)), dim3(256), 0, s, sums, W, dbeta, 0);
-        hipLaunchKernelGGL(ginx_sums_to_grad_kernel, dim3(blocks(W)), dim3(256), 0, s, sums + W, W, dgamma, 0);
+        colsum(s, p->node_off, B, N, 0, 1, xin, y, dy, (const float *)(ws + mr_off), W, sums_part, sums, dbeta, dgamma);
         const int vec = (W & 3) == 0 && (((uintptr_t)m.weight) & 15) == 0;
         hipLaunchKernelGGL(ginx_bn_relu_bwd_kernel, dim3(blocks(vec ? N * W / 4 : N * W)), dim3(256), 0, s, p->node_off, B, xin, y, dy, (const float *)(ws + mr_off), m.weight,
                            sums, W, dx, vec);
     };
     auto bias_grad = [&](const float *dz, float *db) {
-        (void)hipMemsetAsync(sums, 0, sizeof(double) * W, s);
-        hipLaunchKernelGGL(ginx_colsum_kernel, dim3(blocks(N, 128)), dim3(256), 0, s, p->node_off, B, 0, 2, dz, (const float *)nullptr,
-                           (const float *)nullptr, (const float *)nullptr, W, sums);
-        hipLaunchKernelGGL(ginx_sums_to_grad_kernel, dim3(blocks(W)), dim3(256), 0, s, sums, W, db, 0);
+        colsum(s, p->node_off, B, N, 0, 2, dz, nullptr, nullptr, nullptr, W, sums_part, sums, db);
     };
     // dh of the last hidden representation: only its pooled readout feeds the loss
     readout_bwd(L, ws + x.dpool);
@@ -944,9 +1022,18 @@ int32_t gcc_ginx_backward(const gcc_ginx_pass *p, const float *dfeat, const gcc_
         hipLaunchKernelGGL(ginx_spmm_kernel, dim3(blocks(N, 4)), dim3(256), 0, s, p->node_off, p->row_ptr, p->col_idx, B, dB_, Din, (const float *)dC, dA, 1.0f);
     }
     // d x0 (in dA, width d_in) -> the degree embedding's rows
-    (void)hipMemsetAsync(gr->degree_embedding, 0, sizeof(float) * (size_t)(w.max_degree + 1) * w.deg_emb_dim, s);
-    hipLaunchKernelGGL(ginx_feat_bwd_kernel, dim3(blocks(N, kFeatRows)), dim3(256), 0, s, p->node_off, p->row_ptr, B, w.pos_dim, w.deg_emb_dim,
-                       w.max_degree, dA, gr->degree_embedding);
+    const int64_t elems = (int64_t)(w.max_degree + 1) * w.deg_emb_dim;
+    if (elems <= 0) {
+    } else if (elems <= kFeatMaxElems && w.deg_emb_dim <= kFeatStage) {
+        hipLaunchKernelGGL(ginx_feat_bwd_kernel, dim3(blocks(N, kFeatRows)), dim3(256), 0, s, p->node_off, p->row_ptr, B, w.pos_dim, w.deg_emb_dim,
+                           w.max_degree, dA, ws + x.feat_part);
+        hipLaunchKernelGGL(ginx_feat_reduce_kernel, dim3(blocks(elems, 64)), dim3(256), 0, s, p->node_off, B, (int)elems, (const float *)(ws + x.feat_part),
+                           gr->degree_embedding);
+    } else {
+        (void)hipMemsetAsync(gr->degree_embedding, 0, sizeof(float) * (size_t)elems, s);
+        hipLaunchKernelGGL(ginx_feat_bwd_atomic_kernel, dim3(blocks(N, 1024)), dim3(256), 0, s, p->node_off, p->row_ptr, B, w.pos_dim, w.deg_emb_dim,
+                           w.max_degree, dA, gr->degree_embedding);
+    }
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) { snprintf(g_err, kErrLen, "gcc_ginx_backward: launch failed: %s", hipGetErrorString(e)); return -10; }
     return 0;

@@ -1,7 +1,8 @@
 """``--encoder-dtype bf16`` / ``--nce-dtype bf16`` above 64 channels: the any-width encoder and the dense head of
 gcc_amd/csrc/ginx.hip with bf16 operands on v_mfma_f32_16x16x32_bf16 (ginx_gemm_bf16_kernel; gcc_ginx_pass.gemm_dtype = 1,
 gcc_ncex_forward_dt) against tests/bf16_reference.py -- the rule restated with plain torch and run in float64 on the rounded
-values.  Emulator tier; the device tier is tests/test_wide_bf16_gpu.py.
+values.  Emulator tier; the device tier is tests/test_wide_bf16_edges_gpu.py (the same small cases through the same bodies,
+tests/wide_edges_check.py) and tests/test_wide_bf16_gpu.py (hidden 256 on a sampled batch).
 
 Bars: those tests/test_wide_encoder_emu.py uses for the f32 mode -- features rtol 2e-4 / atol 2e-5 (pooled outputs atol 2e-4,
 running statistics rtol 1e-4 / atol 1e-5), gradients 1e-3 of the tensor's largest entry against float64.  One thing is new in
@@ -27,27 +28,21 @@ of the tensor's largest entry):
     72 / 40 / 2       2.9e-7 | 2.8e-7         4.9e-5 | 4.8e-5         3.0e-4 | 1.5e-3         6.0e-8 | 6.9e-8
     fused step, 128 / 2 layers: embeddings 7.2e-6 | 6.9e-7, gradients 2.3e-4 | 1.9e-4 (inside the f32 bars)
     head (D, K) = (128, 96), (80, 200), (96, 4400), E2E: logits <= 1.5e-6 | 1.5e-6, d q <= 3.8e-6 | 5.0e-7 of its largest entry
+    head (80, 200) with 65 rows / one row, E2E at D = 65: logits <= 8.1e-7 | 8.1e-7, d q <= 5.4e-5 | 2.4e-7, gradients 1.9e-7 | 1.9e-7
 Up to three layers the kernels follow the rule to fp32 rounding; at five the rule itself is conditioned as the gap column says.
 """
-import copy
 import ctypes
 
 import pytest
 import torch
 
 from gcc_amd import _cabi
-from gcc_amd.contrast import MemoryMoCo, NCESoftmaxLoss, NCESoftmaxLossNS, WideNceEngine, e2e_logits
+from gcc_amd.contrast import MemoryMoCo
 from gcc_amd.encoder import GraphEncoder
-from gcc_amd.train_step import MoCoTrainStep
-from oracle import encoder as E
-from tests import bf16_reference as R
-from tests.hipemu.emu_driver import emu_lib
-from tests.test_headline_step_emu import B
-from tests.test_nce_emu import emu_nce
-from tests.test_wide_edges_emu import B as HB
-from tests.test_wide_edges_emu import _masks, hand_batch
+from tests import wide_edges_check as C
+from tests.test_wide_edges_emu import _masks, hand_batch  # noqa: F401
 from tests.test_wide_encoder_emu import emu_wide_engine, fixed_views
-from tests.wide_bf16_step_check import Bars, check_wide_bf16_moco_step
+from tests.wide_edges_check import EMU, check_bf16_against_rounded_oracle  # noqa: F401
 
 
 def wide_encoder(hidden, out, layers=5, **kw):
@@ -58,120 +53,25 @@ def wide_encoder(hidden, out, layers=5, **kw):
 
 
 def emu_wide_nce(dtype="bf16"):
-    return WideNceEngine(lib=emu_lib(), ptr=lambda t: 0 if t is None else t.data_ptr(), dtype=dtype)
-
-
-def _keep(layers, nb, out, seed):
-    return (torch.rand(layers, nb, out, generator=torch.Generator().manual_seed(seed)) >= 0.5).float()
-
-
-def _rounded_oracles(model, hidden, out, layers):
-    """-> (the rounded oracle in fp32, the same in float64), both with the model's state"""
-    o32 = E.OracleGraphEncoder(node_hidden_dim=hidden, output_dim=out, num_layers=layers)
-    assert {k: tuple(v.shape) for k, v in model.state_dict().items()} == {k: tuple(v.shape) for k, v in o32.state_dict().items()}
-    o32.load_state_dict(model.state_dict())
-    R.round_gin_linears(o32)
-    return o32, copy.deepcopy(o32).double()
-
-
-def _run_oracle(o, args, keep, d, dt):
-    o.zero_grad()
-    feat, pooled = o(args[0], args[1], args[2], args[3].to(dt), dropout_masks=keep.to(dt), return_all_outputs=True)
-    feat.backward(d.to(dt))
-    return feat.detach(), [p.detach() for p in pooled], {n: p.grad for n, p in o.named_parameters()}
-
-
-def check_bf16_against_rounded_oracle(model, o32, o64, q, keep, out, hidden, monkeypatch, nb=B):
-    """forward (features, pooled outputs), backward (every parameter gradient) and the running statistics of ONE training-mode
-    pass of ``model`` on ``q`` against the rounded oracles -> (the oracle's arguments, Bars with the figures)"""
-    monkeypatch.setattr(torch, "rand", lambda *a, **k: keep.clone())       # the API path draws its dropout masks here
-    feat, pooled = model(q, return_all_outputs=True)
-    assert tuple(feat.shape) == (nb, out) and all(tuple(t.shape) == (nb, hidden) for t in pooled)
-    n = int(q.node_off[nb])
-    args = (q.node_off.long(), q.row_ptr[: n + 1].long(), q.col_idx.long(), q.pos_undirected[:n])
-    d = torch.randn(nb, out, generator=torch.Generator().manual_seed(out))
-    f32, p32, g32 = _run_oracle(o32, args, keep, d, torch.float32)
-    f64, p64, g64 = _run_oracle(o64, args, keep, d, torch.float64)
-    feat.backward(d)
-    bars = Bars()
-    bars.add("features", "feat", feat.detach(), f32, f64, rtol=2e-4, atol=2e-5)
-    for i, (a, b32, b64) in enumerate(zip(pooled, p32, p64)):
-        bars.add("pooled outputs", f"pooled[{i}]", a.detach(), b32, b64, rtol=2e-4, atol=2e-4)
-    for name, p in model.named_parameters():
-        if g64[name] is None:
-            assert p.grad is None or float(p.grad.abs().sum()) == 0.0, name
-            continue
-        assert p.grad.shape == p.shape
-        scale = max(float(g64[name].abs().max()), 1e-3)
-        bars.add("gradients", f"d {name}", p.grad, g32[name], g64[name], rtol=0.0, atol=1e-3, unit=scale)
-    s32, s64 = o32.state_dict(), o64.state_dict()       # running statistics moved as torch's BatchNorm1d moves them
-    for k1, v1 in model.state_dict().items():
-        if "running_" in k1:
-            bars.add("running statistics", k1, v1, s32[k1], s64[k1], rtol=1e-4, atol=1e-5)
-        elif "num_batches" in k1:
-            assert torch.equal(v1, s64[k1]), k1
-    bars.check()
-    return args, bars
+    return EMU.wide_nce(dtype)
 
 
 @pytest.mark.parametrize("hidden,out,layers", [(128, 128, 5), (96, 80, 3), (256, 256, 5), (72, 40, 2)])
 def test_bf16_api_path_forward_backward_vs_rounded_oracle(hidden, out, layers, monkeypatch):
     """Forward features and pooled outputs, every parameter gradient, running statistics and eval mode against the rounded
     float64 oracle; d_in = 49 and the widths 72 / 96 / 40 / 80 leave partial k-tiles and edge tiles that are zero-filled in LDS."""
-    torch.manual_seed(hidden * 100 + out)
-    model = wide_encoder(hidden, out, layers, encoder_dtype="bf16")
-    assert model.wide and not model.is_padded() and model.encoder_dtype == "bf16"
-    o32, o64 = _rounded_oracles(model, hidden, out, layers)
-    model._wide_engine = emu_wide_engine()
-    model.train()
-    o32.train()
-    o64.train()
-    q, _ = fixed_views()
-    args, bars = check_bf16_against_rounded_oracle(model, o32, o64, q, _keep(layers, B, out, hidden), out, hidden, monkeypatch)
-    print(f"{hidden}/{out}/{layers}: " + bars.summary())
-    # the state survives a save / load round trip, and eval mode (running statistics, no dropout) agrees too
-    m2 = wide_encoder(hidden, out, layers, encoder_dtype="bf16")
-    m2.load_state_dict({k: v.clone() for k, v in model.state_dict().items()})
-    m2._wide_engine = emu_wide_engine()
-    m2.eval()
-    for o in (o32, o64):
-        o.load_state_dict(m2.state_dict())        # (both oracles evaluate the SAME running statistics: the model's)
-        o.eval()
-    with torch.no_grad():
-        e32 = o32(*args)
-        e64 = o64(args[0], args[1], args[2], args[3].double())
-        ev = Bars()
-        ev.add("features", "eval feat", m2(q), e32, e64, rtol=2e-4, atol=2e-5)
-        ev.add("features", "embed_views", m2.embed_views(q, q), e32, e64, rtol=2e-4, atol=2e-5)
-        ev.check()
+    C.check_bf16_api_path(EMU, hidden, out, layers, monkeypatch)
 
 
 def test_the_flag_does_something_and_f32_mode_is_untouched(monkeypatch):
     """bf16 and f32 mode differ on the same inputs; f32 mode is bit-identical to a model built without the keyword"""
-    hidden, out, layers = 96, 80, 3
-    q, _ = fixed_views()
-    keep = _keep(layers, B, out, 1)
-    monkeypatch.setattr(torch, "rand", lambda *a, **k: keep.clone())
-    d = torch.randn(B, out, generator=torch.Generator().manual_seed(2))
-    torch.manual_seed(5)
-    plain = wide_encoder(hidden, out, layers)
-    res = {}
-    for tag, kw in (("plain", {}), ("f32", dict(encoder_dtype="f32")), ("bf16", dict(encoder_dtype="bf16"))):
-        m = wide_encoder(hidden, out, layers, **kw)
-        m.load_state_dict(plain.state_dict())
-        m._wide_engine = emu_wide_engine()
-        m.train()
-        p, _buf = m.wide_engine().make_pass(m, q, training=True, keep=keep)
-        assert p.gemm_dtype == (1 if tag == "bf16" else 0)
-        feat, pooled = m(q, return_all_outputs=True)
-        feat.backward(d)
-        res[tag] = [feat.detach()] + [t.detach() for t in pooled] + [p.grad for p in m.parameters() if p.grad is not None] \
-            + [v for k, v in m.state_dict().items() if "running_" in k]
-    assert len(res["plain"]) == len(res["f32"]) == len(res["bf16"])
-    for a, b in zip(res["plain"], res["f32"]):
-        assert torch.equal(a, b)
-    assert not torch.equal(res["bf16"][0], res["f32"][0])
-    assert sum(not torch.equal(a, b) for a, b in zip(res["bf16"], res["f32"])) > len(res["f32"]) // 2
+    C.check_bf16_flag(EMU, monkeypatch)
+
+
+def test_f32_products_are_bit_identical_between_two_models(monkeypatch):
+    """the products of the flag check (tests/test_wide_bf16_edges_gpu.py says what failed on hardware first): features, pooled
+    outputs, running statistics and every Linear weight gradient"""
+    C.check_f32_products_are_reproducible(EMU, monkeypatch)
 
 
 @pytest.mark.parametrize("n_live", [1023, 1025, 2049])
@@ -179,60 +79,20 @@ def test_bf16_on_hand_built_batches_over_stale_rows(n_live, monkeypatch):
     """node_cap 2,112; a 2,100-row batch goes through the same workspace slots first (forward and backward), so the rows past the
     live count hold its activations and gradients, and the dead input rows are NaN: the bf16 staging must never read them.  1,025
     and 2,049 live rows span two and three 1,024-row split-K slabs of the weight gradients (the last one a single row)."""
-    hidden, out, layers, cap = 72, 72, 2, 2112
-    torch.manual_seed(n_live)
-    model = wide_encoder(hidden, out, layers, encoder_dtype="bf16")
-    o32, o64 = _rounded_oracles(model, hidden, out, layers)
-    model._wide_engine = emu_wide_engine()
-    model.train()
-    big = hand_batch(2100, cap, 1, hub_degree=600)
-    keep = _masks(layers, out, 6)
-    monkeypatch.setattr(torch, "rand", lambda *a, **k: keep.clone())
-    for _ in range(2):                               # (the API path alternates between two slots: fill both)
-        model(big).backward(torch.ones(HB, out))
-    model.zero_grad()
-    for m in model.modules():                        # the oracles start from the state the checked pass starts from
-        if isinstance(m, torch.nn.BatchNorm1d):
-            m.reset_running_stats()
-    o32.train()
-    o64.train()
-    g = hand_batch(n_live, cap, 10 + n_live, hub_degree=530)
-    check_bf16_against_rounded_oracle(model, o32, o64, g, keep, out, hidden, monkeypatch, nb=HB)
+    C.check_bf16_stale_rows(EMU, n_live, monkeypatch)
 
 
 @pytest.mark.parametrize("D,K", [(128, 96), (80, 200), (96, 4400)])    # (K >= 4096: the split reduction of d loss / d q)
 def test_bf16_wide_moco_head_vs_rounded_reference(D, K):
     """MemoryMoCo(inputSize > 64, nce_dtype="bf16"): dense logits, loss, prob and d loss / d q against the queue BEFORE the
     enqueue, under the rule in float64; the queue after the enqueue exactly; three steps with a wrapping ring pointer."""
-    torch.manual_seed(D + K)
-    Bq = 40
-    contrast = MemoryMoCo(D, None, K, 0.07, use_softmax=True, nce_dtype="bf16")
-    assert contrast.wide
-    contrast._engine = emu_wide_nce()
-    mem = contrast.memory.clone()
-    index = K - 50 if K > 100 else 0
-    contrast.index = index
-    for step in range(3):
-        q = torch.nn.functional.normalize(torch.randn(Bq, D), dim=1).requires_grad_()
-        k = torch.nn.functional.normalize(torch.randn(Bq, D), dim=1)
-        out = contrast(q, k)
-        loss = NCESoftmaxLoss()(out)
-        loss.backward()
-        r32 = R.moco_head(q.detach(), k, mem, 0.07)
-        r64 = R.moco_head(q.detach().double(), k.double(), mem.double(), 0.07)
-        bars = Bars()                      # (the bars of tests/test_wide_encoder_emu.py's f32 head test)
-        bars.add("logits", "out", out.dense(), r32["out"], r64["out"], rtol=1e-4, atol=1e-4)
-        bars.add("logits", "out[:, 0]", out[:, 0], r32["out"][:, 0], r64["out"][:, 0], rtol=1e-4, atol=1e-4)
-        bars.add("loss", "loss", loss.detach(), r32["loss"], r64["loss"], rtol=1e-5, atol=1e-6)
-        bars.add("prob", "prob", out.prob, r32["prob"], r64["prob"], rtol=1e-5, atol=1e-5)
-        bars.add("d q", "d q", q.grad, r32["grad_q"], r64["grad_q"], rtol=1e-3, atol=1e-3, unit=float(r64["grad_q"].abs().max()))
-        bars.check()
-        ref_mem = mem.clone()
-        ref_mem[(torch.arange(Bq) + index) % K] = k                             # memory_moco.py:55-61
-        assert torch.equal(contrast.memory, ref_mem)
-        mem, index = ref_mem, (index + Bq) % K
-        assert contrast.index == index
-    assert index < 3 * Bq                                                        # the ring pointer wrapped
+    C.check_bf16_head(EMU, D, K)
+
+
+@pytest.mark.parametrize("Bq", [65, 1])
+def test_bf16_wide_head_second_row_tile_and_single_row(Bq):
+    """65 rows enter the second 64-row M-tile of the logits and d q products, 1 leaves the first nearly empty (D = 80, K = 200)"""
+    C.check_bf16_head(EMU, 80, 200, Bq=Bq)
 
 
 def test_bf16_wide_head_differs_from_f32_head():
@@ -247,22 +107,12 @@ def test_bf16_wide_head_differs_from_f32_head():
 
 
 def test_bf16_wide_e2e_head_vs_rounded_reference():
-    torch.manual_seed(3)
-    Bq, D = 48, 128
-    fq = torch.nn.functional.normalize(torch.randn(Bq, D), dim=1).requires_grad_()
-    fk = torch.nn.functional.normalize(torch.randn(Bq, D), dim=1).requires_grad_()
-    out = e2e_logits(fq, fk, 0.07, engine=emu_wide_nce())
-    loss = NCESoftmaxLossNS()(out)
-    loss.backward()
-    r32 = R.e2e_head(fq.detach(), fk.detach(), 0.07)
-    r64 = R.e2e_head(fq.detach().double(), fk.detach().double(), 0.07)
-    bars = Bars()
-    bars.add("logits", "out", out.dense(), r32["out"], r64["out"], rtol=1e-4, atol=1e-4)
-    bars.add("loss", "loss", loss.detach(), r32["loss"], r64["loss"], rtol=1e-5, atol=1e-6)
-    bars.add("prob", "prob", out.prob, r32["prob"], r64["prob"], rtol=1e-5, atol=1e-5)
-    for name, got in (("grad_q", fq.grad), ("grad_k", fk.grad)):
-        bars.add("gradients", name, got, r32[name], r64[name], rtol=1e-3, atol=1e-3, unit=float(r64[name].abs().max()))
-    bars.check()
+    C.check_bf16_e2e_head(EMU, 48, 128)
+
+
+def test_bf16_wide_e2e_head_off_grid_width():
+    """mode 1 (K = B, the grad_mem product) at D = 65 with B = 40"""
+    C.check_bf16_e2e_head(EMU, 40, 65)
 
 
 def test_fused_wide_step_bf16_encoder_and_head_vs_rounded_oracle():
@@ -270,25 +120,7 @@ def test_fused_wide_step_bf16_encoder_and_head_vs_rounded_oracle():
     2): every kind of bf16 product runs -- z1 with k = 49, z2, d a1, d agg, dW1 and dW0 over the node dimension, the head's three --
     while the rule's own fp32-vs-float64 gap stays near the f32 bars, so the comparison keeps its resolution (each further layer
     multiplies that gap: see the module docstring)."""
-    hidden, layers, K = 128, 2, 96
-    torch.manual_seed(128)
-    model, ema = wide_encoder(hidden, hidden, layers, encoder_dtype="bf16"), wide_encoder(hidden, hidden, layers, encoder_dtype="bf16")
-    ema.load_state_dict(model.state_dict())
-    model._wide_engine = ema._wide_engine = emu_wide_engine()
-    contrast = MemoryMoCo(hidden, None, K, 0.07, use_softmax=True, nce_dtype="bf16")
-    contrast._engine = emu_wide_nce()
-
-    class _Views:
-        batch_size = B
-
-        def sample(self, first_id, prof=None):
-            return fixed_views()
-
-    tr = MoCoTrainStep(model, ema, contrast, _Views(), posemb=lambda gr: gr, prefetch=False, flat_engine=emu_nce())
-    assert tr.wide and not tr.use_graph and tr.nce.dtype == "bf16"
-    masks = (torch.rand(layers, B, hidden, generator=torch.Generator().manual_seed(4)) >= 0.5).float().contiguous()
-    rep = check_wide_bf16_moco_step(tr, model, ema, contrast, 0.004, masks, step_id=0)
-    print("fused bf16 step: " + rep["bars"].summary())
+    C.check_bf16_fused_step(EMU)
 
 
 def test_refusals():

@@ -6,10 +6,10 @@ import pytest
 import torch
 
 from gcc_amd.encoder import GraphEncoder
-from gcc_amd.encoder_wide import WideGinEngine
 from oracle import encoder as E
-from tests.hipemu.emu_driver import emu_lib
-from tests.test_headline_step_emu import B, OracleSampler
+from tests import wide_edges_check as C
+from tests.test_headline_step_emu import B  # noqa: F401
+from tests.wide_edges_check import EMU, check_against_oracle, fixed_views  # noqa: F401  (names other test files import from here)
 
 
 def wide_encoder(hidden, out, layers=5):
@@ -20,83 +20,12 @@ def wide_encoder(hidden, out, layers=5):
 
 
 def emu_wide_engine():
-    return WideGinEngine(lib=emu_lib(), ptr=lambda t: 0 if t is None else t.data_ptr())
-
-
-def fixed_views():
-    """The sampled batch of the headline tests with a REPRODUCIBLE positional embedding: OracleSampler's comes from SciPy ARPACK, whose
-    output differs from call to call (the degenerate eigenspaces of small ego-nets), and with ~2 M pre-activations per pass an input
-    now and then puts one of them within fp32 rounding of a ReLU kink -- then ANY two fp32 implementations may disagree on that
-    element's mask and its whole upstream gradient (seen: 1e-2 of a gradient's scale, one element with |y| < 1e-6 in float64).  Unit rows
-    from a seeded generator keep the test's inputs, and so its verdict, the same on every run."""
-    q, k = OracleSampler().views
-    for v, seed in ((q, 11), (k, 12)):
-        x = torch.randn(v.pos_undirected.shape, generator=torch.Generator().manual_seed(seed))
-        v.pos_undirected = torch.nn.functional.normalize(x, dim=1)
-    return q, k
-
-
-def check_against_oracle(model, oracle, q, keep, out, hidden, monkeypatch, rtol=2e-4):
-    monkeypatch.setattr(torch, "rand", lambda *a, **k: keep.clone())       # the API path draws its dropout masks here
-    feat, pooled = model(q, return_all_outputs=True)
-    assert tuple(feat.shape) == (B, out) and all(tuple(t.shape) == (B, hidden) for t in pooled)
-    n = q.n
-    args = (q.node_off.long(), q.row_ptr[: n + 1].long(), q.col_idx.long(), q.pos_undirected[:n])
-    ref, ref_pooled = oracle(*args, dropout_masks=keep, return_all_outputs=True)
-    torch.testing.assert_close(feat, ref, rtol=rtol, atol=2e-5)
-    for a, b in zip(pooled, ref_pooled):
-        torch.testing.assert_close(a, b, rtol=rtol, atol=2e-4)
-    d = torch.randn(B, out)
-    feat.backward(d)
-    ref.backward(d)
-    refg = dict(oracle.named_parameters())
-    # the binding reference for the gradients is the same model in float64: a weight gradient sums thousands of terms that largely cancel,
-    # so two fp32 implementations (the kernels, torch's) differ from each other by what each is off from float64.  The bar: 1e-3 of the
-    # tensor's largest entry against the float64 run (north_star), no allowance for fp32
-    import copy
-    o64 = copy.deepcopy(oracle).double()
-    o64.zero_grad()
-    r64 = o64(args[0], args[1], args[2], args[3].double(), dropout_masks=keep.double(), return_all_outputs=True)[0]
-    r64.backward(d.double())
-    ref64 = dict(o64.named_parameters())
-    for name, p in model.named_parameters():
-        if refg[name].grad is None:
-            assert p.grad is None or float(p.grad.abs().sum()) == 0.0, name
-            continue
-        assert p.grad.shape == p.shape
-        g64 = ref64[name].grad.float()
-        scale = max(float(g64.abs().max()), 1e-3)
-        torch.testing.assert_close(p.grad, g64, rtol=0, atol=1e-3 * scale, msg=lambda m, name=name: f"{name}: {m}")
-    return args
+    return EMU.wide_engine()
 
 
 @pytest.mark.parametrize("hidden,out,layers", [(128, 128, 5), (96, 80, 3), (256, 256, 5), (72, 40, 2)])
 def test_wide_api_path_forward_backward_vs_oracle(hidden, out, layers, monkeypatch):
-    torch.manual_seed(hidden * 100 + out)
-    model = wide_encoder(hidden, out, layers)
-    assert model.wide and not model.is_padded()
-    oracle = E.OracleGraphEncoder(node_hidden_dim=hidden, output_dim=out, num_layers=layers)
-    assert {k: tuple(v.shape) for k, v in model.state_dict().items()} == {k: tuple(v.shape) for k, v in oracle.state_dict().items()}
-    oracle.load_state_dict(model.state_dict())
-    model._wide_engine = emu_wide_engine()
-    model.train()
-    oracle.train()
-    q, _ = fixed_views()
-    keep = (torch.rand(layers, B, out) >= 0.5).float()
-    args = check_against_oracle(model, oracle, q, keep, out, hidden, monkeypatch)
-    # running statistics moved exactly as torch's BatchNorm1d moves them (momentum 0.1, unbiased variance)
-    for (k1, v1), (k2, v2) in zip(model.state_dict().items(), oracle.state_dict().items()):
-        if "running_" in k1 or "num_batches" in k1:
-            torch.testing.assert_close(v1, v2, rtol=1e-4, atol=1e-5, msg=lambda m, k=k1: f"{k}: {m}")
-    # the state survives a save / load round trip, and eval mode (running statistics, no dropout) agrees too
-    m2 = wide_encoder(hidden, out, layers)
-    m2.load_state_dict({k: v.clone() for k, v in model.state_dict().items()})
-    m2._wide_engine = emu_wide_engine()
-    m2.eval()
-    oracle.eval()
-    with torch.no_grad():
-        torch.testing.assert_close(m2(q), oracle(*args), rtol=2e-4, atol=2e-5)
-        torch.testing.assert_close(m2.embed_views(q, q), oracle(*args), rtol=2e-4, atol=2e-5)
+    C.check_api_path(EMU, hidden, out, layers, monkeypatch)
 
 
 def test_the_fused_engine_refuses_a_wide_model():
@@ -106,9 +35,7 @@ def test_the_fused_engine_refuses_a_wide_model():
 
 
 def emu_wide_nce():
-    from gcc_amd.contrast import WideNceEngine
-
-    return WideNceEngine(lib=emu_lib(), ptr=lambda t: 0 if t is None else t.data_ptr())
+    return EMU.wide_nce()
 
 
 @pytest.mark.parametrize("D,K", [(128, 96), (80, 200), (256, 64), (96, 4400)])    # (K >= 4096: the split reduction of d loss / d q)

@@ -1,8 +1,10 @@
-"""Device tier of tests/test_wide_edges_emu.py: the fused any-width step (MoCoTrainStep._body over csrc/ginx.hip and the dense
-head) at --hidden-size 256 on a device-sampled batch -- G1 (1M nodes / 10M edges), bsz 256, rw_hops 256, K 16384, positional
-embedding by the device eigensolvers -- against oracle/encoder.py fed the same batch, dropout masks, weights, Adam moments and
-queue, in fp32 and in float64 (tests/wide_step_check.py).  At ~25 k live rows per view every weight gradient spans many 1,024-row
-slabs, and the checked step is the second, so rows past its live count hold whatever the first step's batch left there."""
+"""The fused any-width step (MoCoTrainStep._body over csrc/ginx.hip and the dense head) at --hidden-size 256 on a device-sampled
+batch -- G1 (1M nodes / 10M edges), bsz 256, rw_hops 256, K 16384, positional embedding by the device eigensolvers -- against
+oracle/encoder.py fed the same batch, dropout masks, weights, Adam moments and queue, in fp32 and in float64
+(tests/wide_step_check.py).  At ~25 k live rows per view every weight gradient spans many 1,024-row slabs, and the checked step
+is the second, so rows past its live count hold whatever the first step's batch left there.  The shape edges of the same kernels
+(off-grid widths, partial tiles, stale rows in a hand-built batch, the head around its split) run on the device in
+tests/test_wide_edges_gpu.py, the device tier of tests/test_wide_edges_emu.py."""
 import pytest
 import torch
 

@@ -1,7 +1,7 @@
 """Shared body of the fused any-width step checks: ONE ``MoCoTrainStep.step`` at --hidden-size above 64 (``_body`` on csrc/ginx.hip
 forward of both views, the dense head, the backward, clip + Adam + EMA + meters, the enqueue) against oracle/encoder.py built with
 the model's own widths, layer count and degree table, fed the same batch, dropout masks, weights, Adam moments and queue -- in fp32
-and in float64.  Used by the emulator tier at the edges (tests/test_wide_edges_emu.py) and by the device tier on a sampled batch
+and in float64.  Used by both tiers at the edges (tests/wide_edges_check.py) and by the device tier on a sampled batch
 (tests/test_wide_step_gpu.py).  TEST INFRASTRUCTURE ONLY.
 
 The bar for gradients is north_star's: 1e-3 of the tensor's largest entry against the float64 run, with no allowance for fp32
