@@ -92,6 +92,19 @@ constexpr float kZeroEig = 1e-5f;    // |lambda| below this is "the null space" 
 // sqrt(s).  The +1/sqrt(2) copies usually ARE among the top 32, so their contrasts (the same Helmert basis as for twin
 // leaves, over the stalks of a hub in index order) are merged into the ranking by value.  Twin leaves and stalks never
 // overlap: a stalk's middle node has exactly one leaf, a hub of >= 2 stalks has >= 2 non-leaf neighbours.
+//
+// ---- multigraphs.  Parallel edges are repeated, adjacent entries of a sorted row (DGL's representation), symmetric with equal
+// copy counts; d = row length is the multigraph's degree and M(i, j) = copies(i, j) / sqrt(d_i d_j).  Both rules above hold
+// unchanged when "degree" is read as ROW LENGTH, because a row of one entry has one neighbour joined by ONE edge:
+//   twin leaf   = a row of exactly one entry.  Its parent's row holds it exactly once (equal copy counts), so its coupling is
+//                 1 / sqrt(1 * d_p) whatever else the parent's row repeats, and t of them are interchangeable as before.
+//   stalk       = a row of two entries with DIFFERENT columns, exactly one of which is such a leaf: both of its edges are
+//                 single, a - b is 1/sqrt(2) and a - h is 1/sqrt(2 d_h).  A look-alike whose hub edge is doubled has a row of
+//                 three entries; a node tied to its only neighbour by two edges has a row of two EQUAL columns, whose
+//                 "leaf" flags agree, so it is neither leaf nor stalk and stays in the quotient with its copies counted.
+// A hub's row may repeat its other neighbours: defl_order_node numbers group members only (each occurs once in the row), the
+// classify kernel's size n' and defl_record read rows of one or two entries only, and the expansion never looks at a row.
+// The dense classes' matrix assembly is the one place that counts copies (posemb_direct_kernel's fill loop, fill_multigraph_by_entry).
 struct Defl {
     int32_t *tcnt, *cbase, *pcnt;       // [cap] leaves per parent | contrast bases: twin groups (low 16 bits), stalk groups (high 16) | stalks per hub
     uint16_t *par, *rep, *ridx, *ord;   // [cap] parent of a leaf | first leaf of a parent | reduced index | order inside the group
@@ -212,6 +225,34 @@ __device__ __forceinline__ float defl_coupling(const Defl &d, int i, int j)
     else if (d.phub[j] == (uint16_t)i && d.pcnt[i] >= 2) f = sqrtf((float)d.pcnt[i]);
     else if (d.phub[i] == (uint16_t)j && d.pcnt[j] >= 2) f = sqrtf((float)d.pcnt[j]);
     return f;
+}
+// ---- the dense classes' matrix M' = norm * adj * norm of a MULTIGRAPH item (work-list entry tagged kItemCopies): the entry of
+// a kept pair is copies(i, j) x coupling / sqrt(d_i d_j), d = row length.  Rows are sorted, so the copies of an edge are
+// adjacent: the first entry of a run counts its run and writes once -- no float atomics, nothing depends on lane order, and a
+// run of one writes the float the simple loop writes (x 1.0f is exact).  Simple graphs are the hot path and an item counts runs
+// only when the classify kernel found a repeated entry.  posemb_direct_kernel does so inside its one fill loop, behind a
+// workgroup-uniform branch: that form leaves every instantiation with the registers it had and no more scratch (a second loop
+// cost the register-capped four-wave kernel 36 more bytes of spills per lane, an out-of-line call every dense kernel 80 bytes of
+// scratch).  The one-wave teams fill by entry, four entries per lane in flight; there the second loop is the cheaper form:
+// (one lane per entry; rpl = the row pointers rebased to the subgraph's first entry, col = the subgraph's E column ids)
+__device__ __forceinline__ void fill_multigraph_by_entry(const Defl &d, const int32_t *rpl, const int32_t *col, int n0, int n,
+                                                          int E, float *A, int lda, int lane)
+{
+    for (int e = lane; e < E; e += 64) {
+        const int j = col[e] - n0;
+        int lo = 0, hi = n;                          // largest i with rpl[i] <= e
+        while (hi - lo > 1) {
+            const int mid = (lo + hi) >> 1;
+            if (rpl[mid] <= e) lo = mid; else hi = mid;
+        }
+        const int i = lo;
+        if (e > rpl[i] && col[e - 1] - n0 == j) continue;
+        if (d.ridx[i] == kNone || d.ridx[j] == kNone) continue;
+        int c = 1;
+        while (e + c < rpl[i + 1] && col[e + c] - n0 == j) ++c;
+        const int di = rpl[i + 1] - rpl[i], dj = rpl[j + 1] - rpl[j];
+        A[d.ridx[i] * lda + d.ridx[j]] = defl_coupling(d, i, j) / sqrtf((float)di * (float)dj) * (float)c;
+    }
 }
 // what the expansion needs of the tables, 8 bytes per node: quotient row | order inside the group | group size (0 = not
 // grouped; bit 15 = stalk member, bit 14 = the stalk's leaf) | contrast base of the group
@@ -347,6 +388,10 @@ enum { kClsSmall = 0, kClsMid = 1, kClsSlot = 2, kClsKrylov = 3, kClsBig = 4, kC
 constexpr int kWaveNodes = 256;
 constexpr int kWaveTeams = 4;        // teams (waves) per workgroup
 static_assert(kNumCls == GCC_POSEMB_TICK_CLASSES, "include/gcc_amd.h: tick buffer classes");
+// A work-list entry is the item id, with kItemCopies set when the item's CSR holds parallel edges (two equal neighbours
+// inside a row: the classify kernel looks once).  Only then do the dense classes count runs while they assemble the matrix; an
+// item without the bit takes the loop that writes one coupling per entry, so simple graphs do not pay for multigraphs.
+constexpr int kItemCopies = 1 << 30, kItemMask = kItemCopies - 1;
 constexpr int kTabFloats = kNodeMax * 4;   // a workgroup's per-node table in the workspace, 16 bytes per node (defl_record fills the first 8)
 struct PosHead {                     // head of the caller's workspace (its first 64 bytes are zeroed per call) and the regions of PosWorkLayout
     int32_t *count;                  // [kNumCls] items per class
@@ -1678,6 +1723,7 @@ __global__ __launch_bounds__(kClsThreads) void posemb_classify_kernel(PosMulti m
         return;
     }
     int cls = kClsKrylov;
+    bool copies = false;
     if (n <= kNodeMax) {
         const int32_t *rp = a.row_ptr + n0;
         int32_t *t = tc[wv];
@@ -1701,6 +1747,17 @@ __global__ __launch_bounds__(kClsThreads) void posemb_classify_kernel(PosMulti m
         }
         for (int dd = 32; dd >= 1; dd >>= 1) zz += wave_shfl_xor(zz, dd);
         const int nr = n - zz;                         // t >= 2 leaves of one parent count once, s >= 2 stalks of one hub as one stalk
+        // parallel edges?  Equal neighbours among the item's entries (one coalesced pass) minus those that straddle two rows
+        // (the last entry of one row, the first of the next non-empty one: common in star-like ego-nets) = equal pairs INSIDE rows
+        const int e0 = rp[0], E = rp[n] - e0;
+        int dup = 0;
+        for (int e = 1 + lane; e < E; e += 64) dup += a.col_idx[e0 + e] == a.col_idx[e0 + e - 1];
+        for (int i = lane; i < n; i += 64) {
+            const int r = rp[i];
+            if (r > e0 && rp[i + 1] > r) dup -= a.col_idx[r] == a.col_idx[r - 1];
+        }
+        for (int dd = 32; dd >= 1; dd >>= 1) dup += wave_shfl_xor(dup, dd);
+        copies = dup > 0;
         cls = (hd.use_wave && nr <= 64 && n <= kWaveNodes) ? (nr <= 48 ? kClsW48 : kClsW64)
             : nr <= kJSmall ? kClsSmall : nr <= kJMax ? kClsMid : hd.use_cheb ? kClsCheb : nr <= kGMax ? kClsSlot : nr <= kBMax ? kClsBig : kClsKrylov;
     }
@@ -1710,7 +1767,7 @@ __global__ __launch_bounds__(kClsThreads) void posemb_classify_kernel(PosMulti m
         if (lane == 0) atomicOr(a.status, (int32_t)GCC_STATUS_POSEMB_TOO_LARGE);
         return;
     }
-    if (lane == 0) hd.list[(int64_t)cls * hd.T + atomicAdd(hd.count + cls, 1)] = item;
+    if (lane == 0) hd.list[(int64_t)cls * hd.T + atomicAdd(hd.count + cls, 1)] = item | (copies ? kItemCopies : 0);
 }
 
 // ---- work lists, largest first.  The class kernels' workgroups pull items off their list with an atomic counter; the classify
@@ -1734,7 +1791,7 @@ __global__ __launch_bounds__(kSortThreads) void posemb_sort_kernel(PosMulti m, P
         const int gb = list[i];
         PosArgs a;
         int b;
-        item_args(m, gb, a, b);
+        item_args(m, gb & kItemMask, a, b);
         const int n = a.node_off[b + 1] - a.node_off[b];
         const int key = n < kSortBins ? n : kSortBins - 1;
         items[i] = gb;
@@ -1814,7 +1871,9 @@ __global__ __launch_bounds__(kT, kPair ? GCC_POSEMB_QUAD_OCC : 1) void posemb_di
     if (tid == 0) sh_item = atomicAdd(hd.next + kCls, 1);
     __syncthreads();
     if (sh_item >= hd.count[kCls]) return;
-    const int gb = hd.list[(int64_t)kCls * hd.T + sh_item];
+    const int entry = hd.list[(int64_t)kCls * hd.T + sh_item];
+    const int gb = entry & kItemMask;
+    const bool copies = (entry & kItemCopies) != 0;     // workgroup-uniform
     PosArgs a;
     int b;
     item_args(m, gb, a, b);
@@ -1869,10 +1928,18 @@ __global__ __launch_bounds__(kT, kPair ? GCC_POSEMB_QUAD_OCC : 1) void posemb_di
         const int ri = d.ridx[i];
         const int di = rp[i + 1] - rp[i];
         for (int e = rp[i] + lane; e < rp[i + 1]; e += 64) {
-            const int j = a.col_idx[e] - n0;
+            const int cj = a.col_idx[e];
+            const int j = cj - n0;
             if (d.ridx[j] == kNone) continue;
             const int dj = rp[j + 1] - rp[j];
-            A[ri * lda + d.ridx[j]] = defl_coupling(d, i, j) / sqrtf((float)di * (float)dj);   // in_degrees().clip(1) ** -0.5 on both sides
+            float v = defl_coupling(d, i, j) / sqrtf((float)di * (float)dj);   // in_degrees().clip(1) ** -0.5 on both sides
+            if (__builtin_expect(copies, 0)) {     // (workgroup-uniform, rare) parallel edges: the first entry of a run writes copies x coupling
+                if (e > rp[i] && a.col_idx[e - 1] == cj) continue;
+                int c = 1;
+                while (e + c < rp[i + 1] && a.col_idx[e + c] == cj) ++c;
+                v *= (float)c;
+            }
+            A[ri * lda + d.ridx[j]] = v;
         }
     }
     // what the expansion at the end needs of the tables: 8 bytes per node, in the workgroup's table in the workspace
@@ -1979,7 +2046,9 @@ __global__ __launch_bounds__(kWaveTeams * 64, kNMax <= 48 ? GCC_POSEMB_W48_OCC :
     if (lane == 0) item = atomicAdd(hd.next + kCls, 1);
     item = wave_bcast_first(item);
     if (item >= hd.count[kCls]) return;
-    const int gb = hd.list[(int64_t)kCls * hd.T + item];
+    const int entry = hd.list[(int64_t)kCls * hd.T + item];
+    const int gb = entry & kItemMask;
+    const bool copies = (entry & kItemCopies) != 0;     // wave-uniform
     PosArgs a;
     int b;
     item_args(m, gb, a, b);
@@ -2032,6 +2101,9 @@ __global__ __launch_bounds__(kWaveTeams * 64, kNMax <= 48 ? GCC_POSEMB_W48_OCC :
         for (int i = lane; i <= n; i += 64) rpl[i] = rp[i] - e0;
         wave_sync();
         const int E = rpl[n];
+        if (__builtin_expect(copies, 0)) {           // (wave-uniform, rare) parallel edges: copies x coupling
+            fill_multigraph_by_entry(d, rpl, a.col_idx + e0, n0, n, E, A, lda, lane);
+        } else
         for (int eb = 0; eb < E; eb += 4 * 64) {
             int jj[4];
 #pragma unroll
@@ -2187,7 +2259,7 @@ __global__ __launch_bounds__(kKThreads) void posemb_krylov_kernel(KryArgs ka)
     if (tid == 0) sh_item = atomicAdd(ka.hd.next + kClsKrylov, 1);
     __syncthreads();
     if (sh_item >= ka.hd.count[kClsKrylov]) return;
-    const int gb = ka.hd.list[(int64_t)kClsKrylov * ka.hd.T + sh_item];
+    const int gb = ka.hd.list[(int64_t)kClsKrylov * ka.hd.T + sh_item] & kItemMask;
     PosArgs a;
     int b;
     item_args(ka.m, gb, a, b);
@@ -2620,7 +2692,7 @@ __global__ __launch_bounds__(kChThreads) GCC_CHEB_REG_CAP void posemb_cheb_kerne
     uint32_t tid_ = threadIdx.x;
     opaque_u32(tid_);
     const int tid = (int)tid_, lane = tid & 63, wv = tid >> 6;
-    const int gb = hd.list[(int64_t)kCls * hd.T + sh_item];
+    const int gb = hd.list[(int64_t)kCls * hd.T + sh_item] & kItemMask;
     PosArgs a;
     int b;
     item_args(m, gb, a, b);
@@ -3439,7 +3511,10 @@ __global__ __launch_bounds__(kChThreads) GCC_CHEB_REG_CAP void posemb_cheb_kerne
                 atomicOr(a.status, (int32_t)GCC_STATUS_POSEMB_TOO_LARGE);
                 cls = -1;
             }
-            if (cls >= 0) hd.list[(int64_t)cls * hd.T + atomicAdd(hd.count + cls, 1)] = gb;
+            if (cls >= 0) hd.list[(int64_t)cls * hd.T + atomicAdd(hd.count + cls, 1)] = gb | kItemCopies;
+            // (A deliberate choice, not a free one: this kernel drops the tag when it masks its entry -- its register and scratch
+            //  footprint is pinned -- so every item it hands on takes the counting fill, which is right for either kind of item
+            //  and a few percent slower in the matrix phase for a simple one.  Handed-on items are rare: status word 3 counts them.)
             atomicAdd(a.status + 3, 1);                          // diagnostics: items that left their first-choice solver
             sh_fail = cls < 0 ? 2 : 1;
         }

@@ -159,10 +159,15 @@ class DeviceGraphCorpus:
 class NodeClassificationDataset:
     def __init__(self, dataset=None, rw_hops=64, subgraph_size=64, restart_prob=0.8, positional_embedding_size=32,
                  step_dist=(1.0, 0.0, 0.0), graph=None, edge_multiplicity=2, batch_size=256, run_seed=0,
-                 device="cuda", sample_fn=None):
+                 device="cuda", sample_fn=None, multigraph=False):
         """``graph`` = (row_ptr, col_idx) of the SIMPLE symmetric graph; ``edge_multiplicity`` = copies of every edge in
         the reference's DGL graph (gcc_amd.ingest.read_edgelist reports it).  ``sample_fn(first_id, seeds) -> (q, k)``
-        is injectable for the emulator tests."""
+        is injectable for the emulator tests.
+        ``multigraph``: ``graph`` holds parallel edges as repeated entries of its sorted rows (gcc_amd.ingest.multigraph_csr,
+        read_ss_graph(csr=True)) and ``edge_multiplicity`` is only the uniform factor on top (the 2 of the reference's
+        double insertion).  The row lengths are then the multigraph's degrees, so the out-degree rule below
+        (graph_dataset.py:244-255) needs nothing else; the flag goes to DeviceGraph, which validates the multigraph contract
+        and keeps the induction scanning every row."""
         if list(step_dist) != [1.0, 0.0, 0.0]:
             raise NotImplementedError("step_dist other than [1, 0, 0] (generate.py and train.py never pass one)")
         assert positional_embedding_size > 1                       # graph_dataset.py:290
@@ -174,6 +179,7 @@ class NodeClassificationDataset:
         self.step_dist = list(step_dist)
         self.edge_multiplicity = int(edge_multiplicity)
         self.batch_size = int(batch_size)
+        self.multigraph = bool(multigraph)
         row_ptr, col_idx = graph
         self.length = int(len(row_ptr) - 1)                        # one item per node, :293
         self.total = self.length
@@ -184,7 +190,7 @@ class NodeClassificationDataset:
             from .sampler import DeviceRWRSampler
 
             self.graph = DeviceGraph(row_ptr, col_idx, rw_hops=rw_hops, restart_prob=restart_prob, device=device,
-                                     ltab=self.ltab)
+                                     ltab=self.ltab, multigraph=self.multigraph)
             self.sampler = DeviceRWRSampler(self.graph, self.batch_size, run_seed=run_seed)
             self._sample = self._device_sample
 

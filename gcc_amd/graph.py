@@ -12,7 +12,7 @@ import math
 import numpy as np
 
 from . import _cabi
-from .graphgen import check_contract
+from .graphgen import check_contract, check_multigraph_contract
 
 
 def seed_cdf_table(row_ptr: np.ndarray, shard_off=None) -> np.ndarray:
@@ -94,18 +94,23 @@ class DeviceGraph:
 
     def __init__(self, row_ptr: np.ndarray, col_idx: np.ndarray, rw_hops: int = 256,
                  restart_prob: float = 0.8, device="cuda", validate: bool = True, ltab: np.ndarray = None,
-                 shard_off=None, trusted: bool = False, hub_table: bool = True):
+                 shard_off=None, trusted: bool = False, hub_table: bool = True, multigraph: bool = False):
         """``validate``: check the input contract (x2dgl.py:39-62) on the host before the upload.  ``trusted``: the caller
         vouches for the contract without the check (graphs of gcc_amd.graphgen, whose generator builds to it).  With
         neither, the graph carries no GCC_GRAPH_CONTRACT_CHECKED bit and the induction scans every member row (the hub-row
-        short cut of gcc_sample_params.hub_degree is exact on a symmetric, sorted, duplicate- and loop-free parent only)."""
+        short cut of gcc_sample_params.hub_degree is exact on a symmetric, sorted, duplicate- and loop-free parent only).
+        ``multigraph``: the parent may hold parallel edges as repeated, adjacent entries of its sorted rows (DGL's
+        representation; ``ingest.multigraph_csr``).  It is validated against ``check_multigraph_contract`` and, checked or
+        trusted, never carries GCC_GRAPH_CONTRACT_CHECKED and gets no hub tables: a uniform draw over a row's entries is
+        the walk on the multigraph and the row-by-row induction emits every copy, but the short cut would not."""
         import torch
 
         row_ptr = np.ascontiguousarray(row_ptr, dtype=np.int32)
         col_idx = np.ascontiguousarray(col_idx, dtype=np.int32)
         if validate:
-            check_contract(row_ptr, col_idx)
-        self.contract_checked = bool(validate or trusted)
+            (check_multigraph_contract if multigraph else check_contract)(row_ptr, col_idx)
+        self.multigraph = bool(multigraph)
+        self.contract_checked = bool(validate or trusted) and not self.multigraph
         self.device = torch.device(device)
         if self.device.type != "cuda":
             raise RuntimeError("DeviceGraph lives in HBM; device must be a HIP/CUDA device")
@@ -118,6 +123,15 @@ class DeviceGraph:
         self.max_degree = int(deg.max())
         d64 = deg.astype(np.float64)
         self.sb_degree = float((d64 * d64).sum() / d64.sum())   # size-biased mean degree: what a random-walk visit sees
+        # most parallel edges between one pair: an induced row of a multigraph can hold up to (n - 1) x this many entries
+        # (DeviceRWRSampler sizes its edge capacity with it; 1 on a simple parent)
+        self.max_copies = 1
+        if self.multigraph and len(col_idx) > 1:
+            new_run = np.ones(len(col_idx), dtype=bool)
+            new_run[1:] = col_idx[1:] != col_idx[:-1]
+            starts = row_ptr[:-1]
+            new_run[starts[starts < len(col_idx)]] = True      # (an unchecked parent may end in empty rows)
+            self.max_copies = int(np.diff(np.append(np.flatnonzero(new_run), len(col_idx))).max())
         if ltab is None:
             ltab = max_nodes_per_seed_table(self.max_degree, rw_hops, restart_prob)
         ltab = np.ascontiguousarray(ltab, dtype=np.int32)

@@ -156,3 +156,32 @@ def check_contract(row_ptr: np.ndarray, col_idx: np.ndarray) -> None:
         raise ValueError("duplicate edge present (x2dgl.py:52-54)")
     if (a != a.T).nnz != 0:
         raise ValueError("graph is not symmetric (x2dgl.py:43-47)")
+
+
+def check_multigraph_contract(row_ptr: np.ndarray, col_idx: np.ndarray) -> None:
+    """Raise ValueError unless the CSR is a multigraph parent the sampler can walk: parallel edges are REPEATED entries
+    of a row, rows are sorted non-decreasing (so the copies of an edge are adjacent), there are no self loops and no
+    empty rows, every pair has the same number of copies in both directions, and all sizes fit int32.  ``check_contract``
+    is this plus "no repeated entry"; only that stricter contract allows the induction's hub-row short cut."""
+    v = row_ptr.shape[0] - 1
+    if v >= 2 ** 31 or col_idx.shape[0] >= 2 ** 31:
+        raise ValueError("node and entry counts must fit int32")
+    if row_ptr[0] != 0 or row_ptr[-1] != col_idx.shape[0]:
+        raise ValueError("row_ptr does not span col_idx")
+    deg = np.diff(np.asarray(row_ptr, dtype=np.int64))
+    if (deg <= 0).any():
+        raise ValueError("zero-degree node: the reference removes them (x2dgl.py:61) "
+                         "and DGL's walker aborts on them")
+    col = np.asarray(col_idx, dtype=np.int64)
+    if col.min() < 0 or col.max() >= v:
+        raise ValueError("col_idx out of range")
+    rows = np.repeat(np.arange(v, dtype=np.int64), deg)
+    inner = np.ones(len(col), dtype=bool)                   # entries that have a predecessor in their row
+    inner[np.asarray(row_ptr[:-1], dtype=np.int64)] = False
+    if (np.diff(col)[inner[1:]] < 0).any():
+        raise ValueError("rows must be sorted (non-decreasing: the copies of a parallel edge are adjacent)")
+    if (rows == col).any():
+        raise ValueError("self loop present (x2dgl.py:41-42)")
+    # sorted rows make the forward keys ascending; the multiset of (col, row) must be the same multiset
+    if not np.array_equal(rows * v + col, np.sort(col * v + rows)):
+        raise ValueError("graph is not symmetric with equal copy counts in both directions (x2dgl.py:43-47)")

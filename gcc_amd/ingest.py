@@ -5,8 +5,10 @@ one "u v" pair per line, node ids re-indexed in order of first appearance; "node
 inserts every pair in both directions (data_util.py:84-85) and its dataset class inserts both directions AGAIN
 (graph_dataset.py:301-302), so its DGL graph is a multigraph in which every undirected edge of the file exists
 ``2 x (times the pair is listed, in either order)`` times per direction.  The HIP path keeps a simple CSR plus ONE
-uniform multiplicity (gcc_gin_pass.edge_multiplicity); files whose pairs repeat a non-uniform number of times, and self
-loops, are rejected rather than approximated.
+uniform multiplicity (gcc_gin_pass.edge_multiplicity); self loops are rejected, and so are files whose pairs repeat a
+non-uniform number of times unless the caller asks for a multigraph: then every listing is its own parallel edge, a
+repeated entry of a sorted CSR row (``multigraph_csr``), and only the uniform factor of the double insertion stays in
+``edge_multiplicity``.
 
 ``read_ss_graph``: the ``<name>.graph`` / ``<name>.dict`` pairs of the similarity-search task (data_util.py:145-191).
 
@@ -19,6 +21,10 @@ from __future__ import annotations
 import numpy as np
 
 
+class NonUniformMultiplicity(ValueError):
+    """pairs of an edge list are listed a non-uniform number of times (``csr_from_pairs`` keeps ONE multiplicity)"""
+
+
 def csr_from_pairs(pairs: np.ndarray, num_nodes: int):
     """pairs int64 [m, 2] (undirected, any order, repeats allowed) -> (row_ptr, col_idx, multiplicity)."""
     if (pairs[:, 0] == pairs[:, 1]).any():
@@ -26,7 +32,7 @@ def csr_from_pairs(pairs: np.ndarray, num_nodes: int):
     lo, hi = pairs.min(axis=1), pairs.max(axis=1)
     key, counts = np.unique(lo * num_nodes + hi, return_counts=True)
     if counts.min() != counts.max():
-        raise ValueError("pairs repeat a non-uniform number of times: a general multigraph is not supported")
+        raise NonUniformMultiplicity("pairs repeat a non-uniform number of times: a general multigraph is not supported")
     u, v = key // num_nodes, key % num_nodes
     src = np.concatenate([u, v])
     dst = np.concatenate([v, u])
@@ -40,9 +46,41 @@ def csr_from_pairs(pairs: np.ndarray, num_nodes: int):
     return row_ptr.astype(np.int32), dst.astype(np.int32), int(counts[0])
 
 
-def read_edgelist(edgelist_path: str, nodelabel_path: str = None, hindex: bool = False):
-    """-> dict(row_ptr, col_idx, edge_multiplicity, node2id, y).  ``edge_multiplicity`` is the number of copies of
-    every edge in the graph the reference's NodeClassificationDataset builds (2 x listings)."""
+def multigraph_csr(pairs: np.ndarray, weights: np.ndarray, num_nodes: int):
+    """pairs int64 [m, 2] (undirected, any order; a pair may be listed more than once, its weights add up), weights int64 [m]
+    (>= 1: parallel edges of the pair) -> (row_ptr, col_idx) int32 of the MULTIGRAPH: both directions, every parallel edge
+    its own entry, rows sorted -- so the copies of a pair are adjacent (DGL's representation; what the sampler walks, the
+    positional embedding counts and the encoders sum).  Only nodes with an edge may have an index below ``num_nodes``."""
+    pairs = np.asarray(pairs, dtype=np.int64).reshape(-1, 2)
+    weights = np.asarray(weights, dtype=np.int64).reshape(-1)
+    if len(weights) != len(pairs):
+        raise ValueError(f"{len(pairs)} pairs but {len(weights)} weights")
+    if len(pairs) == 0:
+        raise ValueError("no edges")
+    if (weights < 1).any():
+        raise ValueError("edge weights must be positive integers (the number of parallel edges)")
+    if (pairs[:, 0] == pairs[:, 1]).any():
+        raise ValueError("self loops are not supported by the sampler contract (x2dgl.py:41-42 removes them)")
+    if pairs.min() < 0 or pairs.max() >= num_nodes:
+        raise ValueError("node index out of range")
+    if 2 * int(weights.sum()) >= 2 ** 31:
+        raise ValueError("the expanded multigraph does not fit int32 entry offsets")
+    src = np.repeat(np.concatenate([pairs[:, 0], pairs[:, 1]]), np.concatenate([weights, weights]))
+    dst = np.repeat(np.concatenate([pairs[:, 1], pairs[:, 0]]), np.concatenate([weights, weights]))
+    order = np.lexsort((dst, src))
+    src, dst = src[order], dst[order]
+    row_ptr = np.zeros(num_nodes + 1, dtype=np.int64)
+    np.cumsum(np.bincount(src, minlength=num_nodes), out=row_ptr[1:])
+    if (np.diff(row_ptr) == 0).any():
+        raise ValueError("isolated nodes (every node of the CSR needs an edge; check the input)")
+    return row_ptr.astype(np.int32), dst.astype(np.int32)
+
+
+def read_edgelist(edgelist_path: str, nodelabel_path: str = None, hindex: bool = False, multigraph: bool = False):
+    """-> dict(row_ptr, col_idx, edge_multiplicity, node2id, y[, multigraph]).  ``edge_multiplicity`` is the number of copies of
+    every edge in the graph the reference's NodeClassificationDataset builds (2 x listings).  ``multigraph``: pairs
+    listed a NON-uniform number of times are expanded into repeated CSR entries (``multigraph_csr``: one parallel edge per
+    listing) and ``edge_multiplicity`` is the 2 of the double insertion; uniformly listed files come out as without it."""
     node2id, pairs = {}, []
     with open(edgelist_path) as f:
         for line in f:
@@ -54,8 +92,18 @@ def read_edgelist(edgelist_path: str, nodelabel_path: str = None, hindex: bool =
                     node2id[n] = len(node2id)
             pairs.append((node2id[x], node2id[y]))
     num_nodes = len(node2id)
-    row_ptr, col_idx, listed = csr_from_pairs(np.asarray(pairs, dtype=np.int64), num_nodes)
+    pairs = np.asarray(pairs, dtype=np.int64)
+    expanded = False
+    try:
+        row_ptr, col_idx, listed = csr_from_pairs(pairs, num_nodes)
+    except NonUniformMultiplicity:
+        if not multigraph:
+            raise
+        row_ptr, col_idx = multigraph_csr(pairs, np.ones(len(pairs), dtype=np.int64), num_nodes)
+        listed, expanded = 1, True
     out = dict(row_ptr=row_ptr, col_idx=col_idx, edge_multiplicity=2 * listed, node2id=node2id, y=None)
+    if multigraph:
+        out["multigraph"] = expanded                 # the CSR holds repeated entries: consumers need DeviceGraph(multigraph=True)
     if nodelabel_path is not None:
         nodes, labels, label2id = [], [], {}
         with open(nodelabel_path) as f:
@@ -76,14 +124,17 @@ def read_edgelist(edgelist_path: str, nodelabel_path: str = None, hindex: bool =
     return out
 
 
-def read_ss_graph(graph_path: str, dict_path: str):
+def read_ss_graph(graph_path: str, dict_path: str, csr: bool = False):
     """``<name>.graph`` / ``<name>.dict`` of the similarity-search datasets (data/panther) as ``SSDataset._preprocess`` reads
     them (data_util.py:159-191): the first line of the graph file is a header; every other line is ``x y t``, a co-author pair
     and the number of joint papers, with ids re-indexed in order of first appearance; the dict file holds ``name<TAB>id``
     lines, and an id that no edge mentions gets the next free index.
     -> dict(node2id, name_dict {name: index}, pairs int64 [m, 2], weights int64 [m], num_nodes).  The reference's edge list
-    is every pair ``weights`` times in both directions.  No CSR is built: these weighted networks need a non-uniform edge
-    multiplicity, which ``csr_from_pairs`` refuses."""
+    is every pair ``weights`` times in both directions.
+    ``csr``: adds ``row_ptr`` / ``col_idx`` (``multigraph_csr``: that edge list, parallel edges as repeated entries) over the
+    ``num_graph_nodes`` nodes the graph file mentions, and ``edge_multiplicity`` = 2, the second insertion of every edge by
+    the dataset class (graph_dataset.py:301-302).  Ids that occur only in the dict file were indexed after those nodes and
+    stay out of the CSR, as in ``SSSingleDataset`` (data_util.py:111-143), whose graph has no node for them."""
     node2id, pairs, weights = {}, [], []
     with open(graph_path) as f:
         f.readline()
@@ -96,6 +147,7 @@ def read_ss_graph(graph_path: str, dict_path: str):
                     node2id[n] = len(node2id)
             pairs.append((node2id[x], node2id[y]))
             weights.append(t)
+    num_graph_nodes = len(node2id)
     name_dict = {}
     with open(dict_path) as f:
         for line in f:
@@ -106,8 +158,13 @@ def read_ss_graph(graph_path: str, dict_path: str):
             if x not in node2id:
                 node2id[x] = len(node2id)
             name_dict[name] = node2id[x]
-    return dict(node2id=node2id, name_dict=name_dict, pairs=np.asarray(pairs, dtype=np.int64).reshape(-1, 2),
-                weights=np.asarray(weights, dtype=np.int64), num_nodes=len(node2id))
+    out = dict(node2id=node2id, name_dict=name_dict, pairs=np.asarray(pairs, dtype=np.int64).reshape(-1, 2),
+               weights=np.asarray(weights, dtype=np.int64), num_nodes=len(node2id))
+    if csr:
+        out["num_graph_nodes"] = num_graph_nodes
+        out["row_ptr"], out["col_idx"] = multigraph_csr(out["pairs"], out["weights"], num_graph_nodes)
+        out["edge_multiplicity"] = 2
+    return out
 
 
 TU_NAMES = {"imdb-binary": "IMDB-BINARY", "imdb-multi": "IMDB-MULTI", "rdt-b": "REDDIT-BINARY",

@@ -133,7 +133,10 @@ class DeviceRWRSampler:
         dev = graph.device
         B = self.batch_size
         self.node_cap = B * (graph.lmax + 1)
-        self.edge_cap = int(edge_cap) if edge_cap else max(64 * B * (graph.rw_hops + 1), 2 * (graph.lmax + 1) ** 2)
+        # (a multigraph parent's induced rows repeat an entry per parallel edge: up to max_copies x (n - 1) entries per row.
+        #  Either term is a heuristic, not a bound -- an overflow sets status bit 4 and goes through check_status() / grow())
+        copies = int(getattr(graph, "max_copies", 1))
+        self.edge_cap = int(edge_cap) if edge_cap else max(64 * B * (graph.rw_hops + 1), 2 * copies * (graph.lmax + 1) ** 2)
         # induction scratch (hit slots): induce_kernel reserves one 1024-entry slot per unit of 256 aligned quads of
         # the members' parent rows, i.e. ~ the SUM OF THE MEMBERS' PARENT DEGREES per subgraph (not min(deg, n) as the
         # first induction did) -- unbounded by n: a hub-only batch needs several times the average.  A walk visits nodes

@@ -4,6 +4,11 @@ keys by cosine similarity, and Recall@k says how often the same author is among 
 
     python -m gcc_amd.tasks.similarity_search --dataset kdd_icdm --emb-path-1 A.npy --emb-path-2 B.npy \\
         [--data-root data/panther] [--k 20 40] [--device cuda:0|cpu] [--save-topk out.npz]
+    python -m gcc_amd.tasks.similarity_search --dataset kdd_icdm --load-path CKPT [--batch-size 256] [--save-emb DIR] ...
+
+With ``--load-path`` the two tables need not exist: both networks are embedded on the device with the checkpoint (what
+``generate.py --ss-graph`` does: the weighted network as the multigraph the reference builds, one row per node of the graph
+file) and handed to the search without a trip through disk; ``--save-emb DIR`` stores them as ``DIR/<network>.npy``.
 
 ``--dataset a_b`` reads ``<data-root>/a.graph``, ``a.dict``, ``b.graph`` and ``b.dict`` (gcc_amd.ingest.read_ss_graph).  On a
 GPU the search is one gcc_sim_search call (gcc_amd/simsearch.py); ``--device cpu`` runs the same rule in NumPy float64.  Among
@@ -125,19 +130,49 @@ def load_dicts(data_root, dataset):
     return dicts
 
 
-def main(argv=None):
+def embed_networks(data_root, dataset, load_path, batch_size=256, device="cuda:0", pipeline=None):
+    """Both networks of ``dataset`` embedded with the checkpoint ``load_path`` (gcc_amd.generate.run on ``--ss-graph``) ->
+    [table 1, table 2], float32 [nodes of the graph file, hidden].  ``pipeline``: generate.py's seam for the emulator tests."""
+    import torch
+
+    from ..generate import run
+
+    dev = torch.device(device)
+    tables = []
+    for name in dataset.split("_"):
+        a = argparse.Namespace(load_path=load_path, dataset=name, gpu=dev.index if dev.type == "cuda" else None, edgelist=None,
+                               nodelabel=None, ss_graph=os.path.join(data_root, name + ".graph"),
+                               ss_dict=os.path.join(data_root, name + ".dict"), graph_npz=None, graphs_npz=None, tudataset=None,
+                               edge_multiplicity=0, batch_size=batch_size, wide_eval="chain", graph_batcher="auto")
+        tables.append(run(a, pipeline=pipeline, save=False).numpy())
+    return tables
+
+
+def main(argv=None, pipeline=None, engine=None):
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
     ap.add_argument("--dataset", required=True, help="<network 1>_<network 2>, e.g. kdd_icdm")
-    ap.add_argument("--emb-path-1", required=True)
-    ap.add_argument("--emb-path-2", required=True)
+    ap.add_argument("--emb-path-1", default=None)
+    ap.add_argument("--emb-path-2", default=None)
+    ap.add_argument("--load-path", default=None, help="checkpoint: embed both networks on the device instead of reading --emb-path-1/-2")
+    ap.add_argument("--batch-size", type=int, default=256, help="--load-path: nodes embedded per batch")
+    ap.add_argument("--save-emb", default=None, metavar="DIR", help="--load-path: store the two tables as DIR/<network>.npy")
     ap.add_argument("--data-root", default=os.path.join("data", "panther"))
     ap.add_argument("--k", type=int, nargs="+", default=[20, 40])
     ap.add_argument("--device", default="cuda:0")
     ap.add_argument("--save-topk", default=None, metavar="OUT.npz")
     a = ap.parse_args(argv)
+    if a.load_path is None and (a.emb_path_1 is None or a.emb_path_2 is None):
+        ap.error("pass --emb-path-1 and --emb-path-2, or --load-path to embed the two networks")
     dict_1, dict_2 = load_dicts(a.data_root, a.dataset)
-    emb_1, emb_2 = load_embedding(a.emb_path_1), load_embedding(a.emb_path_2)
-    result, detail = evaluate(emb_1, emb_2, dict_1, dict_2, a.k, a.device, with_topk=a.save_topk is not None)
+    if a.load_path is not None:
+        emb_1, emb_2 = embed_networks(a.data_root, a.dataset, a.load_path, a.batch_size, a.device, pipeline)
+        if a.save_emb is not None:
+            os.makedirs(a.save_emb, exist_ok=True)
+            for name, emb in zip(a.dataset.split("_"), (emb_1, emb_2)):
+                np.save(os.path.join(a.save_emb, name + ".npy"), emb)
+    else:
+        emb_1, emb_2 = load_embedding(a.emb_path_1), load_embedding(a.emb_path_2)
+    result, detail = evaluate(emb_1, emb_2, dict_1, dict_2, a.k, a.device, with_topk=a.save_topk is not None, engine=engine)
     if a.save_topk is not None:
         names = np.array(detail["names"])
         cols = detail["topk_col"]

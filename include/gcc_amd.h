@@ -102,7 +102,15 @@ typedef struct gcc_graph {
 /* The caller has verified the contract above (symmetric, rows sorted ascending, no self loops, no duplicates).  Only
  * then may the induction skip hub rows (gcc_sample_params.hub_degree >= 0): their induced rows are rebuilt as mirror
  * images of the other rows' hits, which is the DGL-consistent subgraph on such a graph only.  Without the bit every
- * member row is scanned whatever hub_degree says (the result is then the induced subgraph of ANY sorted-row CSR). */
+ * member row is scanned whatever hub_degree says (the result is then the induced subgraph of ANY sorted-row CSR).
+ *
+ * What an UNCHECKED parent may hold: a multigraph.  Parallel edges are repeated entries of a row; rows are sorted
+ * non-decreasing, so the copies of an edge are adjacent; no self loops, no empty rows, and every pair has the same
+ * number of copies in both directions (gcc_amd.graphgen.check_multigraph_contract).  A uniform draw over a row's
+ * entries is then DGL's walk on the multigraph, the induction emits every copy (an induced row can hold MORE than
+ * n - 1 entries: size edge_cap and the scratch for that, overflow sets the usual status bits), the positional
+ * embedding's matrix is copies(i, j) / sqrt(d_i d_j) with d = row length, and the encoders take every entry as an
+ * edge of its own.  Such a parent must never carry the bit: the hub-row short cut mirrors one hit per pair. */
 #define GCC_GRAPH_CONTRACT_CHECKED 1
 
 /* --------------------------------------------------------------- sampler ---
