@@ -234,6 +234,33 @@ SIM_MAX_SPLITS = 64
 STATUS_SIM_ZERO_ROW = 1                      # gcc_sim_search's own status word
 STATUS_SIM_BAD_INDEX = 2
 
+
+
+class GccSvcArgs(ctypes.Structure):          # gcc_svc_args: C-SVC on frozen embeddings (csrc/svc.hip)
+    _fields_ = [
+        ("emb", _VP), ("ld", ctypes.c_int64),
+        ("labels", _VP), ("fold_of_row", _VP), ("gamma", _VP),
+        ("N", ctypes.c_int32), ("D", ctypes.c_int32), ("classes", ctypes.c_int32), ("folds", ctypes.c_int32),
+        ("max_rows", ctypes.c_int32), ("iters_per_launch", ctypes.c_int32), ("iter_cap", ctypes.c_int32),
+        ("reserved_", ctypes.c_int32),
+        ("C", ctypes.c_double), ("eps", ctypes.c_double),
+        ("pred", _VP), ("decision", _VP), ("iters", _VP), ("rho", _VP), ("obj", _VP), ("n_free", _VP), ("n_bounded", _VP),
+        ("problem_rows", _VP), ("unfinished", _VP), ("first_rows", _VP), ("rows_out", _VP), ("alpha_out", _VP),
+    ]
+
+
+SVC_MAX_ROWS = 16384
+SVC_MAX_DIM = 256
+SVC_MAX_PROBLEM_ROWS = 4096
+SVC_MAX_CLASSES = 32
+SVC_MAX_FOLDS = 64
+STATUS_SVC_BAD_LABEL = 1                     # the gcc_svc_* calls' own status word
+STATUS_SVC_BAD_FOLD = 2
+STATUS_SVC_MISSING_CLASS = 4
+STATUS_SVC_NONFINITE = 8
+STATUS_SVC_ITER_CAP = 16
+STATUS_SVC_OVERFLOW = 32
+
 CLS_HEAD_MAX_CLASSES = 64
 CLS_HEAD_MAX_DIM = 256
 
@@ -400,6 +427,13 @@ SIGNATURES = {
     "gcc_sim_workspace_bytes": (ctypes.c_int64, [ctypes.c_int32] * 5),
     "gcc_sim_search": (ctypes.c_int32, [ctypes.POINTER(GccSimArgs), ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p,
                                         ctypes.c_void_p]),
+    "gcc_svc_workspace_bytes": (ctypes.c_int64, [ctypes.c_int32] * 5),
+    "gcc_svc_distances": (ctypes.c_int32, [ctypes.POINTER(GccSvcArgs), ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p,
+                                           ctypes.c_void_p]),
+    "gcc_svc_solve": (ctypes.c_int32, [ctypes.POINTER(GccSvcArgs), ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p,
+                                       ctypes.c_void_p]),
+    "gcc_svc_predict": (ctypes.c_int32, [ctypes.POINTER(GccSvcArgs), ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p,
+                                         ctypes.c_void_p]),
 }
 # symbols declared in the header but not built yet are listed here while the build is in progress
 PENDING = set()

@@ -1,0 +1,161 @@
+"""C-SVC on frozen embeddings, on the device: every fold of a cross-validation and every class pair in one pass
+(gcc_svc_distances / gcc_svc_solve / gcc_svc_predict, gcc_amd/csrc/svc.hip) -- what the reference's
+gcc/tasks/graph_classification.py:47-64 does with one ``sklearn.svm.SVC(C=100000)`` fit per fold.
+
+The classifier is libsvm's: an RBF kernel with ``gamma = 1 / (D * var(training rows))`` per fold, one problem per class pair,
+SMO with the second-order working-set choice until ``max_{I_up} - min_{I_low} < tol``, votes in (i < j) order with ties to the
+lowest class.  A problem's rows are the fold's training rows of its two classes, the lower class first (its rows are +1);
+a positive decision value votes for the lower class.  Ties of a selection go to the lowest row of the problem, so a run
+is reproducible, and the result does not depend on how the iterations are split over launches.
+"""
+from __future__ import annotations
+
+import ctypes
+
+import numpy as np
+import torch
+
+from . import _cabi
+
+STATUS_BITS = {_cabi.STATUS_SVC_BAD_LABEL: "a label outside [0, classes)",
+               _cabi.STATUS_SVC_BAD_FOLD: "a fold id outside [0, folds)",
+               _cabi.STATUS_SVC_MISSING_CLASS: "a fold's training side lacks a class that its test side has",
+               _cabi.STATUS_SVC_NONFINITE: "an embedding is NaN or infinite",
+               _cabi.STATUS_SVC_ITER_CAP: "a problem stopped at the iteration cap before tol was reached",
+               _cabi.STATUS_SVC_OVERFLOW: "a problem has more rows than the workspace was sized for"}
+
+
+def largest_problem(labels, fold_of_row, classes, folds):
+    """rows of the largest (fold, class pair) problem: per fold, the two largest training classes (entries out of range train
+    nothing)"""
+    labels, fold_of_row = np.asarray(labels, dtype=np.int64), np.asarray(fold_of_row, dtype=np.int64)
+    ok = (labels >= 0) & (labels < classes) & (fold_of_row >= 0) & (fold_of_row < folds)
+    test = np.zeros((folds, classes), dtype=np.int64)
+    np.add.at(test, (fold_of_row[ok], labels[ok]), 1)
+    train = np.sort(test.sum(0)[None, :] - test, axis=1)
+    return int((train[:, -1] + train[:, -2]).max())
+
+
+class SVCEngine:
+    """C-ABI calls of the classifier.  ``lib``/``ptr`` are injectable for the emulator tests only."""
+
+    def __init__(self, lib=None, ptr=None):
+        self.lib = lib if lib is not None else _cabi.load()
+        self.ptr = ptr if ptr is not None else _cabi.dev_ptr
+        self._workspace = None
+
+    def workspace(self, nbytes, device):
+        """a buffer of at least ``nbytes`` that later calls reuse (stream-ordered: calls on ONE stream may share it)"""
+        ws = self._workspace
+        if ws is None or ws.numel() < nbytes or ws.device != device:
+            self._workspace = None             # (the old one first: a corpus of 16,384 rows needs a GiB)
+            ws = self._workspace = torch.empty(max(int(nbytes), 256), dtype=torch.uint8, device=device)
+        return ws
+
+    def _emb_args(self, emb):
+        if emb.dtype != torch.float32 or emb.dim() != 2 or (emb.shape[1] > 1 and emb.stride(1) != 1):
+            raise ValueError("emb must be a float32 matrix with unit stride along its rows")
+        if self.ptr is _cabi.dev_ptr and not emb.is_cuda:
+            raise RuntimeError("gcc_amd kernels take device (HIP) tensors only; there is no CPU path")
+        N, D = int(emb.shape[0]), int(emb.shape[1])
+        a = _cabi.GccSvcArgs()
+        a.emb, a.ld, a.N, a.D = emb.data_ptr(), (int(emb.stride(0)) if N > 1 else D), N, D
+        return a
+
+    def distances(self, emb):
+        """emb float32 [N, D] (a row stride larger than D is served) -> d2 float32 [N, N], a view of the engine's workspace"""
+        a = self._emb_args(emb)
+        a.classes, a.folds, a.max_rows = 2, 1, 0
+        nbytes = _cabi.size_query(self.lib, "gcc_svc_workspace_bytes", a.N, a.D, 2, 1, 0)
+        ws = self.workspace(nbytes, emb.device)
+        status = torch.zeros(1, dtype=torch.int32, device=emb.device)
+        _cabi.call(self.lib, "gcc_svc_distances", ctypes.byref(a), self.ptr(ws), ws.numel(), self.ptr(status),
+                   _cabi.raw_stream(emb.device))
+        return ws[: a.N * a.N * 4].view(torch.float32).view(a.N, a.N), status
+
+    def fit_predict_folds(self, emb, labels, fold_of_row, C=1e5, tol=1e-3, iters_per_launch=65536, iter_cap=0, classes=None,
+                          folds=None):
+        """emb float32 [N, D]; labels / fold_of_row: N integers each (array or tensor), fold_of_row[r] = the fold whose test
+        side holds row r.  ``classes`` / ``folds`` default to the largest entry + 1.  ``iter_cap``: total iterations of one
+        problem, 0 for libsvm's max(10^7, 100 rows).  -> dict(pred int32 [N]; decision float64 [N, pairs]; iters int32, rho,
+        obj float64, n_free, n_bounded, problem_rows int32 [folds, pairs]; gamma float64 [folds]; alpha float64 and rows int32
+        [folds, pairs, max_rows] (0 past problem_rows); first_rows int32 [folds, pairs], the rows of the lower class;
+        status int32 [1]; launches, classes, folds, pairs).  Everything runs on torch's current stream.  labels and
+        fold_of_row are host inputs (tensors are copied to the host: the problem sizes come from them); after that the solve
+        loop reads one integer per launch, and the status word is read by check_status."""
+        a = self._emb_args(emb)
+        dev = emb.device
+        lab_h = labels.cpu().numpy() if isinstance(labels, torch.Tensor) else np.asarray(labels)
+        fold_h = fold_of_row.cpu().numpy() if isinstance(fold_of_row, torch.Tensor) else np.asarray(fold_of_row)
+        if lab_h.shape != (a.N,) or fold_h.shape != (a.N,):
+            raise ValueError(f"labels and fold_of_row must hold one entry per row of emb ({a.N})")
+        classes = int(lab_h.max()) + 1 if classes is None else int(classes)
+        folds = int(fold_h.max()) + 1 if folds is None else int(folds)
+        if classes < 2:
+            raise ValueError("a classifier needs at least two classes")
+        if iter_cap < 0 or iter_cap >= 2 ** 31 or not 1 <= iters_per_launch < 2 ** 31:
+            raise ValueError("iters_per_launch must be positive, iter_cap not negative, both below 2^31")
+        pairs = classes * (classes - 1) // 2
+        max_rows = largest_problem(lab_h, fold_h, classes, folds) if 1 <= folds <= _cabi.SVC_MAX_FOLDS else 0
+        nbytes = _cabi.size_query(self.lib, "gcc_svc_workspace_bytes", a.N, a.D, classes, folds, max_rows)
+        lab_d = torch.from_numpy(np.ascontiguousarray(lab_h, dtype=np.int32)).to(dev)
+        fold_d = torch.from_numpy(np.ascontiguousarray(fold_h, dtype=np.int32)).to(dev)
+        x = emb.to(torch.float64)
+        gamma = self._gamma_scale(x, fold_d, folds)
+        i32, f64 = dict(dtype=torch.int32, device=dev), dict(dtype=torch.float64, device=dev)
+        out = dict(pred=torch.empty(a.N, **i32), decision=torch.empty((a.N, pairs), **f64),
+                   iters=torch.empty((folds, pairs), **i32), rho=torch.empty((folds, pairs), **f64),
+                   obj=torch.empty((folds, pairs), **f64), n_free=torch.empty((folds, pairs), **i32),
+                   n_bounded=torch.empty((folds, pairs), **i32), problem_rows=torch.empty((folds, pairs), **i32),
+                   first_rows=torch.zeros((folds, pairs), **i32), rows=torch.zeros((folds, pairs, max(max_rows, 1)), **i32),
+                   alpha=torch.zeros((folds, pairs, max(max_rows, 1)), **f64),
+                   status=torch.zeros(1, **i32), gamma=gamma, classes=classes, folds=folds, pairs=pairs)
+        unfinished = torch.zeros(1, **i32)
+        a.labels, a.fold_of_row, a.gamma = self.ptr(lab_d), self.ptr(fold_d), self.ptr(gamma)
+        a.classes, a.folds, a.max_rows = classes, folds, max_rows
+        a.iters_per_launch, a.iter_cap, a.C, a.eps = int(iters_per_launch), int(iter_cap), float(C), float(tol)
+        for name in ("pred", "decision", "iters", "rho", "obj", "n_free", "n_bounded", "problem_rows"):
+            setattr(a, name, self.ptr(out[name]))
+        a.unfinished, a.first_rows = self.ptr(unfinished), self.ptr(out["first_rows"])
+        a.rows_out, a.alpha_out = self.ptr(out["rows"]), self.ptr(out["alpha"])
+        ws = self.workspace(nbytes, dev)
+        stream = _cabi.raw_stream(dev)
+        call = lambda name: _cabi.call(self.lib, name, ctypes.byref(a), self.ptr(ws), ws.numel(), self.ptr(out["status"]), stream)  # noqa: E731
+        call("gcc_svc_distances")
+        # every problem ends at its iteration cap at the latest, so the launches are bounded too
+        cap = iter_cap if iter_cap > 0 else max(10 ** 7, 100 * max_rows)
+        launches = 0
+        for _ in range(cap // int(iters_per_launch) + 2):
+            call("gcc_svc_solve")
+            launches += 1
+            if int(unfinished.cpu()[0]) == 0:  # the one host read of a launch
+                break
+        else:
+            raise RuntimeError("gcc_svc_solve: problems left unfinished past the iteration cap")
+        call("gcc_svc_predict")
+        out["launches"] = launches
+        return out
+
+    @staticmethod
+    def _gamma_scale(x, fold_d, folds):
+        """sklearn's gamma="scale" per fold, 1 / (D var) over all elements of the fold's training rows, in float64 and without
+        a host read: per-row sums of the table (shifted by its mean, which the variance does not see) are added up per test
+        fold in a fixed order, and a fold's training side is the total minus its own.  x float64 [N, D] -> float64 [folds]"""
+        D = x.shape[1]
+        # (a [folds, N] membership mask and row-wise sums, not index_add: its atomics would make gamma differ from run to run)
+        m = (fold_d[None, :] == torch.arange(folds, dtype=fold_d.dtype, device=x.device)[:, None]).to(torch.float64)
+        xc = x - (x * m.sum(0)[:, None]).sum() / (m.sum() * D).clamp(min=1.0)
+        n, s1, s2 = m.sum(1) * D, (m * xc.sum(1)[None, :]).sum(1), (m * (xc * xc).sum(1)[None, :]).sum(1)
+        n, s1, s2 = n.sum() - n, s1.sum() - s1, s2.sum() - s2
+        var = s2 / n - (s1 / n) ** 2
+        return torch.where(var > 0, 1.0 / (D * var), torch.ones_like(var))       # (an empty or constant side: 1, as sklearn)
+
+    @staticmethod
+    def check_status(result, allow_iter_cap=False):
+        """Raises and names the bits of the call's status word (one host read).  The iteration cap raises unless allowed:
+        libsvm only warns there, and the result is the solver's state at the cap."""
+        bits = int(result["status"].cpu()[0])
+        if allow_iter_cap:
+            bits &= ~_cabi.STATUS_SVC_ITER_CAP
+        if bits:
+            raise RuntimeError("gcc_svc: " + "; ".join(text for bit, text in STATUS_BITS.items() if bits & bit))

@@ -1,0 +1,148 @@
+"""Graph classification on frozen embeddings (gcc/tasks/graph_classification.py of the reference, the "GCC (freeze)" column of
+the paper's graph-classification table): ``StratifiedKFold(10, shuffle=True, random_state=seed)`` over the graphs' labels, an
+RBF C-SVC with C = 100000 per fold, the mean accuracy as ``{"Micro-F1": ...}``.
+
+    python -m gcc_amd.tasks.graph_classification --dataset imdb-binary --emb-path E.npy (--tudataset DIR | --graphs-npz F) \\
+        [--seed 0] [--device cuda:0|cpu] [--C 100000] [--save-pred OUT.npz]
+    python -m gcc_amd.tasks.graph_classification --dataset imdb-binary --load-path CKPT (--tudataset DIR | --graphs-npz F) ...
+
+With ``--load-path`` the table need not exist: the corpus is embedded on the device with the checkpoint (what ``generate.py
+--tudataset / --graphs-npz`` does) and handed on without a trip through disk.  The labels come from the corpus
+(gcc_amd.ingest.read_tudataset, or ``graph_labels`` of the npz).  On a GPU all ten folds and all class pairs are solved in
+one pass of gcc_amd.svc.SVCEngine (gcc_amd/csrc/svc.hip); ``--device cpu`` runs sklearn's ``SVC`` itself, fold by fold, as the
+reference does.  ``--model from_numpy_graph --hidden-size --num-shuffle`` of the reference's command line are accepted and
+checked, nothing more.  Prints the reference's result line with the fold count and the SMO iterations added;
+``--save-pred`` stores the predicted label (-1 where no class pair of the fold could vote), the fold and the decision values of
+every graph."""
+from __future__ import annotations
+
+import argparse
+
+import numpy as np
+
+from .similarity_search import load_embedding
+
+FOLDS = 10
+
+
+def fold_ids(labels, seed, folds=FOLDS):
+    """fold_of_row [N] int32: the fold whose test side holds the row, from the reference's StratifiedKFold"""
+    try:
+        from sklearn.model_selection import StratifiedKFold
+    except ImportError as e:                    # never another split silently: the folds are the reference's or none
+        raise RuntimeError("graph classification needs scikit-learn (the reference's StratifiedKFold picks the folds)") from e
+    fold = np.full(len(labels), -1, dtype=np.int32)
+    for f, (_, test) in enumerate(StratifiedKFold(n_splits=folds, shuffle=True, random_state=seed).split(np.zeros(len(labels)), labels)):
+        fold[test] = f
+    return fold
+
+
+def classify_sklearn(emb, labels, fold, C):
+    """graph_classification.py:47-64 with the folds given: sklearn's SVC per fold -> (pred int32 [N], None, 0)"""
+    from sklearn.svm import SVC
+
+    pred = np.full(len(labels), -1, dtype=np.int32)
+    for f in range(int(fold.max()) + 1):
+        train, test = fold != f, fold == f
+        pred[test] = SVC(C=C).fit(emb[train], labels[train]).predict(emb[test])
+    return pred, None, 0
+
+
+def classify_device(emb, labels, fold, C, device, engine=None):
+    """-> (pred int32 [N], decision float64 [N, pairs], total SMO iterations)"""
+    import torch
+
+    from .. import _cabi
+    from ..svc import SVCEngine
+
+    engine = engine if engine is not None else SVCEngine()
+    x = torch.from_numpy(np.ascontiguousarray(emb, dtype=np.float32)).to(torch.device(device))
+    res = engine.fit_predict_folds(x, labels, fold, C=C)
+    engine.check_status(res, allow_iter_cap=True)
+    if int(res["status"].cpu()[0]) & _cabi.STATUS_SVC_ITER_CAP:  # libsvm warns and goes on with the solver's state at the cap
+        print("warning: a (fold, class pair) problem stopped at the iteration cap before tol was reached")
+    return res["pred"].cpu().numpy(), res["decision"].cpu().numpy(), int(res["iters"].sum())
+
+
+def evaluate(emb, labels, seed=0, C=1e5, device="cpu", engine=None, folds=FOLDS):
+    """-> (result {"Micro-F1": mean accuracy over the folds, "folds": n, "iterations": SMO iterations or 0}, detail dict(pred,
+    fold, decision or None); pred holds the corpus' own label values, -1 for a row without a vote).  ``engine``: a gcc_amd.svc.SVCEngine (injectable for the emulator tests); sklearn when ``device``
+    is "cpu" and no engine is given."""
+    labels = np.asarray(labels)
+    if emb.shape[0] != len(labels):
+        raise ValueError(f"{emb.shape[0]} embedding rows for {len(labels)} labelled graphs")
+    classes, y = np.unique(labels, return_inverse=True)           # sorted, as sklearn orders them
+    if len(classes) < 2:
+        raise ValueError("graph classification needs at least two classes")
+    fold = fold_ids(y, seed, folds)
+    if engine is None and str(device) == "cpu":
+        pred, decision, iterations = classify_sklearn(emb, y, fold, C)
+    else:
+        pred, decision, iterations = classify_device(emb, y, fold, C, device, engine)
+    accuracies = [float((pred[fold == f] == y[fold == f]).mean()) for f in range(folds)]
+    result = {"Micro-F1": float(np.mean(accuracies)), "folds": folds, "iterations": iterations}
+    # a row without a vote (its fold trained none of the pairs) counts as wrong above and is stored as -1
+    return result, dict(pred=np.where(pred >= 0, classes[np.maximum(pred, 0)], -1), fold=fold, decision=decision)
+
+
+def load_labels(a):
+    from .. import ingest
+
+    if a.tudataset:
+        return ingest.read_tudataset(a.tudataset, a.dataset)["graph_labels"]
+    z = np.load(a.graphs_npz)
+    if "graph_labels" not in z:
+        raise ValueError(f"{a.graphs_npz} holds no graph_labels")
+    return z["graph_labels"].astype(np.int64)
+
+
+def embed_corpus(a, pipeline=None):
+    """the corpus embedded with the checkpoint ``--load-path`` (gcc_amd.generate.run) -> float32 [graphs, hidden]"""
+    import torch
+
+    from ..generate import run
+
+    dev = torch.device(a.device)
+    g = argparse.Namespace(load_path=a.load_path, dataset=a.dataset, gpu=dev.index if dev.type == "cuda" else None, edgelist=None,
+                           nodelabel=None, ss_graph=None, ss_dict=None, graph_npz=None, graphs_npz=a.graphs_npz,
+                           tudataset=a.tudataset, edge_multiplicity=0, batch_size=a.batch_size, wide_eval="chain",
+                           graph_batcher="auto")
+    return run(g, pipeline=pipeline, save=False).numpy()
+
+
+def main(argv=None, pipeline=None, engine=None):
+    ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
+    ap.add_argument("--dataset", required=True, help="the corpus' name, e.g. imdb-binary")
+    ap.add_argument("--emb-path", default=None)
+    ap.add_argument("--load-path", default=None, help="checkpoint: embed the corpus on the device instead of reading --emb-path")
+    ap.add_argument("--batch-size", type=int, default=256, help="--load-path: graphs embedded per batch")
+    ap.add_argument("--tudataset", default=None, metavar="DIR")
+    ap.add_argument("--graphs-npz", default=None)
+    ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--device", default="cuda:0")
+    ap.add_argument("--C", type=float, default=100000.0)
+    ap.add_argument("--save-pred", default=None, metavar="OUT.npz")
+    ap.add_argument("--model", default="from_numpy_graph", help="the reference's option: only from_numpy_graph exists")
+    ap.add_argument("--hidden-size", type=int, default=None, help="the reference's option: checked against the table's width")
+    ap.add_argument("--num-shuffle", type=int, default=10, help="the reference's option: unused there as here")
+    a = ap.parse_args(argv)
+    if a.model != "from_numpy_graph":
+        ap.error("--model: the reference's task asserts from_numpy_graph")
+    if (a.emb_path is None) == (a.load_path is None):
+        ap.error("pass --emb-path, or --load-path to embed the corpus")
+    if (a.tudataset is None) == (a.graphs_npz is None):
+        ap.error("pass --tudataset DIR or --graphs-npz F (the labels come from the corpus; dataset files are not bundled)")
+    labels = load_labels(a)
+    emb = embed_corpus(a, pipeline) if a.load_path is not None else load_embedding(a.emb_path)
+    if a.hidden_size is not None and emb.shape[1] != a.hidden_size:
+        ap.error(f"--hidden-size {a.hidden_size}, but the table has {emb.shape[1]} columns")
+    result, detail = evaluate(emb, labels, a.seed, a.C, a.device, engine)
+    if a.save_pred is not None:
+        extra = {} if detail["decision"] is None else dict(decision=detail["decision"])
+        np.savez(a.save_pred, pred=detail["pred"], fold=detail["fold"], labels=labels, **extra)
+    print(result)
+    return result
+
+
+if __name__ == "__main__":
+    main()

@@ -858,6 +858,64 @@ int64_t gcc_sim_workspace_bytes(int32_t mq, int32_t mc, int32_t D, int32_t k, in
  * and normalise; target scores; tiles; merge of the splits), no host synchronisation. */
 int32_t gcc_sim_search(const gcc_sim_args *a, void *workspace, int64_t workspace_bytes, int32_t *status, void *stream);
 
+/* ---------------------------------------------- C-SVC on frozen embeddings ---
+ * gcc/tasks/graph_classification.py:47-64 of the reference: StratifiedKFold, then sklearn.svm.SVC(C=100000) per fold, which
+ * is libsvm's one-vs-one C-SVC with an RBF kernel.  Here every (fold, class pair) is one problem -- the fold's training rows
+ * of the two classes, class ci's rows first (+1), then class cj's (-1), each in corpus order -- and all problems of all
+ * folds are solved side by side, one workgroup each, over ONE matrix of squared distances of the corpus:
+ *   gcc_svc_distances   d2[i, j] = sum_c (x_i[c] - x_j[c])^2 (float32, bitwise symmetric, zero diagonal: the first N * N floats of
+ *                       the workspace) and, with labels, the problems' row lists with alpha = 0, G = -1
+ *   gcc_svc_solve       at most iters_per_launch SMO iterations of every unfinished problem (Fan, Chen, Lin 2005, WSS 2: alpha and
+ *                       G float64, kernel values (float)exp(-gamma[fold] * d2), ties to the lowest row of the problem);
+ *                       *unfinished = the number of problems that need another launch
+ *   gcc_svc_predict     for every corpus row and every class pair of the row's own fold sum_t alpha_t y_t K(t, row) - rho in
+ *                       float64 (positive: class ci), and libsvm's vote: pairs in (ci < cj) order, ties to the lowest class
+ * The three calls share args and workspace; the workspace carries alpha, G and the iteration counts between them.  A pair
+ * one of whose classes has no training row in the fold is not solved and does not vote. */
+#define GCC_SVC_MAX_ROWS 16384
+#define GCC_SVC_MAX_DIM 256
+#define GCC_SVC_MAX_PROBLEM_ROWS 4096
+#define GCC_SVC_MAX_CLASSES 32
+#define GCC_SVC_MAX_FOLDS 64
+#define GCC_STATUS_SVC_BAD_LABEL     1   /* a label outside [0, classes): the row trains nothing (it is still predicted) */
+#define GCC_STATUS_SVC_BAD_FOLD      2   /* a fold id outside [0, folds): the row is left out, pred -1 */
+#define GCC_STATUS_SVC_MISSING_CLASS 4   /* a fold's training side lacks a class that its test side has */
+#define GCC_STATUS_SVC_NONFINITE     8   /* an embedding is NaN or infinite */
+#define GCC_STATUS_SVC_ITER_CAP      16  /* a problem stopped at the iteration cap before eps was reached */
+#define GCC_STATUS_SVC_OVERFLOW      32  /* a problem has more rows than max_rows: not solved */
+typedef struct gcc_svc_args {
+    const float *emb; int64_t ld;          /* device [N, ld], ld >= D */
+    const int32_t *labels, *fold_of_row;   /* device [N]: class 0..classes-1; the fold whose TEST side holds the row */
+    const double *gamma;                   /* device [folds]: 1 / (D * var(the fold's training rows)) for sklearn's "scale" */
+    int32_t N, D, classes, folds;
+    int32_t max_rows;                      /* the largest problem's rows, at most GCC_SVC_MAX_PROBLEM_ROWS */
+    int32_t iters_per_launch;              /* gcc_svc_solve: SMO iterations of one launch per problem, >= 1 */
+    int32_t iter_cap;                      /* total iterations of one problem; 0: libsvm's max(10^7, 100 rows) */
+    int32_t reserved_;
+    double C, eps;                         /* box bound; stop when max_{I_up} - min_{I_low} < eps */
+    int32_t *pred;                         /* device [N] out or NULL: the voted class, -1 without a vote */
+    double *decision;                      /* device [N, classes (classes - 1) / 2] out or NULL; 0 for a pair that was not solved */
+    int32_t *iters;                        /* device [folds * pairs] out or NULL (problem = fold * pairs + pair), as the next five */
+    double *rho, *obj;                     /* obj: the dual objective sum_t alpha_t (G_t - 1) / 2 */
+    int32_t *n_free, *n_bounded;           /* support vectors with 0 < alpha < C / with alpha = C */
+    int32_t *problem_rows;                 /* written by gcc_svc_distances, as first_rows and rows_out */
+    int32_t *unfinished;                   /* device int32[1], gcc_svc_solve */
+    int32_t *first_rows;                   /* device [folds * pairs] out or NULL: the problem's rows of class ci (they come first) */
+    int32_t *rows_out;                     /* device [folds * pairs, max_rows] out or NULL: the problem's corpus rows in its order */
+    double *alpha_out;                     /* device [folds * pairs, max_rows] out or NULL: alpha of a finished problem (gcc_svc_solve);
+                                              entries past problem_rows are not written in either */
+} gcc_svc_args;
+/* bytes of workspace: N * N * 4 for the distances + O(folds * pairs * max_rows); negative on a size out of range, and
+ * gcc_last_error() names it (max_rows beyond GCC_SVC_MAX_PROBLEM_ROWS among them) */
+int64_t gcc_svc_workspace_bytes(int32_t N, int32_t D, int32_t classes, int32_t folds, int32_t max_rows);
+/* status: device int32[1], OR-ed, zeroed by the caller.  A size out of range, a NULL member the call needs, ld < D and a short
+ * workspace return rc < 0, name the member in gcc_last_error() and launch nothing.  No host synchronisation in any of them:
+ * the caller reads *unfinished after a gcc_svc_solve and launches again while it is not 0.  labels == fold_of_row == NULL in
+ * gcc_svc_distances: the distances only. */
+int32_t gcc_svc_distances(const gcc_svc_args *a, void *workspace, int64_t workspace_bytes, int32_t *status, void *stream);
+int32_t gcc_svc_solve(const gcc_svc_args *a, void *workspace, int64_t workspace_bytes, int32_t *status, void *stream);
+int32_t gcc_svc_predict(const gcc_svc_args *a, void *workspace, int64_t workspace_bytes, int32_t *status, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
