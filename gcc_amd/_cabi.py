@@ -9,6 +9,7 @@ from __future__ import annotations
 
 import ctypes
 import os
+from collections import namedtuple
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "csrc", "libgcc_amd.so")
@@ -498,6 +499,56 @@ def error_text(lib, name, rc):
 def node_cap(g) -> int:
     """rows of a batch's per-node arrays (a sampler batch carries ``parent_nid``, the hand-built ones only ``graph_id``)"""
     return g.parent_nid.numel() if hasattr(g, "parent_nid") else g.graph_id.numel()
+
+
+# What an encoder call passes down of one batch (bind_batch): six addresses (None where absent), the scalars that go with them, and
+# ``keep``: tensors the addresses point into that the batch itself does not hold (the col_idx stand-in)
+BatchBinding = namedtuple("BatchBinding", "node_off row_ptr col_idx graph_id pos seed_local batch_size node_cap edge_multiplicity "
+                                          "device keep")
+
+
+def bind_batch(g, ptr, *, need_pos=True, need_graph_id=False, col_placeholder=False) -> BatchBinding:
+    """The one place that turns a batch -- a :class:`gcc_amd.sampler.BatchedCSR`, or a hand-built object with its members -- into
+    the fields of an encoder call's struct.  ``ptr`` maps a tensor to its address (an engine's ``self.ptr``).  Hand-built batches
+    may lack ``parent_nid`` (the capacity is then ``graph_id``'s length), ``seed_local`` (None) and ``edge_multiplicity`` (1).
+    Enforces the capacity rule from the tensors' shapes alone, without a host read of device memory: the
+    kernels clamp a workgroup's first-tile loads to the capacity, not to the live node count; longer arrays are fine.
+    ``col_placeholder``: some C calls refuse the null address of an empty ``col_idx``; one int32 element stands in for it."""
+    pos = getattr(g, "pos_undirected", None)
+    if need_pos and pos is None:
+        raise RuntimeError("the batch has no pos_undirected (run the positional embedding first)")
+    cap = node_cap(g)
+    if g.row_ptr.numel() <= cap:
+        _too_short("row_ptr", g.row_ptr.numel(), cap + 1, cap)
+    if need_graph_id and g.graph_id.numel() < cap:
+        _too_short("graph_id", g.graph_id.numel(), cap, cap)
+    if need_pos and pos.shape[0] < cap:
+        _too_short("pos_undirected", pos.shape[0], cap, cap)
+    device = g.node_off.device
+    col_idx, keep = g.col_idx, ()
+    if col_placeholder and col_idx.numel() == 0:
+        import torch
+
+        col_idx = torch.zeros(1, dtype=torch.int32, device=device)
+        keep = (col_idx,)
+    seed_local = getattr(g, "seed_local", None)
+    return BatchBinding(ptr(g.node_off), ptr(g.row_ptr), ptr(col_idx), ptr(g.graph_id) if need_graph_id else None,
+                        ptr(pos) if need_pos else None, ptr(seed_local) if seed_local is not None else None, g.batch_size, cap,
+                        int(getattr(g, "edge_multiplicity", 1)), device, keep)
+
+
+def _too_short(name, have, need, cap):
+    raise RuntimeError(f"the batch's {name} has {have} rows, its node capacity of {cap} needs at least {need}: row_ptr holds capacity + 1 "
+                       "entries, graph_id and pos_undirected capacity rows (capacity = parent_nid.numel(), or graph_id.numel() without "
+                       "parent_nid) -- the kernels' first-tile loads are clamped to the capacity, not to the live node count")
+
+
+def batch_out(g, ptr, node_cap, csr_only=False) -> GccBatchOut:
+    """gcc_batch_out of a batch's arrays: all six (the sampler's output buffers), or ``csr_only`` -- node_off, row_ptr and col_idx,
+    what the positional embedding reads.  ``node_cap``: rows of the per-node arrays; edge_cap is ``col_idx``'s length."""
+    rest = {} if csr_only else dict(edge_off=ptr(g.edge_off), parent_nid=ptr(g.parent_nid), graph_id=ptr(g.graph_id))
+    return GccBatchOut(node_off=ptr(g.node_off), row_ptr=ptr(g.row_ptr), col_idx=ptr(g.col_idx), node_cap=node_cap,
+                       edge_cap=g.col_idx.numel(), **rest)
 
 
 def raw_stream(where):

@@ -264,36 +264,40 @@ class GraphClassificationDataset:
         rp, _ = self.graphs[idx]
         return idx, int(np.argmax(np.diff(rp)))
 
-    def _batch(self, lo, hi):
+    def _batch_of(self, idx):
+        """The host batcher: the graphs ``idx`` (at most batch_size indices, in any order) as one batch, padded with empty graphs.
+        row_ptr always starts with its [0] row, and a batch without entries gets a one-element col_idx (a null address is
+        refused further down)."""
         import torch
 
         from .sampler import BatchedCSR
 
         B = self.batch_size
-        node_off, edge_off, rows, cols, seeds = [0], [0], [], [], []
-        for idx in range(lo, hi):
-            rp, ci = self.graphs[idx]
+        node_off, edge_off, rows, cols, seeds = [0], [0], [np.zeros(1, dtype=np.int64)], [np.zeros(0, dtype=np.int64)], []
+        for i in idx:
+            rp, ci = self.graphs[i]
             o = node_off[-1]
             rows.append(rp[1:] + edge_off[-1])
             cols.append(ci + o)
-            seeds.append(self._convert_idx(idx)[1])
+            seeds.append(self._convert_idx(i)[1])
             node_off.append(o + len(rp) - 1)
             edge_off.append(edge_off[-1] + len(ci))
-        for _ in range(hi - lo, B):                                   # padding: empty graphs
+        for _ in range(len(idx), B):
             node_off.append(node_off[-1])
             edge_off.append(edge_off[-1])
             seeds.append(0)
-        n, e = node_off[-1], edge_off[-1]
+        n = node_off[-1]
         i32 = dict(dtype=torch.int32, device=self.device)
         row_ptr = torch.zeros(self.node_cap + 1, **i32)
-        row_ptr[: n + 1] = torch.from_numpy(np.concatenate([[0]] + rows).astype(np.int32)).to(self.device)
+        row_ptr[: n + 1] = torch.from_numpy(np.concatenate(rows).astype(np.int32)).to(self.device)
         graph_id = torch.zeros(self.node_cap, **i32)
         graph_id[:n] = torch.repeat_interleave(torch.arange(B, dtype=torch.int32), torch.tensor(np.diff(node_off))).to(self.device)
+        col = np.concatenate(cols).astype(np.int32)
         g = BatchedCSR(B, torch.tensor(node_off, **i32), torch.tensor(edge_off, **i32), torch.zeros(self.node_cap, **i32),
-                       graph_id, row_ptr, torch.from_numpy(np.concatenate(cols).astype(np.int32)).to(self.device))
+                       graph_id, row_ptr, torch.from_numpy(col if len(col) else np.zeros(1, np.int32)).to(self.device))
         g.seed_local = torch.tensor(seeds, **i32)
         g.edge_multiplicity = self.edge_multiplicity
-        g.valid = hi - lo
+        g.valid = len(idx)
         return g
 
     def __iter__(self):
@@ -301,7 +305,7 @@ class GraphClassificationDataset:
             yield from self._iter_device()
             return
         for lo in range(0, self.length, self.batch_size):
-            g = self._batch(lo, min(lo + self.batch_size, self.length))
+            g = self._batch_of(range(lo, min(lo + self.batch_size, self.length)))
             yield g, g                                                # graph_q and graph_k are the same whole graph
 
     def _iter_device(self):
@@ -333,7 +337,7 @@ def _expand_multiplicity(g):
     ``edge_multiplicity`` times in a row.  The sum aggregation and the in-degrees are then exactly the multigraph's.  Sized by
     the buffers' capacity, so no host read of the live edge count.  (Run after the positional embedding: the normalised
     Laplacian of a uniformly multiplied graph is the simple graph's.)"""
-    m = int(getattr(g, "edge_multiplicity", 1))
+    m = int(g.edge_multiplicity)
     if m > 1:
         g.row_ptr = g.row_ptr * m
         g.edge_off = g.edge_off * m
@@ -464,40 +468,6 @@ class GraphClassificationDatasetLabeled(GraphClassificationDataset):
             self.posemb(g)
             parts.append(g.pos_undirected[: int(self.first[idx[-1] + 1] - self.first[idx[0]])].clone())
         self._pos = torch.cat(parts)
-
-    def _batch_of(self, idx):
-        """GraphClassificationDataset._batch over an arbitrary list of graph indices (empty padding graphs)"""
-        import torch
-
-        from .sampler import BatchedCSR
-
-        B = self.batch_size
-        node_off, edge_off, rows, cols, seeds = [0], [0], [np.zeros(1, dtype=np.int64)], [np.zeros(0, dtype=np.int64)], []
-        for i in idx:
-            rp, ci = self.graphs[i]
-            o = node_off[-1]
-            rows.append(rp[1:] + edge_off[-1])
-            cols.append(ci + o)
-            seeds.append(self._convert_idx(i)[1])
-            node_off.append(o + len(rp) - 1)
-            edge_off.append(edge_off[-1] + len(ci))
-        for _ in range(len(idx), B):
-            node_off.append(node_off[-1])
-            edge_off.append(edge_off[-1])
-            seeds.append(0)
-        n = node_off[-1]
-        i32 = dict(dtype=torch.int32, device=self.device)
-        row_ptr = torch.zeros(self.node_cap + 1, **i32)
-        row_ptr[: n + 1] = torch.from_numpy(np.concatenate(rows).astype(np.int32)).to(self.device)
-        graph_id = torch.zeros(self.node_cap, **i32)
-        graph_id[:n] = torch.repeat_interleave(torch.arange(B, dtype=torch.int32), torch.tensor(np.diff(node_off))).to(self.device)
-        col = np.concatenate(cols).astype(np.int32)
-        g = BatchedCSR(B, torch.tensor(node_off, **i32), torch.tensor(edge_off, **i32), torch.zeros(self.node_cap, **i32),
-                       graph_id, row_ptr, torch.from_numpy(col if len(col) else np.zeros(1, np.int32)).to(self.device))
-        g.seed_local = torch.tensor(seeds, **i32)
-        g.edge_multiplicity = self.edge_multiplicity
-        g.valid = len(idx)
-        return g
 
     def _device_batch(self, idx_dev, idx, ready=None):
         """the batch of the graphs ``idx`` whose indices are already on the device (``idx_dev``: int32 [B], -1 = padding)"""

@@ -190,30 +190,17 @@ class GatEngine:
     def forward(self, enc, g, stream=None):
         """-> (out [B, out_dim], saved, pass struct, weights struct)"""
         stream = stream if stream is not None else _cabi.raw_stream(g.node_off)
-        if g.pos_undirected is None:
-            raise RuntimeError("the batch has no pos_undirected (run the positional embedding first)")
+        # (an edge-free batch -- isolated nodes, empty graphs -- gets the col_idx stand-in: the C side refuses a null member, it
+        #  cannot tell such a batch from one with live entries without a sync)
+        b = _cabi.bind_batch(g, self.ptr, col_placeholder=True)
         w = self.weights(enc)
-        node_cap = _cabi.node_cap(g)
-        n = _cabi.size_query(self.lib, "gcc_gat_saved_floats", ctypes.byref(w), node_cap, g.batch_size)
-        dev = g.node_off.device
-        saved = torch.empty(n, dtype=torch.float32, device=dev)
-        out = torch.empty(g.batch_size, enc.output_dim, dtype=torch.float32, device=dev)
-        p = _cabi.GccGatPass()
-        ptr = self.ptr
-        col_idx = g.col_idx
-        if col_idx.numel() == 0:
-            # an edge-free batch (isolated nodes, empty graphs): every row is empty, so the kernels never read col_idx, but
-            # an empty tensor's data pointer is null and the C side refuses a null member (it cannot tell this batch from
-            # one with live entries without a sync).  One placeholder element stands in for it.
-            col_idx = torch.zeros(1, dtype=torch.int32, device=dev)
-        p.node_off, p.row_ptr, p.col_idx = ptr(g.node_off), ptr(g.row_ptr), ptr(col_idx)
-        p._col_idx = col_idx            # the struct holds a raw pointer that the backward reads too: it lives as long as p
-        seed_local = getattr(g, "seed_local", None)
-        p.seed_local = ptr(seed_local) if seed_local is not None else None
-        p.pos = ptr(g.pos_undirected)
-        p.batch_size, p.node_cap = g.batch_size, node_cap
-        p.edge_multiplicity = int(getattr(g, "edge_multiplicity", 1))
-        p.saved, p.out = ptr(saved), ptr(out)
+        n = _cabi.size_query(self.lib, "gcc_gat_saved_floats", ctypes.byref(w), b.node_cap, b.batch_size)
+        saved = torch.empty(n, dtype=torch.float32, device=b.device)
+        out = torch.empty(b.batch_size, enc.output_dim, dtype=torch.float32, device=b.device)
+        p = _cabi.GccGatPass(node_off=b.node_off, row_ptr=b.row_ptr, col_idx=b.col_idx, seed_local=b.seed_local, pos=b.pos,
+                             batch_size=b.batch_size, node_cap=b.node_cap, edge_multiplicity=b.edge_multiplicity,
+                             saved=self.ptr(saved), out=self.ptr(out))
+        p._keep = (g.col_idx, b.keep)   # the struct holds raw pointers that the backward reads too: they live as long as p
         _cabi.call(self.lib, "gcc_gat_forward", ctypes.byref(p), ctypes.byref(w), stream)
         return out, saved, p, w
 
@@ -266,20 +253,20 @@ class GinEngine:
         return self._bufs[k]
 
     def make_pass(self, enc, g, training, keep=None, slot=0, dropout_seed=None, scalars=None, backward=True):
-        """-> (GccGinPass, buffers).  ``g`` needs node_off,row_ptr,col_idx,graph_id,pos_undirected,batch_size.
+        """-> (GccGinPass, buffers).  ``g`` needs node_off,row_ptr,col_idx,graph_id,pos_undirected,batch_size, sized by the
+        capacity rule (:func:`_cabi.bind_batch` raises otherwise: row_ptr capacity + 1 entries, graph_id and pos_undirected
+        capacity rows).
         ``backward=False``: a pass nobody differentiates (MoCo's key encoder): ``agg`` -- kept only for the weight gradient of
         linears.0 -- is not stored (6.4 MB per layer at bsz 256)."""
         ptr = self.ptr
         L = len(enc.gnn.ginlayers)
         enc.ensure_padded()
-        node_cap = _cabi.node_cap(g)
-        buf = self._buffers(slot, node_cap, g.batch_size, L, g.node_off.device)
-        p = _cabi.GccGinPass()
-        p.node_off, p.row_ptr, p.col_idx, p.graph_id = ptr(g.node_off), ptr(g.row_ptr), ptr(g.col_idx), ptr(g.graph_id)
-        if g.pos_undirected is None:
-            raise RuntimeError("the batch has no pos_undirected (run the positional embedding first)")
-        p.pos = ptr(g.pos_undirected)
-        p.batch_size = g.batch_size
+        b = _cabi.bind_batch(g, ptr, need_graph_id=True)
+        node_cap = b.node_cap
+        buf = self._buffers(slot, node_cap, b.batch_size, L, b.device)
+        p = _cabi.GccGinPass(node_off=b.node_off, row_ptr=b.row_ptr, col_idx=b.col_idx, graph_id=b.graph_id, pos=b.pos,
+                             batch_size=b.batch_size, edge_multiplicity=b.edge_multiplicity, seed_local=b.seed_local,
+                             node_cap=node_cap)
         p.training = int(training)
         p.update_running_stats = int(training)
         p.normalize = int(enc.norm)
@@ -291,14 +278,10 @@ class GinEngine:
         for i in range(L):
             p.agg[i], p.z1[i], p.z2[i] = (ptr(buf["agg"][i]) if backward else None), ptr(buf["z1"][i]), ptr(buf["z2"][i])
         p.stats, p.pooled, p.score, p.feat = ptr(buf["stats"]), ptr(buf["pooled"]), ptr(buf["score"]), ptr(buf["feat"])
-        p.edge_multiplicity = int(getattr(g, "edge_multiplicity", 1))
         p.bn_totals = ptr(buf["bn_totals"]) if training else None
-        seed_local = getattr(g, "seed_local", None)
-        p.seed_local = ptr(seed_local) if seed_local is not None else None
         # replayed step (hipGraph): the Philox key of the dropout masks is read from the device struct (gcc_step_scalars)
         p.scalars = ptr(scalars) if scalars is not None else None
-        p.node_cap = node_cap
-        if self.rows_hint is None:               # API path / tests: the first batch this engine sees sizes the grids (one host read, once;
+        if self.rows_hint is None:              # API path / tests: the first batch this engine sees sizes the grids (one host read, once;
             self.hint_rows(int(g.node_off[g.batch_size].item()))      # the fused steps set it before their first pass, outside any capture)
         p.rows_hint = int(self.rows_hint or 0)   # grid of the tile kernels: an upper estimate of the live rows (0: the capacity)
         key = (slot, node_cap, g.batch_size, L, str(g.node_off.device))
@@ -337,7 +320,7 @@ class GinEngine:
         (gcc_gin_backward_sumsq; not with ``accumulate``) -- the call then returns (targets, number of partials)."""
         ptr = self.ptr
         L = len(enc.gnn.ginlayers)
-        node_cap = _cabi.node_cap(buf["_keepalive"][0])
+        node_cap = p.node_cap
         nbytes = self.lib.gcc_gin_backward_workspace_bytes(node_cap, p.batch_size, L)
         key = ("bwd", nbytes, str(dfeat.device))
         if key not in self._bufs:

@@ -28,8 +28,8 @@ class WideGinEngine:
     def make_pass(self, enc, g, training, keep=None, slot=0, want_pooled=False):
         ptr = self.ptr
         L = len(enc.gnn.ginlayers)
-        node_cap = _cabi.node_cap(g)
-        B, dev = g.batch_size, g.node_off.device
+        b = _cabi.bind_batch(g, ptr, need_graph_id=True)
+        node_cap, B, dev = b.node_cap, b.batch_size, b.device
         d_in = enc.positional_embedding_size + enc.degree_embedding_size + 1
         nbytes = _cabi.size_query(self.lib, "gcc_ginx_workspace_bytes", node_cap, B, L, d_in, enc.hidden, enc.output_dim, named=False)
         key = (slot, nbytes, str(dev))
@@ -39,19 +39,12 @@ class WideGinEngine:
                                  pooled=torch.zeros(L, B, enc.hidden, dtype=torch.float32, device=dev))
         buf = self._ws[key]
         self._gen[key] = self._gen.get(key, 0) + 1
-        if g.pos_undirected is None:
-            raise RuntimeError("the batch has no pos_undirected (run the positional embedding first)")
-        p = _cabi.GccGinxPass()
-        p.node_off, p.row_ptr, p.col_idx, p.graph_id = ptr(g.node_off), ptr(g.row_ptr), ptr(g.col_idx), ptr(g.graph_id)
-        p.pos = ptr(g.pos_undirected)
-        seed_local = getattr(g, "seed_local", None)
-        p.seed_local = ptr(seed_local) if seed_local is not None else None
-        p.batch_size, p.training, p.update_running_stats, p.normalize = B, int(training), int(training), int(enc.norm)
+        p = _cabi.GccGinxPass(node_off=b.node_off, row_ptr=b.row_ptr, col_idx=b.col_idx, graph_id=b.graph_id, pos=b.pos,
+                              seed_local=b.seed_local, batch_size=B, edge_multiplicity=b.edge_multiplicity, node_cap=node_cap)
+        p.training, p.update_running_stats, p.normalize = int(training), int(training), int(enc.norm)
         p.dropout_keep = ptr(keep) if keep is not None else None
         p.hidden, p.out_dim = enc.hidden, enc.output_dim
-        p.edge_multiplicity = int(getattr(g, "edge_multiplicity", 1))
         p.gemm_dtype = _cabi.GEMM_DTYPES[getattr(enc, "encoder_dtype", "f32")]      # (--encoder-dtype: the per-node Linears' operands)
-        p.node_cap = node_cap
         p.w = fill_weights(enc, ptr)
         p.workspace, p.workspace_bytes = ptr(buf["ws"]), nbytes
         p.feat = ptr(buf["feat"])

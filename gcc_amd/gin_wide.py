@@ -202,11 +202,14 @@ class WideResidentEngine:
     def embed(self, enc, views):
         """views: one or two batches (BatchedCSR with pos_undirected) of the same batch size.  -> [B, output_dim] f32."""
         self.refuse(enc)
-        fold = self.folded(enc)
         ptr = self.ptr
-        g0 = views[0]
-        B, L, dev = g0.batch_size, len(fold.layers), g0.node_off.device
-        node_cap = max(_cabi.node_cap(g) for g in views)
+        bound = [_cabi.bind_batch(g, ptr, col_placeholder=True) for g in views]      # (an edge-free batch: the C side refuses a null col_idx)
+        b0 = bound[0]
+        if any(b.batch_size != b0.batch_size or b.edge_multiplicity != b0.edge_multiplicity for b in bound):
+            raise ValueError("the views of one call share batch size and edge multiplicity")
+        fold = self.folded(enc)
+        B, L, dev = b0.batch_size, len(fold.layers), b0.device
+        node_cap = max(b.node_cap for b in bound)
         nbytes = _cabi.size_query(self.lib, "gcc_ginw_embed_workspace_bytes", node_cap, B)
         key = (nbytes, B, L, enc.output_dim, str(dev))
         if key not in self._bufs:
@@ -218,22 +221,10 @@ class WideResidentEngine:
             self.status = torch.zeros(1, dtype=torch.int32, device=dev)
         a = _cabi.GccGinwEmbedArgs(num_views=len(views), batch_size=B, num_layers=L, pos_dim=enc.positional_embedding_size,
                                    deg_emb_dim=enc.degree_embedding_size, max_degree=enc.max_degree,
-                                   edge_multiplicity=max(int(getattr(g0, "edge_multiplicity", 1)), 1), hidden=enc.hidden,
+                                   edge_multiplicity=max(b0.edge_multiplicity, 1), hidden=enc.hidden,
                                    out_dim=enc.output_dim, normalize=int(enc.norm), norm_eps=1e-5, node_cap=node_cap)   # graph_encoder.py:196
-        keep = []
-        for v, g in enumerate(views):
-            if g.batch_size != B or int(getattr(g, "edge_multiplicity", 1)) != int(getattr(g0, "edge_multiplicity", 1)):
-                raise ValueError("the views of one call share batch size and edge multiplicity")
-            if g.pos_undirected is None:
-                raise RuntimeError("the batch has no pos_undirected (run the positional embedding first)")
-            col_idx = g.col_idx
-            if col_idx.numel() == 0:      # an edge-free batch: never read, but the C side refuses a null member
-                col_idx = torch.zeros(1, dtype=torch.int32, device=dev)
-                keep.append(col_idx)
-            a.node_off[v], a.row_ptr[v], a.col_idx[v] = ptr(g.node_off), ptr(g.row_ptr), ptr(col_idx)
-            seed_local = getattr(g, "seed_local", None)
-            a.seed_local[v] = ptr(seed_local) if seed_local is not None else None
-            a.pos[v] = ptr(g.pos_undirected)
+        for v, b in enumerate(bound):
+            a.node_off[v], a.row_ptr[v], a.col_idx[v], a.seed_local[v], a.pos[v] = b.node_off, b.row_ptr, b.col_idx, b.seed_local, b.pos
             a.pooled[v] = ptr(buf["pooled"][v])
         a.degree_embedding = ptr(enc.degree_embedding.weight.detach())
         for i, ly in enumerate(fold.layers):

@@ -71,9 +71,7 @@ class DevicePosEmb:
     def __call__(self, graph, evals=None, raw=None, prof=None):
         out = self._ring[self._next]
         self._next = (self._next + 1) % len(self._ring)
-        c = _cabi.GccBatchOut(node_off=self.ptr(graph.node_off), edge_off=0, parent_nid=0, graph_id=0,
-                              row_ptr=self.ptr(graph.row_ptr), col_idx=self.ptr(graph.col_idx),
-                              node_cap=out.shape[0], edge_cap=graph.col_idx.numel())
+        c = _cabi.batch_out(graph, self.ptr, out.shape[0], csr_only=True)
         st = _cabi.raw_stream(out)
         _cabi.call(self.lib, "gcc_posemb", ctypes.byref(c), self.B, self.hidden, self.ptr(out),
                    self.ptr(evals) if evals is not None else None,
@@ -97,9 +95,7 @@ class DevicePosEmb:
         for i, graph in enumerate(graphs):
             out = self._ring[self._next]
             self._next = (self._next + 1) % len(self._ring)
-            c = _cabi.GccBatchOut(node_off=self.ptr(graph.node_off), edge_off=0, parent_nid=0, graph_id=0,
-                                  row_ptr=self.ptr(graph.row_ptr), col_idx=self.ptr(graph.col_idx),
-                                  node_cap=out.shape[0], edge_cap=graph.col_idx.numel())
+            c = _cabi.batch_out(graph, self.ptr, out.shape[0], csr_only=True)
             keep.append(c)
             views[i] = _cabi.GccPosembView(g=ctypes.addressof(c), pos=self.ptr(out),
                                            evals=self.ptr(evals[i]) if evals is not None else None,

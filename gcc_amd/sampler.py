@@ -26,10 +26,30 @@ class BatchedCSR:
     All tensors are capacity-sized device buffers; the live extents are
     ``node_off[batch_size]`` nodes and ``edge_off[batch_size]`` edges and stay on
     the device (kernels read them there), so building a batch never syncs.
+
+    Every field a consumer may read (int32 tensors unless noted):
+
+    ``batch_size``         subgraphs in the batch, padding rows included
+    ``node_off``           [batch_size + 1] first node of every subgraph
+    ``edge_off``           [batch_size + 1] first CSR entry of every subgraph
+    ``parent_nid``         [cap] node ids in the parent graph; its length IS the node capacity ``cap``
+    ``graph_id``           [>= cap] subgraph of every node
+    ``row_ptr``            [>= cap + 1] CSR rows, global entry offsets
+    ``col_idx``            [edge capacity] neighbours, batch-global node ids
+    ``pos_undirected``     None, or [>= cap, P] f32 once the positional embedding has run
+    ``edge_multiplicity``  every CSR entry counts this many times
+    ``seed_local``         None (the seed is local node 0), or [batch_size] the seed's local index (whole-graph batches)
+    ``valid``              rows that are items of the dataset; the rest pad a partial last batch
+
+    The capacity rule: ``row_ptr.numel() >= cap + 1``, ``graph_id.numel() >= cap`` and ``pos_undirected.shape[0] >= cap`` with
+    ``cap = parent_nid.numel()``.  The encoder kernels read up to the capacity whatever the live count is;
+    :func:`gcc_amd._cabi.bind_batch` refuses a batch that breaks the rule.
     """
 
     def __init__(self, batch_size, node_off, edge_off, parent_nid, graph_id, row_ptr, col_idx):
         self.batch_size = int(batch_size)
+        self.valid = self.batch_size
+        self.seed_local = None
         self.node_off = node_off
         self.edge_off = edge_off
         self.parent_nid = parent_nid
@@ -74,11 +94,7 @@ class BatchedCSR:
                     row_ptr=self.row_ptr[: n + 1].cpu().numpy(), col_idx=self.col_idx[:e].cpu().numpy())
 
     def c_struct(self) -> _cabi.GccBatchOut:
-        return _cabi.GccBatchOut(
-            node_off=self.node_off.data_ptr(), edge_off=self.edge_off.data_ptr(),
-            parent_nid=self.parent_nid.data_ptr(), graph_id=self.graph_id.data_ptr(),
-            row_ptr=self.row_ptr.data_ptr(), col_idx=self.col_idx.data_ptr(),
-            node_cap=self.parent_nid.numel(), edge_cap=self.col_idx.numel())
+        return _cabi.batch_out(self, lambda t: t.data_ptr(), self.parent_nid.numel())
 
 
 class _NData:
@@ -95,8 +111,8 @@ class _NData:
             n = g.number_of_nodes()
             s = torch.zeros(n, dtype=torch.long, device=g.node_off.device)
             first = g.node_off[: g.batch_size].long()
-            local = getattr(g, "seed_local", None)
-            if local is not None:                   # entire_graph=True: the seed keeps its own index, data_util.py:236-237
+            local = g.seed_local
+            if local is not None:                  # entire_graph=True: the seed keeps its own index, data_util.py:236-237
                 keep = (g.node_off[1: g.batch_size + 1] > g.node_off[: g.batch_size])
                 s[(first + local.long())[keep]] = 1
             else:

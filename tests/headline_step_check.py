@@ -9,6 +9,7 @@ Tolerance: north_star's 1e-3 relative (fp32); tighter where it holds."""
 import numpy as np
 import torch
 
+from gcc_amd import _cabi
 from gcc_amd.encoder import grad_params
 from oracle import encoder as E
 
@@ -32,8 +33,7 @@ def _feat(tr, slot, g):
     """the pass's output embeddings (the kernels' 64 channels cut to the model's output width)"""
     if getattr(tr, "wide", False):                       # the any-width step keeps its last passes' buffers (MoCoTrainStep._body)
         return tr.last_bufs[slot[1]]["feat"]
-    node_cap = g.parent_nid.numel() if hasattr(g, "parent_nid") else g.graph_id.numel()
-    f = tr.gin._buffers(slot, node_cap, g.batch_size, tr.L if hasattr(tr, "L") else len(tr.model.gnn.ginlayers),
+    f = tr.gin._buffers(slot, _cabi.node_cap(g), g.batch_size, tr.L if hasattr(tr, "L") else len(tr.model.gnn.ginlayers),
                         g.node_off.device)["feat"]
     assert float(f[:, tr.model.output_dim:].abs().sum()) == 0.0          # padding channels stay exactly zero
     return f[:, : tr.model.output_dim]

@@ -95,7 +95,7 @@ def test_small_hand_built_batch_on_device():
     n = int(batch["node_off"][-1])
     g.batch_size = 4
     g.node_off = batch["node_off"].int().cuda()
-    g.row_ptr = batch["row_ptr"].int().cuda()
+    g.row_ptr = torch.cat([batch["row_ptr"], batch["row_ptr"][-1:].repeat(50)]).int().cuda()     # capacity + 1 entries
     g.col_idx = batch["col_idx"].int().cuda()
     g.graph_id = torch.zeros(n + 50, dtype=torch.int32, device="cuda")
     g.pos_undirected = torch.cat([batch["pos_undirected"], torch.zeros(50, 16)]).cuda()
