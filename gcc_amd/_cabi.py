@@ -262,6 +262,30 @@ STATUS_SVC_NONFINITE = 8
 STATUS_SVC_ITER_CAP = 16
 STATUS_SVC_OVERFLOW = 32
 
+
+class GccLogregArgs(ctypes.Structure):       # gcc_logreg_args: logistic regression on frozen embeddings (csrc/logreg.hip)
+    _fields_ = [
+        ("emb", _VP), ("ld", ctypes.c_int64),
+        ("y", _VP), ("fold_of_row", _VP),
+        ("N", ctypes.c_int32), ("D", ctypes.c_int32), ("classes", ctypes.c_int32), ("folds", ctypes.c_int32),
+        ("iters_per_sync", ctypes.c_int32), ("iter_cap", ctypes.c_int32),
+        ("C", ctypes.c_double), ("tol", ctypes.c_double), ("intercept_penalty", ctypes.c_double),
+        ("pred", _VP), ("decision", _VP), ("counts", _VP), ("coef", _VP), ("intercept", _VP), ("iters", _VP), ("grad", _VP),
+        ("state", _VP), ("unfinished", _VP),
+    ]
+
+
+LR_MAX_ROWS = 65536
+LR_MAX_DIM = 256
+LR_MAX_CLASSES = 256
+LR_MAX_FOLDS = 16
+STATUS_LR_BAD_FOLD = 1                       # the gcc_logreg_* calls' own status word
+STATUS_LR_NONFINITE = 2
+STATUS_LR_ITER_CAP = 4
+STATUS_LR_PIVOT = 8
+STATUS_LR_LINE_SEARCH = 16
+(LR_RUNNING, LR_CONVERGED, LR_CAPPED, LR_ALL_ZERO, LR_ALL_ONE, LR_BAD_PIVOT, LR_NO_DECREASE, LR_NOT_RUN) = range(8)   # a problem's state
+
 CLS_HEAD_MAX_CLASSES = 64
 CLS_HEAD_MAX_DIM = 256
 
@@ -435,6 +459,13 @@ SIGNATURES = {
                                        ctypes.c_void_p]),
     "gcc_svc_predict": (ctypes.c_int32, [ctypes.POINTER(GccSvcArgs), ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p,
                                          ctypes.c_void_p]),
+    "gcc_logreg_workspace_bytes": (ctypes.c_int64, [ctypes.c_int32] * 4),
+    "gcc_logreg_setup": (ctypes.c_int32, [ctypes.POINTER(GccLogregArgs), ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p,
+                                          ctypes.c_void_p]),
+    "gcc_logreg_step": (ctypes.c_int32, [ctypes.POINTER(GccLogregArgs), ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p,
+                                         ctypes.c_void_p]),
+    "gcc_logreg_predict": (ctypes.c_int32, [ctypes.POINTER(GccLogregArgs), ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p,
+                                            ctypes.c_void_p]),
 }
 # symbols declared in the header but not built yet are listed here while the build is in progress
 PENDING = set()

@@ -1,0 +1,178 @@
+"""Node classification on frozen embeddings (gcc/tasks/node_classification.py of the reference, the "GCC (freeze)" column of the
+paper's node-classification table): ``StratifiedKFold(10, shuffle=True, random_state=seed)`` over ``label_matrix.argmax(1)``,
+a one-vs-rest ``LogisticRegression(C=1000)`` per fold, per held-out row the k classes of highest probability (k = the row's label
+count; a row without labels gets every class, the reference's ``argsort()[-0:]``), micro-F1 per fold, the mean as
+``{"Micro-F1": ...}``.
+
+    python -m gcc_amd.tasks.node_classification --dataset usa_airport --emb-path E.npy (--edgelist F --nodelabel F | --labels-npz F) \\
+        [--seed 0] [--device cuda:0|cpu] [--C 1000] [--solver lbfgs|liblinear] [--save-pred OUT.npz]
+    python -m gcc_amd.tasks.node_classification --dataset usa_airport --load-path CKPT --edgelist F --nodelabel F ...
+
+The feature matrix is the table itself, row i for node i.  The labels come from gcc_amd.ingest.read_edgelist (h-index datasets:
+above / not above the median) or from key ``y`` [N, classes] of ``--labels-npz``.  With ``--load-path`` the nodes are embedded on
+the device with the checkpoint first (what ``generate.py --edgelist`` does).  On a GPU all folds and classes are fitted in one
+pass of gcc_amd.logreg.LogRegEngine (gcc_amd/csrc/logreg.hip), which computes the minimiser of sklearn's objective; ``--device
+cpu`` runs sklearn itself, fold by fold, as the reference does.  ``--solver lbfgs`` is the intercept-unpenalised objective of
+scikit-learn >= 0.22, ``liblinear`` the one of the reference's pinned 0.20.3 (the intercept penalised as a feature).
+``--model from_numpy --hidden-size --num-shuffle`` of the reference's command line are accepted and checked, nothing more.
+Prints the reference's result line with the fold count and the Newton iterations added; ``--save-pred`` stores the predicted
+label sets, the folds, the decision values and the labels."""
+from __future__ import annotations
+
+import argparse
+
+import numpy as np
+
+from .graph_classification import fold_ids
+from .similarity_search import load_embedding
+
+FOLDS = 10
+SOLVERS = {"lbfgs": 0.0, "liblinear": 1.0}      # -> the intercept's penalty
+
+
+def top_k(decision, k):
+    """the reference's TopKRanker.predict on decision values: per row the k[r] highest (decision descending, then class
+    ascending); k = 0 selects every class -> uint8 [rows, classes]"""
+    n, classes = decision.shape
+    pred = np.zeros((n, classes), dtype=np.uint8)
+    for r in range(n):
+        order = sorted(range(classes), key=lambda c: (-decision[r, c], c))
+        pred[r, order[: int(k[r]) if k[r] > 0 else classes]] = 1
+    return pred
+
+
+def fold_f1(tp, fp, fn):
+    """micro-F1 as sklearn computes it: 2 tp / (2 tp + fp + fn), 0 without any positive"""
+    den = 2 * tp + fp + fn
+    return float(2 * tp / den) if den > 0 else 0.0
+
+
+def classify_sklearn(emb, y, fold, C, solver):
+    """node_classification.py:64-79 with the folds given: sklearn's one-vs-rest LogisticRegression per fold and the reference's
+    own ranking (argsort of the probabilities) -> (pred uint8 [N, classes], None, counts [folds, 3], 0)"""
+    from sklearn.linear_model import LogisticRegression
+    from sklearn.multiclass import OneVsRestClassifier
+
+    folds = int(fold.max()) + 1
+    emb = np.asarray(emb, dtype=np.float64)                        # (the reference's features_matrix is float64)
+    pred = np.zeros(y.shape, dtype=np.uint8)
+    counts = np.zeros((folds, 3), dtype=np.int64)
+    for f in range(folds):
+        train, test = fold != f, fold == f
+        clf = OneVsRestClassifier(LogisticRegression(C=C, solver=solver)).fit(emb[train], y[train])
+        probs = np.asarray(clf.predict_proba(emb[test]))
+        rows = np.nonzero(test)[0]
+        for i, r in enumerate(rows):
+            k = int(y[r].sum())
+            pred[r, clf.classes_[probs[i].argsort()[-k:]]] = 1     # (k = 0: the whole row, as the reference)
+        counts[f] = _counts(pred[test], y[test])
+    return pred, None, counts, 0
+
+
+def _counts(pred, y):
+    p, t = pred != 0, y != 0
+    return int((p & t).sum()), int((p & ~t).sum()), int((~p & t).sum())
+
+
+def classify_device(emb, y, fold, C, solver, device, engine=None):
+    """-> (pred uint8 [N, classes], decision float64 [N, classes], counts [folds, 3], total Newton iterations)"""
+    import torch
+
+    from .. import _cabi
+    from ..logreg import LogRegEngine
+
+    engine = engine if engine is not None else LogRegEngine()
+    x = torch.from_numpy(np.ascontiguousarray(emb, dtype=np.float32)).to(torch.device(device))
+    res = engine.fit_predict_folds(x, y, fold, C=C, intercept_penalty=SOLVERS[solver])
+    engine.check_status(res, allow_iter_cap=True)
+    if int(res["status"].cpu()[0]) & _cabi.STATUS_LR_ITER_CAP:
+        print("warning: a (fold, class) problem stopped at the iteration cap before tol was reached")
+    return (res["pred"].cpu().numpy(), res["decision"].cpu().numpy(), res["counts"].cpu().numpy().astype(np.int64),
+            int(res["iters"].sum()))
+
+
+def evaluate(emb, y, seed=0, C=1000.0, solver="lbfgs", device="cpu", engine=None, folds=FOLDS):
+    """-> (result {"Micro-F1": mean over the folds, "folds": n, "iterations": Newton iterations or 0}, detail dict(pred, fold,
+    decision or None)).  ``engine``: a gcc_amd.logreg.LogRegEngine (injectable for the emulator tests); sklearn when ``device``
+    is "cpu" and no engine is given."""
+    y = (np.asarray(y) != 0).astype(np.float32)
+    if y.ndim != 2 or emb.shape[0] != y.shape[0]:
+        raise ValueError(f"{emb.shape[0]} embedding rows for a label matrix of shape {y.shape}")
+    if solver not in SOLVERS:
+        raise ValueError(f"solver {solver!r}: one of {sorted(SOLVERS)}")
+    fold = fold_ids(y.argmax(axis=1), seed, folds)
+    if engine is None and str(device) == "cpu":
+        pred, decision, counts, iterations = classify_sklearn(emb, y, fold, C, solver)
+    else:
+        pred, decision, counts, iterations = classify_device(emb, y, fold, C, solver, device, engine)
+    scores = [fold_f1(*(int(v) for v in counts[f])) for f in range(folds)]
+    result = {"Micro-F1": sum(scores) / len(scores), "folds": folds, "iterations": iterations}
+    return result, dict(pred=pred, fold=fold, decision=decision)
+
+
+def load_labels(a):
+    from .. import ingest
+
+    if a.labels_npz is not None:
+        z = np.load(a.labels_npz)
+        if "y" not in z:
+            raise ValueError(f"{a.labels_npz} holds no y")
+        return z["y"]
+    return ingest.read_edgelist(a.edgelist, a.nodelabel, hindex="hindex" in a.dataset)["y"]
+
+
+def embed_nodes(a, pipeline=None):
+    """the nodes embedded with the checkpoint ``--load-path`` (gcc_amd.generate.run) -> float32 [nodes, hidden]"""
+    import torch
+
+    from ..generate import run
+
+    dev = torch.device(a.device)
+    g = argparse.Namespace(load_path=a.load_path, dataset=a.dataset, gpu=dev.index if dev.type == "cuda" else None,
+                           edgelist=a.edgelist, nodelabel=a.nodelabel, ss_graph=None, ss_dict=None, graph_npz=None, graphs_npz=None,
+                           tudataset=None, edge_multiplicity=0, batch_size=a.batch_size, wide_eval="chain", graph_batcher="auto")
+    return run(g, pipeline=pipeline, save=False).numpy()
+
+
+def main(argv=None, pipeline=None, engine=None):
+    ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
+    ap.add_argument("--dataset", required=True, help="the corpus' name, e.g. usa_airport (a name with 'hindex': median labels)")
+    ap.add_argument("--emb-path", default=None)
+    ap.add_argument("--load-path", default=None, help="checkpoint: embed the nodes on the device instead of reading --emb-path")
+    ap.add_argument("--batch-size", type=int, default=256, help="--load-path: nodes embedded per batch")
+    ap.add_argument("--edgelist", default=None)
+    ap.add_argument("--nodelabel", default=None)
+    ap.add_argument("--labels-npz", default=None, help="key y [N, classes]: the label matrix of a corpus without dataset files")
+    ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--device", default="cuda:0")
+    ap.add_argument("--C", type=float, default=1000.0)
+    ap.add_argument("--solver", default="lbfgs", choices=sorted(SOLVERS),
+                    help="lbfgs: the intercept unpenalised (scikit-learn >= 0.22); liblinear: penalised (the reference's 0.20.3)")
+    ap.add_argument("--save-pred", default=None, metavar="OUT.npz")
+    ap.add_argument("--model", default="from_numpy", help="the reference's option: only from_numpy is a frozen table")
+    ap.add_argument("--hidden-size", type=int, default=None, help="the reference's option: checked against the table's width")
+    ap.add_argument("--num-shuffle", type=int, default=10, help="the reference's option: unused there as here")
+    a = ap.parse_args(argv)
+    if a.model != "from_numpy":
+        ap.error("--model: only from_numpy (a frozen embedding table) is served")
+    if (a.emb_path is None) == (a.load_path is None):
+        ap.error("pass --emb-path, or --load-path to embed the nodes")
+    files = a.edgelist is not None or a.nodelabel is not None
+    if files == (a.labels_npz is not None) or (files and (a.edgelist is None or a.nodelabel is None)):
+        ap.error("pass --edgelist F --nodelabel F, or --labels-npz F (dataset files are not bundled)")
+    if a.load_path is not None and a.edgelist is None:
+        ap.error("--load-path embeds the nodes of --edgelist")
+    y = load_labels(a)
+    emb = embed_nodes(a, pipeline) if a.load_path is not None else load_embedding(a.emb_path)
+    if a.hidden_size is not None and emb.shape[1] != a.hidden_size:
+        ap.error(f"--hidden-size {a.hidden_size}, but the table has {emb.shape[1]} columns")
+    result, detail = evaluate(emb, y, a.seed, a.C, a.solver, a.device, engine)
+    if a.save_pred is not None:
+        extra = {} if detail["decision"] is None else dict(decision=detail["decision"])
+        np.savez(a.save_pred, pred=detail["pred"], fold=detail["fold"], labels=np.asarray(y), **extra)
+    print(result)
+    return result
+
+
+if __name__ == "__main__":
+    main()

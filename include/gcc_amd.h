@@ -916,6 +916,64 @@ int32_t gcc_svc_distances(const gcc_svc_args *a, void *workspace, int64_t worksp
 int32_t gcc_svc_solve(const gcc_svc_args *a, void *workspace, int64_t workspace_bytes, int32_t *status, void *stream);
 int32_t gcc_svc_predict(const gcc_svc_args *a, void *workspace, int64_t workspace_bytes, int32_t *status, void *stream);
 
+/* ------------------------------- logistic regression on frozen embeddings ---
+ * gcc/tasks/node_classification.py:53-101 of the reference: StratifiedKFold, then one-vs-rest LogisticRegression(C=1000) per fold
+ * over the columns of an indicator matrix y [N, classes], and per held-out row the k classes of highest probability, k = the
+ * row's label count (0 labels: every class).  Here every (fold, class) is one problem, p = fold * classes + class, over the corpus
+ * rows whose fold id differs from its fold, and all problems run side by side.  A problem computes the minimiser of
+ *   f(w, b) = 1/2 |w|^2 + intercept_penalty 1/2 b^2 + C sum_r [log(1 + exp(z_r)) - t_r z_r],  z_r = w . x_r + b
+ * by damped Newton steps from 0 (exact Hessian on the fp64 matrix cores, Cholesky, Armijo backtracking with constant 1e-4 and
+ * step halving, 64 eps |f| allowed for the rounding of f), everything in float64 on float32 rows, until max|grad f| / C <= tol.  A column that is constant on a fold's
+ * training side is not solved: its decision value is -inf (all zeros) or +inf (all ones).
+ *   gcc_logreg_setup     problem states, w = 0, the gradient at 0; flags fold ids out of range and non-finite embeddings
+ *   gcc_logreg_step      iters_per_sync Newton iterations of every unfinished problem; *unfinished = the problems that need more
+ *   gcc_logreg_predict   decision [N, classes] of every row's own fold, pred (top-k: decision descending, then class ascending),
+ *                        counts [folds, 3] = tp, fp, fn, and the problems' coef / intercept / iters / grad / state
+ * The calls share args and workspace.  Every sum has one fixed order that depends on the sizes alone (no floating-point atomics),
+ * so every output is bit-identical for every iters_per_sync. */
+#define GCC_LR_MAX_ROWS 65536
+#define GCC_LR_MAX_DIM 256
+#define GCC_LR_MAX_CLASSES 256
+#define GCC_LR_MAX_FOLDS 16
+#define GCC_STATUS_LR_BAD_FOLD    1   /* a fold id outside [0, folds): the row trains nothing, pred 0, decision 0 */
+#define GCC_STATUS_LR_NONFINITE   2   /* an embedding is NaN or infinite */
+#define GCC_STATUS_LR_ITER_CAP    4   /* a problem stopped at iter_cap before tol was reached */
+#define GCC_STATUS_LR_PIVOT       8   /* a problem met a non-positive pivot in the Cholesky factorisation and stopped */
+#define GCC_STATUS_LR_LINE_SEARCH 16  /* a problem's step shrank below 2^-40 without a decrease and the problem stopped */
+/* state of a problem: 0 running, 1 converged, 2 at the iteration cap, 3 not solved (all zeros), 4 not solved (all ones),
+ * 5 stopped at a pivot, 6 stopped in the line search, 7 not run (GCC_STATUS_LR_NONFINITE: w = 0) */
+typedef struct gcc_logreg_args {
+    const float *emb; int64_t ld;          /* device [N, ld], ld >= D */
+    const uint8_t *y;                      /* device [N, classes]: non-zero = the row has the label */
+    const int32_t *fold_of_row;            /* device [N]: the fold whose TEST side holds the row */
+    int32_t N, D, classes, folds;
+    int32_t iters_per_sync;                /* gcc_logreg_step: Newton iterations per call, >= 1 */
+    int32_t iter_cap;                      /* total Newton iterations of one problem, >= 1 */
+    double C, tol;
+    double intercept_penalty;              /* rho: 0 = sklearn >= 0.22's objective (lbfgs), 1 = liblinear's */
+    uint8_t *pred;                         /* device [N, classes] */
+    double *decision;                      /* device [N, classes] or NULL */
+    int32_t *counts;                       /* device [folds, 3] or NULL: tp, fp, fn over the fold's held-out rows */
+    double *coef, *intercept;              /* device [folds * classes, D] / [folds * classes] or NULL */
+    int32_t *iters;                        /* device [folds * classes] or NULL */
+    double *grad;                          /* device [folds * classes] or NULL: the last max|grad f| / C */
+    int32_t *state;                        /* device [folds * classes] or NULL */
+    int32_t *unfinished;                   /* device int32[1], gcc_logreg_step */
+} gcc_logreg_args;
+/* bytes of workspace, with P = folds * classes, Dpad = D + 1 rounded up to 16, tiles = (Dpad / 16)(Dpad / 16 + 1) / 2 and
+ * splits = min(64, ceil(1024 / (P tiles)), ceil(N / 64)) row splits (re-derived from their rows, a multiple of 32):
+ *   3 P N 8 (Z, Zd, the Hessian weights) + P splits tiles 2048 (Hessian parts) + P (D + 1)^2 8 where D > 128 (the Cholesky
+ *   that leaves LDS) + P (gsplits + 3) Dpad 8 (gradient parts in gsplits = ceil(N / (ceil(N / 64) rounded up to 256)) <= 64 row
+ *   splits of their own, w, g, d) + 24 P, each array rounded up to 256 bytes.
+ * Negative on a size out of range, and gcc_last_error() names it. */
+int64_t gcc_logreg_workspace_bytes(int32_t N, int32_t D, int32_t classes, int32_t folds);
+/* status: device int32[1], OR-ed, zeroed by the caller.  A size out of range, a NULL member the call needs, ld < D and a short
+ * workspace return rc < 0, name the member in gcc_last_error() and launch nothing.  No host synchronisation in any of them: the
+ * caller reads *unfinished after a gcc_logreg_step and calls again while it is not 0. */
+int32_t gcc_logreg_setup(const gcc_logreg_args *a, void *workspace, int64_t workspace_bytes, int32_t *status, void *stream);
+int32_t gcc_logreg_step(const gcc_logreg_args *a, void *workspace, int64_t workspace_bytes, int32_t *status, void *stream);
+int32_t gcc_logreg_predict(const gcc_logreg_args *a, void *workspace, int64_t workspace_bytes, int32_t *status, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
