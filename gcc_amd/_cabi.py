@@ -286,6 +286,40 @@ STATUS_LR_PIVOT = 8
 STATUS_LR_LINE_SEARCH = 16
 (LR_RUNNING, LR_CONVERGED, LR_CAPPED, LR_ALL_ZERO, LR_ALL_ONE, LR_BAD_PIVOT, LR_NO_DECREASE, LR_NOT_RUN) = range(8)   # a problem's state
 
+PRONE_MAX_DIM = 64
+PRONE_OVERSAMPLE = 10
+PRONE_MAX_STEP = 32
+PRONE_SEGMENT = 32
+PRONE_CHUNK = 1024
+PRONE_MAX_CHUNK = 4096
+(PRONE_MODE_F, PRONE_MODE_FT, PRONE_MODE_M, PRONE_MODE_A1) = range(4)
+(PRONE_TAIL_NONE, PRONE_TAIL_HALF, PRONE_TAIL_CHEB) = range(3)
+STATUS_PRONE_BAD_CSR = 1                     # the gcc_prone_* calls' own status word
+STATUS_PRONE_DUPLICATE = 2
+STATUS_PRONE_SPLIT_FULL = 4
+STATUS_PRONE_RANK = 8
+STATUS_PRONE_SWEEPS = 16
+STATUS_PRONE_SINGULAR = 32
+
+
+class GccProneArgs(ctypes.Structure):        # gcc_prone_args: ProNE node embeddings of a parent graph (csrc/prone.hip)
+    _fields_ = [
+        ("row_ptr", _VP), ("col_idx", _VP),
+        ("n", ctypes.c_int64), ("nnz", ctypes.c_int64),
+        ("d", ctypes.c_int32), ("step", ctypes.c_int32), ("chunk", ctypes.c_int32),
+        ("mode", ctypes.c_int32), ("tail", ctypes.c_int32), ("k", ctypes.c_int32),
+        ("mu", ctypes.c_double), ("alpha", ctypes.c_double), ("beta", ctypes.c_double),
+        ("bessel", ctypes.c_double * PRONE_MAX_STEP),
+        ("r", _VP), ("c", _VP),
+        ("x", _VP), ("z", _VP), ("w", _VP),
+        ("y", _VP), ("conv", _VP),
+        ("rfac", _VP),
+        ("omega", _VP),
+        ("emb", _VP), ("emb32", _VP),
+        ("sigma", _VP),
+    ]
+
+
 CLS_HEAD_MAX_CLASSES = 64
 CLS_HEAD_MAX_DIM = 256
 
@@ -466,6 +500,15 @@ SIGNATURES = {
                                          ctypes.c_void_p]),
     "gcc_logreg_predict": (ctypes.c_int32, [ctypes.POINTER(GccLogregArgs), ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p,
                                             ctypes.c_void_p]),
+    "gcc_prone_workspace_bytes": (ctypes.c_int64, [ctypes.c_int64, ctypes.c_int64, ctypes.c_int32]),
+    "gcc_prone_node_terms": (ctypes.c_int32, [ctypes.POINTER(GccProneArgs), ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p,
+                                              ctypes.c_void_p]),
+    "gcc_prone_spmm": (ctypes.c_int32, [ctypes.POINTER(GccProneArgs), ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p,
+                                        ctypes.c_void_p]),
+    "gcc_prone_orthonormalize": (ctypes.c_int32, [ctypes.POINTER(GccProneArgs), ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p,
+                                                  ctypes.c_void_p]),
+    "gcc_prone_embed": (ctypes.c_int32, [ctypes.POINTER(GccProneArgs), ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p,
+                                         ctypes.c_void_p]),
 }
 # symbols declared in the header but not built yet are listed here while the build is in progress
 PENDING = set()

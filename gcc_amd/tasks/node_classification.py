@@ -7,6 +7,8 @@ count; a row without labels gets every class, the reference's ``argsort()[-0:]``
     python -m gcc_amd.tasks.node_classification --dataset usa_airport --emb-path E.npy (--edgelist F --nodelabel F | --labels-npz F) \\
         [--seed 0] [--device cuda:0|cpu] [--C 1000] [--solver lbfgs|liblinear] [--save-pred OUT.npz]
     python -m gcc_amd.tasks.node_classification --dataset usa_airport --load-path CKPT --edgelist F --nodelabel F ...
+    python -m gcc_amd.tasks.node_classification --dataset usa_airport --model prone --hidden-size 64 --edgelist F --nodelabel F \\
+        [--prone-seed S] [--save-emb OUT.npy]
 
 The feature matrix is the table itself, row i for node i.  The labels come from gcc_amd.ingest.read_edgelist (h-index datasets:
 above / not above the median) or from key ``y`` [N, classes] of ``--labels-npz``.  With ``--load-path`` the nodes are embedded on
@@ -15,6 +17,9 @@ pass of gcc_amd.logreg.LogRegEngine (gcc_amd/csrc/logreg.hip), which computes th
 cpu`` runs sklearn itself, fold by fold, as the reference does.  ``--solver lbfgs`` is the intercept-unpenalised objective of
 scikit-learn >= 0.22, ``liblinear`` the one of the reference's pinned 0.20.3 (the intercept penalised as a feature).
 ``--model from_numpy --hidden-size --num-shuffle`` of the reference's command line are accepted and checked, nothing more.
+``--model prone`` is the reference's ProNE baseline (gcc/models/emb/prone.py): the table is computed from ``--edgelist`` first, on
+the device by gcc_amd.prone.ProNEEngine (gcc_amd/csrc/prone.hip) or, with ``--device cpu``, by its float64 NumPy restatement;
+``--hidden-size`` (default 64) is its width, ``--prone-seed`` (default ``--seed``) the seed of the range finder's test matrix.
 Prints the reference's result line with the fold count and the Newton iterations added; ``--save-pred`` stores the predicted
 label sets, the folds, the decision values and the labels."""
 from __future__ import annotations
@@ -134,7 +139,23 @@ def embed_nodes(a, pipeline=None):
     return run(g, pipeline=pipeline, save=False).numpy()
 
 
-def main(argv=None, pipeline=None, engine=None):
+def embed_prone(a, prone_engine=None):
+    """the ProNE table of ``--edgelist`` (gcc/tasks/__init__.py: build_model("prone")) -> float32 [nodes, hidden]"""
+    from .. import ingest
+    from ..prone import ProNEEngine, embed_numpy
+
+    g = ingest.read_edgelist(a.edgelist)
+    d = 64 if a.hidden_size is None else a.hidden_size
+    seed = a.seed if a.prone_seed is None else a.prone_seed
+    if prone_engine is None and str(a.device) == "cpu":
+        return embed_numpy(g["row_ptr"], g["col_idx"], d, seed=seed)["emb32"]
+    engine = prone_engine if prone_engine is not None else ProNEEngine(device=a.device)
+    res = engine.embed(g["row_ptr"], g["col_idx"], d, seed=seed)
+    engine.check_status(res)
+    return res["emb32"].cpu().numpy()
+
+
+def main(argv=None, pipeline=None, engine=None, prone_engine=None):
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
     ap.add_argument("--dataset", required=True, help="the corpus' name, e.g. usa_airport (a name with 'hindex': median labels)")
     ap.add_argument("--emb-path", default=None)
@@ -149,13 +170,23 @@ def main(argv=None, pipeline=None, engine=None):
     ap.add_argument("--solver", default="lbfgs", choices=sorted(SOLVERS),
                     help="lbfgs: the intercept unpenalised (scikit-learn >= 0.22); liblinear: penalised (the reference's 0.20.3)")
     ap.add_argument("--save-pred", default=None, metavar="OUT.npz")
-    ap.add_argument("--model", default="from_numpy", help="the reference's option: only from_numpy is a frozen table")
-    ap.add_argument("--hidden-size", type=int, default=None, help="the reference's option: checked against the table's width")
+    ap.add_argument("--model", default="from_numpy", help="the reference's option: from_numpy (a frozen table) or prone (the baseline)")
+    ap.add_argument("--hidden-size", type=int, default=None,
+                    help="the reference's option: checked against the table's width; --model prone: the width (default 64)")
+    ap.add_argument("--prone-seed", type=int, default=None, help="--model prone: the seed of the range finder's test matrix (default --seed)")
+    ap.add_argument("--save-emb", default=None, metavar="OUT.npy", help="--model prone: store the float32 table")
     ap.add_argument("--num-shuffle", type=int, default=10, help="the reference's option: unused there as here")
     a = ap.parse_args(argv)
-    if a.model != "from_numpy":
-        ap.error("--model: only from_numpy (a frozen embedding table) is served")
-    if (a.emb_path is None) == (a.load_path is None):
+    if a.model not in ("from_numpy", "prone"):
+        ap.error("--model: only from_numpy (a frozen embedding table) and prone (the ProNE baseline) are served")
+    if a.model == "prone":
+        if a.emb_path is not None or a.load_path is not None:
+            ap.error("--model prone computes the table: it takes neither --emb-path nor --load-path")
+        if a.edgelist is None or a.nodelabel is None or a.labels_npz is not None:
+            ap.error("--model prone needs --edgelist F --nodelabel F")
+    elif a.save_emb is not None or a.prone_seed is not None:
+        ap.error("--save-emb and --prone-seed go with --model prone")
+    elif (a.emb_path is None) == (a.load_path is None):
         ap.error("pass --emb-path, or --load-path to embed the nodes")
     files = a.edgelist is not None or a.nodelabel is not None
     if files == (a.labels_npz is not None) or (files and (a.edgelist is None or a.nodelabel is None)):
@@ -163,7 +194,12 @@ def main(argv=None, pipeline=None, engine=None):
     if a.load_path is not None and a.edgelist is None:
         ap.error("--load-path embeds the nodes of --edgelist")
     y = load_labels(a)
-    emb = embed_nodes(a, pipeline) if a.load_path is not None else load_embedding(a.emb_path)
+    if a.model == "prone":
+        emb = embed_prone(a, prone_engine)
+        if a.save_emb is not None:
+            np.save(a.save_emb, emb)
+    else:
+        emb = embed_nodes(a, pipeline) if a.load_path is not None else load_embedding(a.emb_path)
     if a.hidden_size is not None and emb.shape[1] != a.hidden_size:
         ap.error(f"--hidden-size {a.hidden_size}, but the table has {emb.shape[1]} columns")
     result, detail = evaluate(emb, y, a.seed, a.C, a.solver, a.device, engine)

@@ -974,6 +974,75 @@ int32_t gcc_logreg_setup(const gcc_logreg_args *a, void *workspace, int64_t work
 int32_t gcc_logreg_step(const gcc_logreg_args *a, void *workspace, int64_t workspace_bytes, int32_t *status, void *stream);
 int32_t gcc_logreg_predict(const gcc_logreg_args *a, void *workspace, int64_t workspace_bytes, int32_t *status, void *stream);
 
+/* ---- ProNE node embeddings of a parent graph (csrc/prone.hip): the baseline of the reference's node classification
+ * (gcc/models/emb/prone.py).  Input: a simple undirected graph as symmetric CSR in node-id order, rows sorted, no self loops.
+ * Everything is float64; k = d + 10 is the width of the randomized range finder.
+ *   node terms   r_i = -log(deg_i), s_j = sum_{i in N(j)} 1 / deg_i, c_j = -log(s_j^0.75 / sum_j s_j^0.75).  The factorised
+ *                matrix F has A's pattern and the values F_ij = r_i + c_j; it is never stored.
+ *   products     y = op x (+ tail) for x, y [n, k] row-major (gcc_prone_spmm), op one of GCC_PRONE_MODE_*.
+ *   orthonormalisation  CholeskyQR2 of y [n, k] in place (gcc_prone_orthonormalize).
+ *   the pipeline  sklearn's randomized_svd(F, d, n_iter=5) from a given Omega, svd_flip (per column the entry of largest
+ *                magnitude positive, ties to the lowest row), U sqrt(Sigma), rows L2-normalised; then the Chebyshev-Gaussian
+ *                propagation of `step` terms and the same finish on the thin SVD of its result (gcc_prone_embed).
+ * ORDER OF A ROW'S SUM: the neighbours are taken in CSR order in segments of GCC_PRONE_SEGMENT; a segment is summed left to
+ * right, the segment sums are added as a binary counter adds them (two sums of 2^l segments each make one of 2^(l+1); what is
+ * left at the end is added from the lowest level up).  A row longer than `chunk` neighbours is split into parts of `chunk`, one
+ * wave group each, whose sums go to the workspace and are added by the same rule; `chunk` is GCC_PRONE_SEGMENT times a power of
+ * two, so every chunk gives the same bits.  No floating-point atomics anywhere: every sum depends on the sizes alone. */
+#define GCC_PRONE_MAX_DIM 64
+#define GCC_PRONE_OVERSAMPLE 10
+#define GCC_PRONE_MAX_K (GCC_PRONE_MAX_DIM + GCC_PRONE_OVERSAMPLE)
+#define GCC_PRONE_MAX_STEP 32
+#define GCC_PRONE_SEGMENT 32
+#define GCC_PRONE_CHUNK 1024          /* neighbours of one part of a split row (args.chunk = 0) */
+#define GCC_PRONE_MAX_CHUNK 4096
+#define GCC_PRONE_POWER_ITERS 5       /* randomized_svd's n_iter */
+#define GCC_PRONE_MODE_F  0           /* y_i = sum_{j in N(i)} (r_i + c_j) x_j */
+#define GCC_PRONE_MODE_FT 1           /* y_i = sum_{j in N(i)} (r_j + c_i) x_j */
+#define GCC_PRONE_MODE_M  2           /* m_i = ((1 - 1/(deg_i + 1)) - mu) x_i - (sum_{j in N(i)} x_j) / (deg_i + 1), then the tail */
+#define GCC_PRONE_MODE_A1 3           /* y_i = (x_i - z_i) + sum_{j in N(i)} (x_j - z_j) */
+#define GCC_PRONE_TAIL_NONE 0         /* y = m */
+#define GCC_PRONE_TAIL_HALF 1         /* y = 0.5 m - z;  conv = alpha z + beta y      (prone.py l.91-94) */
+#define GCC_PRONE_TAIL_CHEB 2         /* y = (m - 2 z) - w;  conv += alpha y          (prone.py l.97-102); y may be w */
+#define GCC_STATUS_PRONE_BAD_CSR    1   /* row_ptr not ascending from 0 to nnz, a column outside [0, n), a self loop or an unsorted row */
+#define GCC_STATUS_PRONE_DUPLICATE  2   /* a repeated entry in a row: a multigraph parent */
+#define GCC_STATUS_PRONE_SPLIT_FULL 4   /* the split rows of this chunk do not fit the workspace */
+#define GCC_STATUS_PRONE_RANK       8   /* orthonormalisation met a pivot that is not positive: the range lost rank */
+#define GCC_STATUS_PRONE_SWEEPS    16   /* the eigensolver stopped at its sweep limit */
+#define GCC_STATUS_PRONE_SINGULAR  32   /* a singular value not above n eps sigma_1 */
+/* any of BAD_CSR, SPLIT_FULL, RANK and SINGULAR ends the call where it is met: the kernels after it return at once, and an output
+ * that was not reached keeps what it held: the zeros gcc_prone_embed puts there first, or the factorisation's rows when the
+ * propagation's decomposition is what failed.  No NaN is written. */
+typedef struct gcc_prone_args {
+    const int32_t *row_ptr, *col_idx;      /* device [n + 1], [nnz] */
+    int64_t n, nnz;                        /* both within int32 */
+    int32_t d;                             /* 2..GCC_PRONE_MAX_DIM; n >= d + 10 */
+    int32_t step;                          /* gcc_prone_embed: 1..GCC_PRONE_MAX_STEP; 1 returns the factorisation's rows */
+    int32_t chunk;                         /* 0: GCC_PRONE_CHUNK; else GCC_PRONE_SEGMENT 2^j up to GCC_PRONE_MAX_CHUNK */
+    int32_t mode, tail, k;                 /* gcc_prone_spmm / gcc_prone_orthonormalize: columns of x and y, 1..GCC_PRONE_MAX_K */
+    double mu;                             /* gcc_prone_embed, GCC_PRONE_MODE_M */
+    double alpha, beta;                    /* gcc_prone_spmm: the tail's coefficients */
+    double bessel[GCC_PRONE_MAX_STEP];     /* gcc_prone_embed: I_i(theta), i < step */
+    double *r, *c;                         /* device [n] or NULL (then the workspace holds them) */
+    const double *x, *z, *w;               /* gcc_prone_spmm: device [n, k]; y must not be x */
+    double *y, *conv;                      /* gcc_prone_spmm out; gcc_prone_orthonormalize: y in place */
+    double *rfac;                          /* gcc_prone_orthonormalize: device [2, k, k] or NULL: R of the two passes, y_in = q R2 R1 */
+    const double *omega;                   /* gcc_prone_embed: device [n, d + 10] */
+    double *emb; float *emb32;             /* gcc_prone_embed out: device [n, d] */
+    double *sigma;                         /* gcc_prone_embed out: device [2, d] (factorisation, propagation) or NULL */
+} gcc_prone_args;
+/* bytes of workspace: r, c, the split rows' lists and partial sums (2 nnz / GCC_PRONE_CHUNK + 64 parts of 80 float64), the Gram
+ * partials, the small factors, n d float64 of projected rows and max(2 n (d + 10), 5 n d) float64 of iterates.  Negative on a
+ * size out of range, and gcc_last_error() names it. */
+int64_t gcc_prone_workspace_bytes(int64_t n, int64_t nnz, int32_t d);
+/* status: device int32[1], OR-ed, zeroed by the caller.  A size out of range, a NULL member the call needs and a short workspace
+ * return rc < 0, name the member in gcc_last_error() and launch nothing.  No host synchronisation in any of them.  The calls share
+ * args and workspace; gcc_prone_spmm in modes F / FT reads r and c (gcc_prone_node_terms, or the caller's own). */
+int32_t gcc_prone_node_terms(const gcc_prone_args *a, void *workspace, int64_t workspace_bytes, int32_t *status, void *stream);
+int32_t gcc_prone_spmm(const gcc_prone_args *a, void *workspace, int64_t workspace_bytes, int32_t *status, void *stream);
+int32_t gcc_prone_orthonormalize(const gcc_prone_args *a, void *workspace, int64_t workspace_bytes, int32_t *status, void *stream);
+int32_t gcc_prone_embed(const gcc_prone_args *a, void *workspace, int64_t workspace_bytes, int32_t *status, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
