@@ -1,130 +1,66 @@
-"""Kernel-logic parity on CPU for the MoCo / InfoNCE head (gcc_amd/csrc/nce.hip on
-the wave64 emulator) vs the reference-generated golden vectors and the oracle."""
-import os
-
+"""Kernel-logic parity on CPU for the MoCo / InfoNCE head (gcc_amd/csrc/nce.hip on the wave64 emulator) vs the
+reference-generated golden vectors and the oracle, and for the E2E head at ragged batch sizes, the optimizer tail at ragged
+sizes and the enqueue against float64 restatements: the checks of tests/nce_check.py, which tests/test_nce_gpu.py runs on the
+device."""
 import pytest
-import torch
 
-from gcc_amd.contrast import MemoryMoCo, NceEngine, NCESoftmaxLoss, NCESoftmaxLossNS, e2e_logits
-from oracle import encoder as E
+from gcc_amd.contrast import NceEngine
+from tests import nce_check as C
 from tests.hipemu.emu_driver import emu_lib
-
-GOLD = torch.load(os.path.join(os.path.dirname(__file__), "golden", "encoder_golden.pt"), weights_only=False)
 
 
 def emu_nce():
     return NceEngine(lib=emu_lib(), ptr=lambda t: 0 if t is None else t.data_ptr())
 
 
-def test_moco_head_matches_reference_golden():
-    g = GOLD["moco"]
-    contrast = MemoryMoCo(64, None, g["K"], g["T"], use_softmax=True)
-    contrast._engine = emu_nce()
-    contrast.load_state_dict({"params": torch.tensor([-1]), "memory": g["init"]["memory"].clone()})
-    q = g["feat_q"].clone().requires_grad_(True)
-    dense_before = contrast.logits(q, g["feat_k"])
-    torch.testing.assert_close(dense_before, g["out"], rtol=1e-5, atol=1e-5)
-    out = contrast(q, g["feat_k"])
-    assert tuple(out.shape) == tuple(g["out"].shape)
-    loss = NCESoftmaxLoss()(out)
-    torch.testing.assert_close(loss, g["loss"], rtol=1e-5, atol=1e-6)
-    torch.testing.assert_close(out[:, 0].mean(), g["prob"], rtol=1e-5, atol=1e-6)
-    torch.testing.assert_close(out.prob, g["prob"], rtol=1e-5, atol=1e-6)
-    # the queue now holds the keys (memory_moco.py:55-61) and the ring pointer advanced
-    torch.testing.assert_close(contrast.memory, g["after"]["memory"])
-    assert contrast.index == g["after"]["index"]
-    # dense logits on demand are those of the queue BEFORE the enqueue
-    torch.testing.assert_close(out.dense(), g["out"], rtol=1e-5, atol=1e-5)
-    loss.backward()
-    torch.testing.assert_close(q.grad, g["dfeat_q"], rtol=1e-4, atol=1e-7)
+@pytest.fixture(scope="module")
+def S():
+    return C.head("emu")
 
 
-@pytest.mark.parametrize("B,K", [(1, 1), (5, 7), (70, 200), (130, 64)])
-def test_moco_head_ragged_shapes_vs_oracle(B, K):
-    torch.manual_seed(B * 1000 + K)
-    q = torch.nn.functional.normalize(torch.randn(B, 64), dim=1).requires_grad_(True)
-    k = torch.nn.functional.normalize(torch.randn(B, 64), dim=1)
-    mem = E.memory_init(K, 64)
-    index0 = K // 3
-    ref_mem = mem.clone()
-    qo = q.detach().clone().requires_grad_(True)
-    out_ref, idx_ref = E.moco_forward(ref_mem, index0, qo, k, 0.07) if B <= K else (None, None)
-    if out_ref is None:
-        pytest.skip("the reference's index_copy_ needs B <= K")
-    loss_ref = E.nce_softmax_loss(out_ref)
-    loss_ref.backward()
-    contrast = MemoryMoCo(64, None, K, 0.07, use_softmax=True)
-    contrast._engine = emu_nce()
-    contrast.memory.copy_(mem)
-    contrast.index = index0
-    out = contrast(q, k)
-    torch.testing.assert_close(out.loss, loss_ref.detach(), rtol=1e-5, atol=1e-6)
-    torch.testing.assert_close(contrast.memory, ref_mem)
-    assert contrast.index == idx_ref
-    torch.testing.assert_close(out.dense(), out_ref.detach(), rtol=1e-5, atol=1e-5)
-    out.loss.backward()
-    torch.testing.assert_close(q.grad, qo.grad, rtol=1e-4, atol=1e-7)
+def test_moco_head_matches_reference_golden(S):
+    C.check_moco_golden(S)
 
 
-def test_e2e_head_matches_reference_golden():
-    g = GOLD["e2e"]
-    fq = g["feat_q"].clone().requires_grad_(True)
-    fk = g["feat_k"].clone().requires_grad_(True)
-    out = e2e_logits(fq, fk, 0.07, engine=emu_nce())
-    loss = NCESoftmaxLossNS()(out)
-    torch.testing.assert_close(loss, g["loss"], rtol=1e-5, atol=1e-6)
-    torch.testing.assert_close(out.prob, g["prob"], rtol=1e-5, atol=1e-6)
-    torch.testing.assert_close(out.dense(), g["out"], rtol=1e-5, atol=1e-5)
-    rq = g["feat_q"].clone().requires_grad_(True)
-    rk = g["feat_k"].clone().requires_grad_(True)
-    E.nce_softmax_loss_ns(rk @ rq.t() / 0.07).backward()
-    loss.backward()
-    torch.testing.assert_close(fq.grad, rq.grad, rtol=1e-4, atol=1e-7)
-    torch.testing.assert_close(fk.grad, rk.grad, rtol=1e-4, atol=1e-7)
+@pytest.mark.parametrize("B,K", C.RAGGED)
+def test_moco_head_ragged_shapes_vs_oracle(S, B, K):
+    C.check_ragged_vs_oracle(S, B, K)
 
 
-def test_ema_matches_moment_update():
-    torch.manual_seed(0)
-    p, e = torch.randn(1000), torch.randn(1000)
-    ref = e * 0.999 + (1 - 0.999) * p
-    emu_nce().ema(e, p, 0.999)
-    torch.testing.assert_close(e, ref, rtol=1e-6, atol=1e-7)
+def test_e2e_head_matches_reference_golden(S):
+    C.check_e2e_golden(S)
 
 
-def _bf16_round(t):
-    return t.to(torch.bfloat16).to(torch.float32)
+def test_ema_matches_moment_update(S):
+    C.check_ema(S)
 
 
 @pytest.mark.parametrize("B,K", [(6, 48), (70, 200)])
-def test_bf16_head_equals_the_oracle_on_rounded_operands_and_bounds_the_distance_to_f32(B, K):
-    """GCC_NCE_BF16 (north_star's throughput mode of the head): q, k and the queue rounded to bf16 on load, products on
-    the bf16 matrix instruction, fp32 accumulation / softmax.  (1) It must equal the fp32 oracle evaluated on the rounded
-    operands (only the summation order differs) -- loss, dense logits, dq.  (2) Against the unrounded fp32 oracle the
-    logits move by <= 2^-8 |q||k| / T each; the test states what that does to the loss at T = 0.07: a few 1e-3
-    absolute, so north_star's 1e-3 parity bar holds for the f32 mode only, which stays the default."""
-    torch.manual_seed(K)
-    q = torch.nn.functional.normalize(torch.randn(B, 64), dim=1)
-    k = torch.nn.functional.normalize(torch.randn(B, 64), dim=1)
-    mem = E.memory_init(K, 64)
-    # oracle on rounded operands
-    qr = _bf16_round(q).requires_grad_(True)
-    out_r, _ = E.moco_forward(_bf16_round(mem), 0, qr, _bf16_round(k), 0.07)
-    loss_r = E.nce_softmax_loss(out_r)
-    loss_r.backward()
-    out_f, _ = E.moco_forward(mem.clone(), 0, q.clone(), k, 0.07)
-    loss_f = E.nce_softmax_loss(out_f)
-    contrast = MemoryMoCo(64, None, K, 0.07, use_softmax=True, nce_dtype="bf16")
-    contrast._engine = NceEngine(lib=emu_lib(), ptr=lambda t: 0 if t is None else t.data_ptr(), dtype="bf16")
-    contrast.memory.copy_(mem)
-    qd = q.clone().requires_grad_(True)
-    dense = contrast.logits(qd, k)
-    torch.testing.assert_close(dense, out_r.detach(), rtol=1e-5, atol=2e-5)
-    out = contrast(qd, k)
-    loss = NCESoftmaxLoss()(out)
-    torch.testing.assert_close(loss, loss_r.detach(), rtol=1e-5, atol=2e-6)
-    loss.backward()
-    torch.testing.assert_close(qd.grad, qr.grad, rtol=1e-4, atol=1e-7)
-    torch.testing.assert_close(contrast.memory[:B], k)                      # the queue itself stays fp32
-    err = abs(float(loss.detach()) - float(loss_f.detach()))
-    assert err < 2e-2, err                                                   # bf16 operands at T = 0.07: not a 1e-3 mode
-    assert (dense - out_f.detach()).abs().max() < 64 * 2.0 ** -8 / 0.07 * 0.2
+def test_bf16_head_equals_the_oracle_on_rounded_operands_and_bounds_the_distance_to_f32(S, B, K):
+    C.check_bf16_head(S, B, K)
+
+
+@pytest.mark.parametrize("dtype", ["f32", "bf16"])
+@pytest.mark.parametrize("B", C.E2E_B)
+def test_e2e_head_ragged_batch_sizes(S, B, dtype):
+    C.check_e2e_ragged(S, B, dtype)
+
+
+@pytest.mark.parametrize("n", C.ADAM_N)
+def test_adam_step_ragged_sizes(S, n):
+    C.check_adam(S, n)
+
+
+@pytest.mark.parametrize("tail", C.ADAM_TAILS)
+@pytest.mark.parametrize("n", C.ADAM_N)
+def test_adam_ema_step_ragged_sizes_and_tail_past_the_live_prefix(S, n, tail):
+    C.check_adam(S, n, tail)
+
+
+@pytest.mark.parametrize("n", C.ADAM_N)
+def test_ema_ragged_sizes(S, n):
+    C.check_ema_ragged(S, n)
+
+
+def test_enqueue_full_queue_wrap_at_the_first_key_and_refusal(S):
+    C.check_enqueue(S)
