@@ -320,6 +320,27 @@ class GccProneArgs(ctypes.Structure):        # gcc_prone_args: ProNE node embedd
     ]
 
 
+GRAPHWAVE_ORDER = 30
+GRAPHWAVE_MAX_DIM = 256
+GRAPHWAVE_MAX_NODES = 65536
+GRAPHWAVE_MAX_WIDTH = 4096
+GRAPHWAVE_ROW_BLOCK = 128
+STATUS_GRAPHWAVE_BAD_CSR = 1                 # the gcc_graphwave_* calls' own status word
+
+
+class GccGraphwaveArgs(ctypes.Structure):    # gcc_graphwave_args: GraphWave node embeddings of a parent graph (csrc/graphwave.hip)
+    _fields_ = [
+        ("row_ptr", _VP), ("col_idx", _VP),
+        ("n_rows", ctypes.c_int64), ("nnz", ctypes.c_int64),
+        ("d", ctypes.c_int32), ("width", ctypes.c_int32), ("heat_chunk", ctypes.c_int32), ("reserved", ctypes.c_int32),
+        ("coeff", (ctypes.c_double * (GRAPHWAVE_ORDER + 1)) * 2),
+        ("time_points", ctypes.c_double * (GRAPHWAVE_MAX_DIM // 4)),
+        ("threshold", ctypes.c_double),
+        ("chi", _VP), ("chi32", _VP),
+        ("heat", _VP),
+    ]
+
+
 CLS_HEAD_MAX_CLASSES = 64
 CLS_HEAD_MAX_DIM = 256
 
@@ -509,6 +530,12 @@ SIGNATURES = {
                                                   ctypes.c_void_p]),
     "gcc_prone_embed": (ctypes.c_int32, [ctypes.POINTER(GccProneArgs), ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p,
                                          ctypes.c_void_p]),
+    "gcc_graphwave_panel_width": (ctypes.c_int64, [ctypes.c_int64, ctypes.c_int32, ctypes.c_int32]),
+    "gcc_graphwave_workspace_bytes": (ctypes.c_int64, [ctypes.c_int64, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32]),
+    "gcc_graphwave_heat": (ctypes.c_int32, [ctypes.POINTER(GccGraphwaveArgs), ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p,
+                                            ctypes.c_void_p]),
+    "gcc_graphwave_embed": (ctypes.c_int32, [ctypes.POINTER(GccGraphwaveArgs), ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p,
+                                             ctypes.c_void_p]),
 }
 # symbols declared in the header but not built yet are listed here while the build is in progress
 PENDING = set()

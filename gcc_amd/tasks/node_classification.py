@@ -9,6 +9,8 @@ count; a row without labels gets every class, the reference's ``argsort()[-0:]``
     python -m gcc_amd.tasks.node_classification --dataset usa_airport --load-path CKPT --edgelist F --nodelabel F ...
     python -m gcc_amd.tasks.node_classification --dataset usa_airport --model prone --hidden-size 64 --edgelist F --nodelabel F \\
         [--prone-seed S] [--save-emb OUT.npy]
+    python -m gcc_amd.tasks.node_classification --dataset usa_airport --model graphwave --hidden-size 64 --edgelist F --nodelabel F \\
+        [--save-emb OUT.npy]
 
 The feature matrix is the table itself, row i for node i.  The labels come from gcc_amd.ingest.read_edgelist (h-index datasets:
 above / not above the median) or from key ``y`` [N, classes] of ``--labels-npz``.  With ``--load-path`` the nodes are embedded on
@@ -20,6 +22,9 @@ scikit-learn >= 0.22, ``liblinear`` the one of the reference's pinned 0.20.3 (th
 ``--model prone`` is the reference's ProNE baseline (gcc/models/emb/prone.py): the table is computed from ``--edgelist`` first, on
 the device by gcc_amd.prone.ProNEEngine (gcc_amd/csrc/prone.hip) or, with ``--device cpu``, by its float64 NumPy restatement;
 ``--hidden-size`` (default 64) is its width, ``--prone-seed`` (default ``--seed``) the seed of the range finder's test matrix.
+``--model graphwave`` is the reference's GraphWave baseline (gcc/models/emb/graphwave.py): the table of characteristic-function
+samples of the heat wavelets, on the device by gcc_amd.graphwave.GraphWaveEngine (gcc_amd/csrc/graphwave.hip) or, with ``--device
+cpu``, by its float64 NumPy restatement; ``--hidden-size`` (default 64, a multiple of 4) is its width.  It draws nothing.
 Prints the reference's result line with the fold count and the Newton iterations added; ``--save-pred`` stores the predicted
 label sets, the folds, the decision values and the labels."""
 from __future__ import annotations
@@ -155,7 +160,23 @@ def embed_prone(a, prone_engine=None):
     return res["emb32"].cpu().numpy()
 
 
-def main(argv=None, pipeline=None, engine=None, prone_engine=None):
+def embed_graphwave(a, graphwave_engine=None):
+    """the GraphWave table of ``--edgelist`` (gcc/tasks/__init__.py: build_model("graphwave")) -> float32 [nodes, hidden]"""
+    from .. import ingest
+    from ..graphwave import GraphWaveEngine, check_width, embed_numpy
+
+    g = ingest.read_edgelist(a.edgelist)
+    d = 64 if a.hidden_size is None else a.hidden_size
+    check_width(d)
+    if graphwave_engine is None and str(a.device) == "cpu":
+        return embed_numpy(g["row_ptr"], g["col_idx"], d)["chi32"]
+    engine = graphwave_engine if graphwave_engine is not None else GraphWaveEngine(device=a.device)
+    res = engine.embed(g["row_ptr"], g["col_idx"], d)
+    engine.check_status(res)
+    return res["chi32"].cpu().numpy()
+
+
+def main(argv=None, pipeline=None, engine=None, prone_engine=None, graphwave_engine=None):
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
     ap.add_argument("--dataset", required=True, help="the corpus' name, e.g. usa_airport (a name with 'hindex': median labels)")
     ap.add_argument("--emb-path", default=None)
@@ -170,22 +191,26 @@ def main(argv=None, pipeline=None, engine=None, prone_engine=None):
     ap.add_argument("--solver", default="lbfgs", choices=sorted(SOLVERS),
                     help="lbfgs: the intercept unpenalised (scikit-learn >= 0.22); liblinear: penalised (the reference's 0.20.3)")
     ap.add_argument("--save-pred", default=None, metavar="OUT.npz")
-    ap.add_argument("--model", default="from_numpy", help="the reference's option: from_numpy (a frozen table) or prone (the baseline)")
+    ap.add_argument("--model", default="from_numpy", help="the reference's option: from_numpy (a frozen table), prone or graphwave (the baselines)")
     ap.add_argument("--hidden-size", type=int, default=None,
-                    help="the reference's option: checked against the table's width; --model prone: the width (default 64)")
+                    help="the reference's option: checked against the table's width; --model prone / graphwave: the width (default 64)")
     ap.add_argument("--prone-seed", type=int, default=None, help="--model prone: the seed of the range finder's test matrix (default --seed)")
-    ap.add_argument("--save-emb", default=None, metavar="OUT.npy", help="--model prone: store the float32 table")
+    ap.add_argument("--save-emb", default=None, metavar="OUT.npy", help="--model prone / graphwave: store the float32 table")
     ap.add_argument("--num-shuffle", type=int, default=10, help="the reference's option: unused there as here")
     a = ap.parse_args(argv)
-    if a.model not in ("from_numpy", "prone"):
-        ap.error("--model: only from_numpy (a frozen embedding table) and prone (the ProNE baseline) are served")
-    if a.model == "prone":
+    if a.model not in ("from_numpy", "prone", "graphwave"):
+        ap.error("--model: only from_numpy (a frozen embedding table), prone and graphwave (the baselines) are served")
+    if a.model in ("prone", "graphwave"):
         if a.emb_path is not None or a.load_path is not None:
-            ap.error("--model prone computes the table: it takes neither --emb-path nor --load-path")
+            ap.error(f"--model {a.model} computes the table: it takes neither --emb-path nor --load-path")
         if a.edgelist is None or a.nodelabel is None or a.labels_npz is not None:
-            ap.error("--model prone needs --edgelist F --nodelabel F")
+            ap.error(f"--model {a.model} needs --edgelist F --nodelabel F")
+        if a.model == "graphwave" and a.prone_seed is not None:
+            ap.error("--prone-seed goes with --model prone (GraphWave draws nothing)")
+        if a.model == "graphwave" and a.hidden_size is not None and (a.hidden_size % 4 != 0 or not 4 <= a.hidden_size <= 256):
+            ap.error(f"--model graphwave: --hidden-size {a.hidden_size} must be a multiple of 4 in 4..256")
     elif a.save_emb is not None or a.prone_seed is not None:
-        ap.error("--save-emb and --prone-seed go with --model prone")
+        ap.error("--save-emb goes with --model prone / graphwave, --prone-seed with --model prone")
     elif (a.emb_path is None) == (a.load_path is None):
         ap.error("pass --emb-path, or --load-path to embed the nodes")
     files = a.edgelist is not None or a.nodelabel is not None
@@ -194,8 +219,8 @@ def main(argv=None, pipeline=None, engine=None, prone_engine=None):
     if a.load_path is not None and a.edgelist is None:
         ap.error("--load-path embeds the nodes of --edgelist")
     y = load_labels(a)
-    if a.model == "prone":
-        emb = embed_prone(a, prone_engine)
+    if a.model in ("prone", "graphwave"):
+        emb = embed_prone(a, prone_engine) if a.model == "prone" else embed_graphwave(a, graphwave_engine)
         if a.save_emb is not None:
             np.save(a.save_emb, emb)
     else:

@@ -5,10 +5,16 @@ keys by cosine similarity, and Recall@k says how often the same author is among 
     python -m gcc_amd.tasks.similarity_search --dataset kdd_icdm --emb-path-1 A.npy --emb-path-2 B.npy \\
         [--data-root data/panther] [--k 20 40] [--device cuda:0|cpu] [--save-topk out.npz]
     python -m gcc_amd.tasks.similarity_search --dataset kdd_icdm --load-path CKPT [--batch-size 256] [--save-emb DIR] ...
+    python -m gcc_amd.tasks.similarity_search --dataset kdd_icdm --model graphwave [--hidden-size 64] [--save-emb DIR] ...
 
 With ``--load-path`` the two tables need not exist: both networks are embedded on the device with the checkpoint (what
 ``generate.py --ss-graph`` does: the weighted network as the multigraph the reference builds, one row per node of the graph
 file) and handed to the search without a trip through disk; ``--save-emb DIR`` stores them as ``DIR/<network>.npy``.
+
+``--model graphwave`` is the reference's GraphWave baseline (gcc/models/emb/graphwave.py): both networks, as the multigraphs of
+``read_ss_graph(csr=True)`` (one row per node of the graph file, parallel edges counted), are embedded by
+gcc_amd.graphwave.GraphWaveEngine (gcc_amd/csrc/graphwave.hip) or, with ``--device cpu``, by its float64 NumPy restatement, and the
+two tables are searched as above.  ``--model from_numpy`` (the default) is the search of given or checkpoint-made tables.
 
 ``--dataset a_b`` reads ``<data-root>/a.graph``, ``a.dict``, ``b.graph`` and ``b.dict`` (gcc_amd.ingest.read_ss_graph).  On a
 GPU the search is one gcc_sim_search call (gcc_amd/simsearch.py); ``--device cpu`` runs the same rule in NumPy float64.  Among
@@ -148,30 +154,62 @@ def embed_networks(data_root, dataset, load_path, batch_size=256, device="cuda:0
     return tables
 
 
-def main(argv=None, pipeline=None, engine=None):
+def embed_graphwave(data_root, dataset, hidden_size=64, device="cuda:0", graphwave_engine=None):
+    """Both networks of ``dataset`` as GraphWave tables -> [table 1, table 2], float32 [nodes of the graph file, hidden_size]"""
+    from ..graphwave import GraphWaveEngine, check_width, embed_numpy
+
+    check_width(hidden_size)
+    tables = []
+    for name in dataset.split("_"):
+        g = read_ss_graph(os.path.join(data_root, name + ".graph"), os.path.join(data_root, name + ".dict"), csr=True)
+        if graphwave_engine is None and str(device) == "cpu":
+            tables.append(embed_numpy(g["row_ptr"], g["col_idx"], hidden_size)["chi32"])
+            continue
+        eng = graphwave_engine if graphwave_engine is not None else GraphWaveEngine(device=device)
+        res = eng.embed(g["row_ptr"], g["col_idx"], hidden_size)
+        eng.check_status(res)
+        tables.append(res["chi32"].cpu().numpy())
+    return tables
+
+
+def main(argv=None, pipeline=None, engine=None, graphwave_engine=None):
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
     ap.add_argument("--dataset", required=True, help="<network 1>_<network 2>, e.g. kdd_icdm")
     ap.add_argument("--emb-path-1", default=None)
     ap.add_argument("--emb-path-2", default=None)
     ap.add_argument("--load-path", default=None, help="checkpoint: embed both networks on the device instead of reading --emb-path-1/-2")
     ap.add_argument("--batch-size", type=int, default=256, help="--load-path: nodes embedded per batch")
-    ap.add_argument("--save-emb", default=None, metavar="DIR", help="--load-path: store the two tables as DIR/<network>.npy")
+    ap.add_argument("--save-emb", default=None, metavar="DIR", help="--load-path / --model graphwave: store the two tables as DIR/<network>.npy")
+    ap.add_argument("--model", default="from_numpy", choices=["from_numpy", "graphwave"],
+                    help="the reference's option: from_numpy (tables that exist or --load-path makes) or graphwave (the baseline)")
+    ap.add_argument("--hidden-size", type=int, default=None, help="--model graphwave: the tables' width (default 64, a multiple of 4); else checked against the tables' width")
     ap.add_argument("--data-root", default=os.path.join("data", "panther"))
     ap.add_argument("--k", type=int, nargs="+", default=[20, 40])
     ap.add_argument("--device", default="cuda:0")
     ap.add_argument("--save-topk", default=None, metavar="OUT.npz")
     a = ap.parse_args(argv)
-    if a.load_path is None and (a.emb_path_1 is None or a.emb_path_2 is None):
+    if a.model == "graphwave":
+        if a.load_path is not None or a.emb_path_1 is not None or a.emb_path_2 is not None:
+            ap.error("--model graphwave computes the tables: it takes neither --emb-path-1/-2 nor --load-path")
+        hidden = 64 if a.hidden_size is None else a.hidden_size
+        if hidden % 4 != 0 or not 4 <= hidden <= 256:
+            ap.error(f"--model graphwave: --hidden-size {hidden} must be a multiple of 4 in 4..256")
+    elif a.load_path is None and (a.emb_path_1 is None or a.emb_path_2 is None):
         ap.error("pass --emb-path-1 and --emb-path-2, or --load-path to embed the two networks")
     dict_1, dict_2 = load_dicts(a.data_root, a.dataset)
-    if a.load_path is not None:
-        emb_1, emb_2 = embed_networks(a.data_root, a.dataset, a.load_path, a.batch_size, a.device, pipeline)
+    if a.model == "graphwave" or a.load_path is not None:
+        if a.model == "graphwave":
+            emb_1, emb_2 = embed_graphwave(a.data_root, a.dataset, hidden, a.device, graphwave_engine)
+        else:
+            emb_1, emb_2 = embed_networks(a.data_root, a.dataset, a.load_path, a.batch_size, a.device, pipeline)
         if a.save_emb is not None:
             os.makedirs(a.save_emb, exist_ok=True)
             for name, emb in zip(a.dataset.split("_"), (emb_1, emb_2)):
                 np.save(os.path.join(a.save_emb, name + ".npy"), emb)
     else:
         emb_1, emb_2 = load_embedding(a.emb_path_1), load_embedding(a.emb_path_2)
+    if a.hidden_size is not None and not emb_1.shape[1] == emb_2.shape[1] == a.hidden_size:
+        ap.error(f"--hidden-size {a.hidden_size}, but the tables have {emb_1.shape[1]} and {emb_2.shape[1]} columns")
     result, detail = evaluate(emb_1, emb_2, dict_1, dict_2, a.k, a.device, with_topk=a.save_topk is not None, engine=engine)
     if a.save_topk is not None:
         names = np.array(detail["names"])

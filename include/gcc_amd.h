@@ -1043,6 +1043,52 @@ int32_t gcc_prone_spmm(const gcc_prone_args *a, void *workspace, int64_t workspa
 int32_t gcc_prone_orthonormalize(const gcc_prone_args *a, void *workspace, int64_t workspace_bytes, int32_t *status, void *stream);
 int32_t gcc_prone_embed(const gcc_prone_args *a, void *workspace, int64_t workspace_bytes, int32_t *status, void *stream);
 
+/* ---- GraphWave node embeddings of a parent graph (csrc/graphwave.hip): the second baseline of the reference's node
+ * classification and similarity search (gcc/models/emb/graphwave.py), as the reference calls it.  Input: an undirected graph as
+ * symmetric CSR in node-id order, rows sorted, no self loops; a repeated entry is a parallel edge and counts.  Everything is
+ * float64.  With n the number of rows that have an entry (a row without one is a node id outside the graph: it takes part in no
+ * mean and its row of the table is zero) and T = d / 4:
+ *   operator     M = -D^-1/2 A D^-1/2, deg_i = the entries of row i, 1 / sqrt(deg_i) = 0 for an empty row.
+ *   heat         H_i = sum_{k = 0..GCC_GRAPHWAVE_ORDER} coeff[i][k] T_k(M), T_0 = I, T_1 = M, T_k = 2 M T_{k-1} - T_{k-2}, computed
+ *                on panels of W source columns ([n_rows, W] row-major), one launch per order; then x -> x > threshold / n ? x : 0.
+ *   table        chi[u][i 2T + 2j] = (sum_v cos(time_points[j] H_i[v][u])) / n, chi[u][i 2T + 2j + 1] the same with sin.
+ * ORDER OF THE SUMS: a row's product sum takes the neighbours in CSR order in segments of GCC_PRONE_SEGMENT, a segment left to
+ * right, the segments as a binary counter adds them (see above).  A column's sum over the rows takes blocks of
+ * GCC_GRAPHWAVE_ROW_BLOCK rows from row 0 (four runs of 32 rows, left to right, added as (0 + 1) + (2 + 3)), the blocks by the
+ * same counter.  Neither depends on W or on the grid: every panel width gives the same bits.  No floating-point atomics. */
+#define GCC_GRAPHWAVE_ORDER 30
+#define GCC_GRAPHWAVE_MAX_DIM 256
+#define GCC_GRAPHWAVE_MAX_NODES 65536
+#define GCC_GRAPHWAVE_MAX_WIDTH 4096
+#define GCC_GRAPHWAVE_ROW_BLOCK 128
+#define GCC_STATUS_GRAPHWAVE_BAD_CSR 1  /* row_ptr not ascending from 0 to nnz, a column outside [0, n_rows), a self loop or an unsorted row */
+/* GCC_STATUS_GRAPHWAVE_BAD_CSR ends the call where it is met: the kernels after it return at once and the outputs keep the zeros
+ * the call puts there first.  No NaN is written. */
+typedef struct gcc_graphwave_args {
+    const int32_t *row_ptr, *col_idx;      /* device [n_rows + 1], [nnz] */
+    int64_t n_rows, nnz;                   /* 2..GCC_GRAPHWAVE_MAX_NODES; nnz within int32 */
+    int32_t d;                             /* a multiple of 4 in 4..GCC_GRAPHWAVE_MAX_DIM */
+    int32_t width;                         /* columns of a panel: 0 (gcc_graphwave_panel_width's default) or a multiple of 64 */
+    int32_t heat_chunk;                    /* gcc_graphwave_heat: the panel, columns [heat_chunk W, (heat_chunk + 1) W) */
+    int32_t reserved;
+    double coeff[2][GCC_GRAPHWAVE_ORDER + 1];          /* the Chebyshev coefficients of the two scales */
+    double time_points[GCC_GRAPHWAVE_MAX_DIM / 4];     /* the first d / 4 are read */
+    double threshold;                      /* divided by n on the device (the reference: 1e-4) */
+    double *chi; float *chi32;             /* gcc_graphwave_embed out: device [n_rows, d] */
+    double *heat;                          /* gcc_graphwave_heat out: device [2, n_rows, W], after the threshold; rows and columns
+                                            * of empty rows and columns past n_rows are zero */
+} gcc_graphwave_args;
+/* the columns of one panel: `width` itself (a multiple of 64 up to GCC_GRAPHWAVE_MAX_WIDTH), or for 0 the widest multiple of 64
+ * up to 2048 whose workspace stays within 256 MiB, at most n_rows rounded up to 64.  Negative on a size out of range. */
+int64_t gcc_graphwave_panel_width(int64_t n_rows, int32_t d, int32_t width);
+/* bytes of workspace: n_rows float64 of node scales, four panels [n_rows, W] (two Chebyshev iterates, two heat sums) and the
+ * row blocks' partial sums [n_rows / GCC_GRAPHWAVE_ROW_BLOCK, d, W].  Negative on a size out of range, gcc_last_error() names it. */
+int64_t gcc_graphwave_workspace_bytes(int64_t n_rows, int64_t nnz, int32_t d, int32_t width);
+/* status: device int32[1], OR-ed, zeroed by the caller.  A size out of range, a NULL member the call needs and a short workspace
+ * return rc < 0, name the member in gcc_last_error() and launch nothing.  No host synchronisation in either. */
+int32_t gcc_graphwave_heat(const gcc_graphwave_args *a, void *workspace, int64_t workspace_bytes, int32_t *status, void *stream);
+int32_t gcc_graphwave_embed(const gcc_graphwave_args *a, void *workspace, int64_t workspace_bytes, int32_t *status, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
