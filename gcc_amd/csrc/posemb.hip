@@ -2591,6 +2591,13 @@ constexpr int kChRowsPerThread = kNodeMax / kChThreads;   // rows of the deflate
 #else
 #define GCC_CHEB_REG_CAP __attribute__((amdgpu_waves_per_eu(GCC_POSEMB_CH_THREADS / 256 + 1)))   // its waves per SIMD + one: <= 168 VGPRs at 512
 #endif
+// The matrix build gives a row of at most 64 entries to a group of lanes: 8 at 1024 threads, so that one pass of the
+// workgroup covers 128 rows whatever its size (never fewer than 4 lanes: a row's first entries stay in registers)
+constexpr int kChGrp = kChThreads / 128 < 4 ? 4 : kChThreads / 128;
+constexpr int kChGrpRows = kChThreads / kChGrp;            // rows per pass
+constexpr int kChGrpPasses = kNodeMax / kChGrpRows;        // passes that cover the largest item
+static_assert((kChGrp & (kChGrp - 1)) == 0 && 64 % kChGrp == 0 && kNodeMax % kChGrpRows == 0, "lane groups of the matrix build");
+constexpr int kChOrderWave = 16;     // group parents with more entries than this are numbered by a wave, not a thread
 constexpr int kChCsrCap = 12288;     // directed edges of the deflated subgraph (uint16 column ids in LDS)
 #ifndef GCC_POSEMB_CH_LONGDEG
 #define GCC_POSEMB_CH_LONGDEG 32
@@ -2612,6 +2619,26 @@ constexpr float kChTol = 2e-5f;      // residual norm of the wanted Ritz pairs
 constexpr double kChShift = 1e-8;
 constexpr float kChAmpLog = 12.9f;  // ln of the largest filter amplification between two re-orthonormalisations (4e5; at 1e7 fp32 loses the guard end and one hub ego-net in 29 misses the strict invariants)
 constexpr int kChBw = 32;            // inverse iterations of the Ritz problem per batch
+
+// Sum over each half of the wave (lanes 0-31 / 32-63), in every lane of the half, by the tree wave_sum walks when the other
+// half holds zeros: wave_sum(v) of a wave whose upper 32 lanes are +0 has the bits of this sum of its lower half, and a row
+// placed in the upper half is added in the same order.  (half32_sum is a different tree on both tiers.)
+__device__ __forceinline__ float half32_tree_sum(float v)
+{
+#ifdef GCC_AMD_HIPEMU
+    for (int d = 16; d >= 1; d >>= 1) v += wave_shfl_xor(v, d);      // wave_sum's butterfly without its first stage (+ 0)
+    return v;
+#else
+    v += dpp_or_zero<0x111, 0xF>(v);      // wave_scan_incl_dpp without its last stage: row_shr:1, 2, 4, 8 ...
+    v += dpp_or_zero<0x112, 0xF>(v);
+    v += dpp_or_zero<0x114, 0xF>(v);
+    v += dpp_or_zero<0x118, 0xF>(v);
+    v += dpp_or_zero<0x142, 0xA>(v);      // ... and row_bcast:15: lanes 31 / 63 hold the sums of rows 0 + 1 / 2 + 3
+    const float t31 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 31));
+    const float t63 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 63));
+    return lane_id() < 32 ? t31 : t63;
+#endif
+}
 
 struct LdsYes { static constexpr bool value = true; };
 struct LdsNo { static constexpr bool value = false; };
@@ -2670,7 +2697,7 @@ __global__ __launch_bounds__(kChThreads) GCC_CHEB_REG_CAP void posemb_cheb_kerne
     __shared__ uint8_t chunk_row[kChMaxChunks], rowx[kNodeMax];      // long-row index of a chunk / of a row (0xFF: short)
     __shared__ int sh_clen, sh_long_t;
     __shared__ int wsum[kChThreads / 64 + 1];
-    __shared__ int sh_item, sh_tot[3], sh_nlong, sh_nchunk, sh_fail;
+    __shared__ int sh_item, sh_tot[3], sh_nlong, sh_nchunk, sh_fail, sh_nlongrow;
     __shared__ int colsrc[64];
     constexpr int kCls = kClsCheb;
     const PosMulti &m = ca.m;
@@ -2711,12 +2738,45 @@ __global__ __launch_bounds__(kChThreads) GCC_CHEB_REG_CAP void posemb_cheb_kerne
     Defl d;
     defl_bind(d, region, kNodeMax);
     for (int i = tid; i < n; i += kChThreads) defl_init_node(d, i, rp, a.col_idx, n0);
-    if (tid == 0) { sh_fail = 0; sh_nlong = 0; sh_nchunk = 0; }
+    if (tid == 0) { sh_fail = 0; sh_nlong = 0; sh_nchunk = 0; sh_nlongrow = 0; }
     __syncthreads();
     for (int i = tid; i < n; i += kChThreads) defl_count_node(d, i, rp, a.col_idx, n0, hd.use_stalks != 0);
     __syncthreads();
-    for (int p = tid; p < n; p += kChThreads) defl_order_node(d, p, rp, a.col_idx, n0);
+    // order inside the groups.  defl_order_node walks its parent's row alone, one dependent global load per entry: a hub row
+    // of 400 entries was ~70 us of this phase with 1,023 threads waiting behind it.  Group parents with more than kChOrderWave
+    // entries are listed and numbered by whole waves (ballot prefix, 64 entries per round, rows round-robin) to the same tables.
+    uint16_t *longlist = (uint16_t *)slab;                   // [<= kNodeMax] (the slab is free until the products; defl_prefix_block's scratch between the two uses)
+    for (int p = tid; p < n; p += kChThreads) {
+        if (rp[p + 1] - rp[p] > kChOrderWave && (d.tcnt[p] >= 2 || d.pcnt[p] >= 2)) longlist[atomicAdd(&sh_nlongrow, 1)] = (uint16_t)p;
+        else defl_order_node(d, p, rp, a.col_idx, n0);
+    }
     __syncthreads();
+    for (int x = wv, nx = sh_nlongrow; x < nx; x += kNW) {   // wave-uniform
+        const int p = longlist[x];
+        const bool lt = d.tcnt[p] >= 2, st = d.pcnt[p] >= 2;
+        int o = 0, q = 0;
+        for (int e0 = rp[p]; e0 < rp[p + 1]; e0 += 64) {     // rows are sorted: the members of a group in index order
+            const bool in = e0 + lane < rp[p + 1];
+            const int j = in ? a.col_idx[e0 + lane] - n0 : 0;
+            const bool tw = in && lt && d.par[j] == (uint16_t)p;
+            const bool sk = in && !tw && st && d.phub[j] == (uint16_t)p;
+            const unsigned long long mt = wave_ballot(tw), ms = wave_ballot(sk);
+            if (tw) {
+                const int r = o + __popcll(mt & lanemask_lt());
+                if (r == 0) d.rep[p] = (uint16_t)j;
+                d.ord[j] = (uint16_t)r;
+            }
+            if (sk) {
+                const int r = q + __popcll(ms & lanemask_lt());
+                if (r == 0) d.prep[p] = (uint16_t)j;
+                d.ord[j] = (uint16_t)r;
+            }
+            o += __popcll(mt);
+            q += __popcll(ms);
+        }
+    }
+    __syncthreads();
+    if (tid == 0) sh_nlongrow = 0;                           // (the matrix build lists its long rows behind the barriers of the prefix)
     defl_prefix_block<kChThreads>(d, n, sh_tot, (int *)slab);
     const int nr = sh_tot[0], z = sh_tot[1], zp = sh_tot[2];
     // ---- sparse M' = diag(scale) A' diag(scale): rows of the kept nodes, columns ascending; a super-leaf standing for t
@@ -2738,8 +2798,44 @@ __global__ __launch_bounds__(kChThreads) GCC_CHEB_REG_CAP void posemb_cheb_kerne
     }
     for (int r = tid; r <= nr; r += kChThreads) crow[r] = 0;
     __syncthreads();
-    for (int i = wv; i < n; i += kNW) {                      // kept neighbours per kept row
-        if (d.ridx[i] == kNone) continue;                    // wave-uniform
+    // Kept neighbours per kept row, then (behind the prefix) the column fill.  A row of at most 64 entries belongs to a group
+    // of kChGrp lanes, so one pass of the workgroup covers kChGrpRows rows (one wave per row was 25 dependent rounds of
+    // rp -> col_idx -> ridx per loop at n = 400, 58 of 64 lanes idle).  A group owns its slice of the wave's ballot: the kept
+    // entries land in ccol in their original order, repeated entries of a multigraph row stay repeated.  What the first
+    // round of a pass read (the row's bounds, its reduced index and the reduced columns of its first kChGrp entries) stays in
+    // registers for the fill; only longer rows read their entries again.  Rows of more than 64 entries are listed (in any
+    // order: a row's outputs do not depend on who writes them) and taken wave-wide by the waves round-robin, as before.
+    const int gl = lane & (kChGrp - 1), grp = tid / kChGrp;
+    const unsigned long long gmask = ((1ull << kChGrp) - 1ull) << (lane - gl);     // this group's lanes of the ballot
+    int g_e0[kChGrpPasses], g_len[kChGrpPasses], g_ri[kChGrpPasses], g_rj[kChGrpPasses];
+#pragma unroll
+    for (int p = 0; p < kChGrpPasses; ++p) {                 // the rows' bounds, all passes in flight
+        const int i = p * kChGrpRows + grp;
+        g_ri[p] = i < n ? (int)d.ridx[i] : (int)kNone;
+        g_e0[p] = i < n ? rp[i] : 0;
+        g_len[p] = g_ri[p] != (int)kNone ? rp[i + 1] - g_e0[p] : 0;
+        if (g_len[p] > 64) {
+            if (gl == 0) longlist[atomicAdd(&sh_nlongrow, 1)] = (uint16_t)i;
+            g_len[p] = 0;                                    // not this group's
+        }
+    }
+#pragma unroll
+    for (int p = 0; p < kChGrpPasses; ++p)                   // the first kChGrp entries of every row
+        g_rj[p] = gl < g_len[p] ? (int)d.ridx[a.col_idx[g_e0[p] + gl] - n0] : (int)kNone;
+#pragma unroll
+    for (int p = 0; p < kChGrpPasses; ++p) {
+        if (p * kChGrpRows >= n) break;                      // block-uniform
+        int c = __popcll(wave_ballot(g_rj[p] != (int)kNone) & gmask);
+        for (int r = kChGrp; wave_ballot(r < g_len[p]) != 0ull; r += kChGrp) {     // wave-uniform: the longest row of the wave
+            const bool keep = r + gl < g_len[p] && d.ridx[a.col_idx[g_e0[p] + r + gl] - n0] != kNone;
+            c += __popcll(wave_ballot(keep) & gmask);
+        }
+        if (gl == 0 && g_ri[p] != (int)kNone && g_len[p] > 0) crow[g_ri[p] + 1] = (uint16_t)c;
+    }
+    __syncthreads();
+    const int nlongrow = sh_nlongrow;
+    for (int x = wv; x < nlongrow; x += kNW) {               // wave-uniform
+        const int i = longlist[x];
         int c = 0;
         for (int e0 = rp[i]; e0 < rp[i + 1]; e0 += 64) {
             const int e = e0 + lane;
@@ -2772,8 +2868,22 @@ __global__ __launch_bounds__(kChThreads) GCC_CHEB_REG_CAP void posemb_cheb_kerne
     }
     __syncthreads();
     if (!sh_fail) {
-        for (int i = wv; i < n; i += kNW) {
-            if (d.ridx[i] == kNone) continue;
+#pragma unroll
+        for (int p = 0; p < kChGrpPasses; ++p) {
+            if (p * kChGrpRows >= n) break;                  // block-uniform
+            int at = g_len[p] > 0 ? (int)crow[g_ri[p]] : 0;
+            unsigned long long mk = wave_ballot(g_rj[p] != (int)kNone) & gmask;
+            if (g_rj[p] != (int)kNone) ccol[at + __popcll(mk & lanemask_lt())] = (uint16_t)g_rj[p];
+            at += __popcll(mk);
+            for (int r = kChGrp; wave_ballot(r < g_len[p]) != 0ull; r += kChGrp) {
+                const int rj = r + gl < g_len[p] ? (int)d.ridx[a.col_idx[g_e0[p] + r + gl] - n0] : (int)kNone;
+                mk = wave_ballot(rj != (int)kNone) & gmask;
+                if (rj != (int)kNone) ccol[at + __popcll(mk & lanemask_lt())] = (uint16_t)rj;
+                at += __popcll(mk);
+            }
+        }
+        for (int x = wv; x < nlongrow; x += kNW) {
+            const int i = longlist[x];
             int at = (int)crow[d.ridx[i]];
             for (int e0 = rp[i]; e0 < rp[i + 1]; e0 += 64) {
                 const int e = e0 + lane;
@@ -3194,37 +3304,62 @@ __global__ __launch_bounds__(kChThreads) GCC_CHEB_REG_CAP void posemb_cheb_kerne
 #pragma unroll
                 for (int c = 0; c < 32; ++c) ar[c] = live ? G[lane * P + cb + c] : 0.0;
                 if (half == 1) {                                 // replay steps 0..31 on the right half
+                    double ln = Lt[lane];                        // (the column of the next step is in flight while this one's is applied)
 #pragma unroll 1
                     for (int k = 0; k < 32; ++k) {
-                        const double l = Lt[k * P + lane];       // 0 above the diagonal (written below)
+                        const double l = ln;                     // 0 above the diagonal (written below)
+                        ln = Lt[(k < 31 ? k + 1 : 31) * P + lane];
 #pragma unroll
                         for (int u = 0; u < 32; ++u) ar[u] = fma(-l, wave_readlane(l, 32 + u), ar[u]);
                     }
                 }
-                double cap = ar[0];
+                // The chain of a column step -- pivot broadcast, fp64 sqrt and division, scaled column, update of the NEXT
+                // column -- waits on itself most of the time, and the update of the other columns does not depend on it.
+                // So step k updates column k + 1 first, broadcasts its pivot, judges it and scales the column by
+                // 1 / sqrt(pivot) in one basic block with the update of the last eight columns (always right of k), whose
+                // independent instructions fill the chain's stalls; the blocks left of them follow as before.  The same
+                // operations on the same operands (column k + 1 is computed twice, to the same bits).  The rank test still
+                // stops the factorisation before a rejected pivot's column is stored or applied; its reciprocal (and the
+                // one of whatever follows the half's last column) is computed and dropped.
+                double piv = wave_readlane(ar[0], cb);
+                bool ok = piv > 0.1 * kChShift;
+                double l = (live && lane >= cb) ? ar[0] * (1.0 / sqrt(piv)) : 0.0;         // L[lane][k] of the coming step
 #pragma unroll 1
                 for (int k = cb; k < cb + 32; ++k) {
-                    const double piv = wave_readlane(cap, k);
-                    if (!(piv > 0.1 * kChShift)) {               // wave-uniform: the block lost its numerical rank
+                    if (!ok) {                                   // wave-uniform: the block lost its numerical rank
 #ifdef GCC_AMD_HIPEMU
                         if (getenv("GCC_POSEMB_DEBUG") && lane == 0) fprintf(stderr, "cheb chol fail round=%d col=%d piv=%g\n", round, k, piv);
 #endif
                         bad = true;
                         break;
                     }
-                    const double l = (live && lane >= k) ? cap * (1.0 / sqrt(piv)) : 0.0;  // L[lane][k]
                     if (live) Lt[k * P + lane] = l;
+                    const int kn = k + 1 - cb;                   // the next column (32: none in this half)
+                    double nx = 0.0;
 #pragma unroll
                     for (int jb = 0; jb < 4; ++jb) {
-                        if (cb + 8 * jb + 7 > k) {               // wave-uniform: some column of the block is right of k
+                        if ((kn >> 3) == jb) {                   // wave-uniform
 #pragma unroll
-                            for (int u = 0; u < 8; ++u) {
-                                const int j = 8 * jb + u;
-                                ar[j] = fma(-l, wave_readlane(l, cb + j), ar[j]);
-                                if (cb + j == k + 1) cap = ar[j];
-                            }
+                            for (int t = 0; t < 8; ++t)
+                                if ((kn & 7) == t) nx = ar[8 * jb + t];
                         }
                     }
+                    nx = fma(-l, wave_readlane(l, (k + 1) & 63), nx);
+                    piv = wave_readlane(nx, (k + 1) & 63);
+                    ok = piv > 0.1 * kChShift;
+                    const double lnx = nx * (1.0 / sqrt(piv));
+                    keep_alive(lnx);                             // (computed here by every lane: sunk behind a branch on `live`, the chain is fenced off from the updates)
+                    const double ln = (live && lane > k) ? lnx : 0.0;
+#pragma unroll
+                    for (int j = 24; j < 32; ++j) ar[j] = fma(-l, wave_readlane(l, cb + j), ar[j]);
+#pragma unroll
+                    for (int jb = 0; jb < 3; ++jb) {
+                        if (cb + 8 * jb + 7 > k) {               // wave-uniform: some column of the block is right of k
+#pragma unroll
+                            for (int u = 0; u < 8; ++u) ar[8 * jb + u] = fma(-l, wave_readlane(l, cb + 8 * jb + u), ar[8 * jb + u]);
+                        }
+                    }
+                    l = ln;
                 }
             }
             if (bad && lane == 0) sh_fail = 1;
@@ -3531,14 +3666,31 @@ __global__ __launch_bounds__(kChThreads) GCC_CHEB_REG_CAP void posemb_cheb_kerne
         for (int i = tid; i < a.hidden; i += kChThreads)
             a.evals[(int64_t)b * a.hidden + i] = i < k ? (colsrc[i] >= 0 ? theta[colsrc[i]] : kStalkEig) : 0.f;
     }
-    for (int v = wv; v < n; v += kNW) {
-        const int rsrc = xrec[4 * v], o = xrec[4 * v + 1], g = xrec[4 * v + 2], cb = xrec[4 * v + 3];
-        const float val = lane < k ? defl_expand(rsrc, o, g, cb, colsrc[lane], XA, P) : 0.f;
-        const float s2 = wave_sum(val * val);
-        const float inv = s2 > 0.f ? 1.0f / sqrtf(s2) : 1.0f;
-        if (lane < a.hidden) {
-            a.pos[(int64_t)(n0 + v) * a.hidden + lane] = val * inv;
-            if (a.raw) a.raw[(int64_t)(n0 + v) * a.hidden + lane] = val;
+    // two nodes per wave step, one per half-wave (k <= 32 columns), and four steps in flight: the records and gathers of the
+    // later ones are requested before the first is reduced.  half32_tree_sum adds a row's squares by the tree wave_sum used
+    // when the upper half of the wave carried zeros, so the norms keep their bits.
+    {
+        const int hl = lane & 31, hv = lane >> 5;
+        const int src = hl < k ? colsrc[hl] : 0;
+        auto node_value = [&](int v) -> float {
+            if (v >= n || hl >= k) return 0.f;
+            const int rsrc = xrec[4 * v], o = xrec[4 * v + 1], g = xrec[4 * v + 2], cb = xrec[4 * v + 3];
+            return defl_expand(rsrc, o, g, cb, src, XA, P);
+        };
+        auto node_store = [&](int v, float val, float s2) {
+            const float inv = s2 > 0.f ? 1.0f / sqrtf(s2) : 1.0f;
+            if (v < n && hl < a.hidden) {
+                a.pos[(int64_t)(n0 + v) * a.hidden + hl] = val * inv;
+                if (a.raw) a.raw[(int64_t)(n0 + v) * a.hidden + hl] = val;
+            }
+        };
+        constexpr int kFly = 4;                                  // steps of a wave in flight
+        for (int v0 = 2 * wv; v0 < n; v0 += 2 * kFly * kNW) {    // wave-uniform
+            float x[kFly];
+#pragma unroll
+            for (int f = 0; f < kFly; ++f) x[f] = node_value(v0 + hv + 2 * kNW * f);
+#pragma unroll
+            for (int f = 0; f < kFly; ++f) node_store(v0 + hv + 2 * kNW * f, x[f], half32_tree_sum(x[f] * x[f]));
         }
     }
     PHASE_TICK(4);                                               // expansion
