@@ -14,13 +14,14 @@
 //   gw_step_kernel    THE HOT PATH, one launch per order k >= 2: X_k = 2 M X_{k-1} - X_{k-2} written over X_{k-2} (a thread reads only
 //       its own entry of it), the neighbours' rows of X_{k-1} gathered through col_idx, one coalesced read per neighbour and wave;
 //       Ha += c_a[k] X_k, Hb += c_b[k] X_k in the same launch.  A row's sum is ordered by the row alone (the binary counter of
-//       include/gcc_amd.h over segments of 32 neighbours).
+//       include/gcc_amd.h over segments of 32 neighbours: SumCounter of task_common.h).
 //   gw_char_kernel    grid (column tile, block of 128 rows, filter x group of 8 time points): threshold, sincos per time point; a wave sums
 //       32 rows left to right, the four waves are added as (0 + 1) + (2 + 3) -> the block's partial sums in the workspace.
 //   gw_table_kernel   per column and table entry the blocks by the same counter, / n -> chi and, rounded once, chi32.
 //   gw_heat_kernel    the two thresholded panels -> args.heat (the stage tests).
-// No floating-point atomics: every sum has one fixed order, which depends on n_rows and the row alone (never on W or the grid).
-#include "host_common.h"
+// No floating-point atomics: every sum has one fixed order, which depends on n_rows and the row alone (never on W or the grid).  The
+// counter, the CSR guards and the entry points' scaffold are task_common.h's.
+#include "task_common.h"
 
 #include <limits.h>
 #include <math.h>
@@ -63,53 +64,6 @@ struct GwChar {
 
 __device__ __forceinline__ bool fatal(const int32_t *status) { return (load_fresh_i32(status) & GCC_STATUS_GRAPHWAVE_BAD_CSR) != 0; }
 
-// the entries of row i; a row_ptr that does not fit gives an empty row (gw_scale_kernel reports it)
-__device__ __forceinline__ bool row_range(const GwDev &a, int i, int &b, int &e)
-{
-    b = a.rp[i];
-    e = a.rp[i + 1];
-    if (b < 0 || e < b || e > a.nnz) {
-        b = e = 0;
-        return false;
-    }
-    return true;
-}
-
-// sums of 2^l items at level l: push() adds item number t (t items came before), fold() adds what is left from the lowest level up
-template <int L> struct Counter {
-    double v[L];
-    __device__ __forceinline__ Counter()
-    {
-#pragma unroll
-        for (int l = 0; l < L; ++l) v[l] = 0.0;
-    }
-    __device__ __forceinline__ void push(int t, double c)
-    {
-        bool go = true;
-#pragma unroll
-        for (int l = 0; l < L; ++l) {
-            if (!go) continue;
-            if ((t >> l) & 1) c = v[l] + c;
-            else {
-                v[l] = c;
-                go = false;
-            }
-        }
-    }
-    __device__ __forceinline__ double fold(int m) const
-    {
-        double s = 0.0;
-        bool have = false;
-#pragma unroll
-        for (int l = 0; l < L; ++l) {
-            if (!((m >> l) & 1)) continue;
-            s = have ? v[l] + s : v[l];
-            have = true;
-        }
-        return s;
-    }
-};
-
 __global__ __launch_bounds__(kThreads) void gw_scale_kernel(GwDev a)
 {
     const int lane = lane_id(), wv = (int)threadIdx.x >> 6;
@@ -117,15 +71,12 @@ __global__ __launch_bounds__(kThreads) void gw_scale_kernel(GwDev a)
     if (i64 >= a.n_rows) return;                                    // (the whole wave)
     const int i = (int)i64;
     int b, e;
-    bool ok = row_range(a, i, b, e);
-    if (i == 0 && a.rp[0] != 0) ok = false;
-    if (i == a.n_rows - 1 && a.rp[a.n_rows] != a.nnz) ok = false;
+    const bool ok = csr_row_range(a.rp, a.nnz, i, b, e) && csr_ends_ok(a.rp, a.n_rows, a.nnz, i);
     int bits = ok ? 0 : GCC_STATUS_GRAPHWAVE_BAD_CSR;
     for (int e0 = b; e0 < e; e0 += 64) {
         const int q = e0 + lane;
         if (q >= e) continue;
-        const int j = a.ci[q], before = q > b ? a.ci[q - 1] : -1;
-        if ((unsigned)j >= (unsigned)a.n_rows || j == i || before > j) bits |= GCC_STATUS_GRAPHWAVE_BAD_CSR;
+        if (csr_entry_bad(a.ci, b, q, i, a.n_rows)) bits |= GCC_STATUS_GRAPHWAVE_BAD_CSR;
     }
     if (bits) atomicOr(a.status, (int32_t)bits);
     if (lane == 0) {
@@ -162,7 +113,7 @@ __global__ __launch_bounds__(kThreads) void gw_init_kernel(GwDev a, GwInit in)
     if (i64 >= a.n_rows || c >= a.ncols) return;
     const int i = (int)i64, u = a.col0 + c;
     int b, e;
-    row_range(a, i, b, e);
+    csr_row_range(a.rp, a.nnz, i, b, e);
     const double x0 = i == u ? 1.0 : 0.0;
     const int m = multiplicity(a.ci, b, e, u);
     const double x1 = m ? -(a.dinv[i] * ((double)m * a.dinv[u])) : 0.0;
@@ -182,7 +133,7 @@ __global__ __launch_bounds__(kThreads) void gw_step_kernel(GwDev a)
     const int i = wave_uniform((int)i64);                           // (a wave is one row: its entries and scales come by scalar loads)
     if (c >= a.ncols) return;
     int b, e;
-    row_range(a, i, b, e);
+    csr_row_range(a.rp, a.nnz, i, b, e);
     const double *x = a.xb + c;
     auto segment = [&](int f0, int f1) {
         double t = 0.0;
@@ -196,8 +147,8 @@ __global__ __launch_bounds__(kThreads) void gw_step_kernel(GwDev a)
     double s;
     if (nseg <= 1) s = segment(b, e);
     else {
-        Counter<kLvRow> cn;
-        for (int t = 0; t < nseg; ++t) cn.push(t, segment(b + t * kSeg, min(b + (t + 1) * kSeg, e)));
+        SumCounter<kLvRow, 1> cn;
+        for (int t = 0; t < nseg; ++t) cn.push(t, {segment(b + t * kSeg, min(b + (t + 1) * kSeg, e))});
         s = cn.fold(nseg);
     }
     const long long o = (long long)i * a.W + c;
@@ -259,8 +210,8 @@ __global__ __launch_bounds__(kThreads) void gw_table_kernel(GwDev a, const doubl
     if (c >= a.ncols || entry >= d) return;
     const int u = a.col0 + c;
     if (!(a.dinv[u] > 0.0)) return;                                 // (its row keeps the zeros put there first)
-    Counter<kLvBlocks> cn;
-    for (int rb = 0; rb < blocks; ++rb) cn.push(rb, part[((long long)rb * d + entry) * a.W + c]);
+    SumCounter<kLvBlocks, 1> cn;
+    for (int rb = 0; rb < blocks; ++rb) cn.push(rb, {part[((long long)rb * d + entry) * a.W + c]});
     const double v = cn.fold(blocks) / (double)*a.nlive;
     chi[(long long)u * d + entry] = v;
     chi32[(long long)u * d + entry] = (float)v;
@@ -327,46 +278,30 @@ Plan make_plan(int64_t n_rows, int32_t d, int32_t width)
     Plan p;
     p.W = panel_width(n_rows, d, width);
     p.blocks = (int32_t)row_blocks(n_rows);
-    auto al = [](int64_t x) { return (x + 255) & ~(int64_t)255; };
-    int64_t o = 0;
+    Carve cv;
     p.panel = n_rows * p.W * 8;
-    p.off_dinv = o; o = al(o + n_rows * 8);
-    p.off_nlive = o; o = al(o + 8);
-    p.off_x = o; o = al(o + 4 * p.panel);
-    p.off_part = o; o = al(o + (int64_t)p.blocks * d * p.W * 8);
-    p.total = o;
+    p.off_dinv = cv.take(n_rows * 8);
+    p.off_nlive = cv.take(8);
+    p.off_x = cv.take(4 * p.panel);
+    p.off_part = cv.take((int64_t)p.blocks * d * p.W * 8);
+    p.total = cv.total();
     return p;
 }
 
 // the checks both entry points share; fills dv and pl; rc < 0 names the member in g_err
 int prepare(const char *who, const gcc_graphwave_args *h, void *workspace, int64_t workspace_bytes, int32_t *status, GwDev &dv, Plan &pl)
 {
-    if (!h) {
-        snprintf(g_err, kErrLen, "%s: args is NULL", who);
-        return -1;
-    }
-    const int rc = check_sizes(who, h->n_rows, h->nnz, h->d, h->width);
+    int rc = null_member(who, {{h, "args"}});
     if (rc) return rc;
-    if (!status || !h->row_ptr || (!h->col_idx && h->nnz > 0)) {
-        snprintf(g_err, kErrLen, "%s: %s is NULL", who, !status ? "status" : !h->row_ptr ? "row_ptr" : "col_idx");
-        return -1;
-    }
+    if ((rc = check_sizes(who, h->n_rows, h->nnz, h->d, h->width))) return rc;
+    if ((rc = null_member(who, {{status, "status"}, {h->row_ptr, "row_ptr"}, {h->col_idx, "col_idx", h->nnz > 0}}))) return rc;
     pl = make_plan(h->n_rows, h->d, h->width);
-    if (!workspace || workspace_bytes < pl.total) {
-        snprintf(g_err, kErrLen, "%s: workspace_bytes %lld is less than gcc_graphwave_workspace_bytes (%lld)", who,
-                 (long long)(workspace ? workspace_bytes : 0), (long long)pl.total);
-        return -8;
-    }
-    if (((uintptr_t)workspace & 15) != 0) {
-        snprintf(g_err, kErrLen, "%s: workspace must be aligned to 16 bytes", who);
-        return -9;
-    }
-    unsigned char *base = static_cast<unsigned char *>(workspace);
+    if ((rc = check_workspace(who, "gcc_graphwave_workspace_bytes", workspace, workspace_bytes, pl.total))) return rc;
     dv = GwDev();
     dv.rp = h->row_ptr; dv.ci = h->col_idx; dv.n_rows = (int32_t)h->n_rows; dv.nnz = (int32_t)h->nnz; dv.W = pl.W;
-    dv.dinv = reinterpret_cast<double *>(base + pl.off_dinv);
-    dv.nlive = reinterpret_cast<int32_t *>(base + pl.off_nlive);
-    double *x = reinterpret_cast<double *>(base + pl.off_x);
+    dv.dinv = ws_at<double>(workspace, pl.off_dinv);
+    dv.nlive = ws_at<int32_t>(workspace, pl.off_nlive);
+    double *x = ws_at<double>(workspace, pl.off_x);
     const int64_t pe = pl.panel / 8;
     dv.xa = x; dv.xb = x + pe; dv.ha = x + 2 * pe; dv.hb = x + 3 * pe;
     dv.status = status;
@@ -421,12 +356,9 @@ int32_t gcc_graphwave_heat(const gcc_graphwave_args *h, void *workspace, int64_t
     const char *who = "gcc_graphwave_heat";
     GwDev d;
     Plan pl;
-    const int rc = prepare(who, h, workspace, workspace_bytes, status, d, pl);
+    int rc = prepare(who, h, workspace, workspace_bytes, status, d, pl);
     if (rc) return rc;
-    if (!h->heat) {
-        snprintf(g_err, kErrLen, "%s: heat is NULL", who);
-        return -1;
-    }
+    if ((rc = null_member(who, {{h->heat, "heat"}}))) return rc;
     if (h->heat_chunk < 0 || (int64_t)h->heat_chunk * pl.W >= h->n_rows) {
         snprintf(g_err, kErrLen, "%s: heat_chunk %d outside the %lld panels of %d columns", who, h->heat_chunk,
                  (long long)((h->n_rows + pl.W - 1) / pl.W), pl.W);
@@ -439,7 +371,7 @@ int32_t gcc_graphwave_heat(const gcc_graphwave_args *h, void *workspace, int64_t
     d.col0 = h->heat_chunk * pl.W;
     d.ncols = d.n_rows - d.col0 < d.W ? d.n_rows - d.col0 : d.W;
     hipLaunchKernelGGL(gw_heat_kernel, dim3(d.W / 64, (d.n_rows + kWaves - 1) / kWaves), dim3(kThreads), 0, s, d, h->threshold, h->heat);
-    return hipGetLastError() == hipSuccess ? 0 : -10;
+    return launched();
 }
 
 int32_t gcc_graphwave_embed(const gcc_graphwave_args *h, void *workspace, int64_t workspace_bytes, int32_t *status, void *stream)
@@ -447,12 +379,9 @@ int32_t gcc_graphwave_embed(const gcc_graphwave_args *h, void *workspace, int64_
     const char *who = "gcc_graphwave_embed";
     GwDev d;
     Plan pl;
-    const int rc = prepare(who, h, workspace, workspace_bytes, status, d, pl);
+    int rc = prepare(who, h, workspace, workspace_bytes, status, d, pl);
     if (rc) return rc;
-    if (!h->chi || !h->chi32) {
-        snprintf(g_err, kErrLen, "%s: %s is NULL", who, !h->chi ? "chi" : "chi32");
-        return -1;
-    }
+    if ((rc = null_member(who, {{h->chi, "chi"}, {h->chi32, "chi32"}}))) return rc;
     hipStream_t s = (hipStream_t)stream;
     const int64_t nd = h->n_rows * h->d;
     (void)hipMemsetAsync(h->chi, 0, (size_t)nd * 8, s);
@@ -464,7 +393,7 @@ int32_t gcc_graphwave_embed(const gcc_graphwave_args *h, void *workspace, int64_
     ch.groups = (ch.T + kTg - 1) / kTg;
     ch.threshold = h->threshold;
     for (int j = 0; j < kMaxT; ++j) ch.t[j] = j < ch.T ? h->time_points[j] : 0.0;
-    ch.part = reinterpret_cast<double *>(static_cast<unsigned char *>(workspace) + pl.off_part);
+    ch.part = ws_at<double>(workspace, pl.off_part);
     for (int col0 = 0; col0 < d.n_rows; col0 += pl.W) {
         launch_panel(d, h, col0, s);
         d.col0 = col0;
@@ -475,7 +404,7 @@ int32_t gcc_graphwave_embed(const gcc_graphwave_args *h, void *workspace, int64_
         hipLaunchKernelGGL(gw_table_kernel, dim3(tiles, (h->d + kWaves - 1) / kWaves), dim3(kThreads), 0, s, d, (const double *)ch.part, (int)h->d,
                            (int)pl.blocks, h->chi, h->chi32);
     }
-    return hipGetLastError() == hipSuccess ? 0 : -10;
+    return launched();
 }
 
 }  // extern "C"

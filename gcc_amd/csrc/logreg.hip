@@ -25,8 +25,9 @@
 //       1e-4), then w -= s d, Z -= s Zd.
 //   lr_predict_kernel    one workgroup per corpus row: decision values of the row's own fold from the final w (float64, lanes
 //       strided), top-k under (decision descending, class ascending), tp / fp / fn per fold with integer atomics.
-// No floating-point atomics: every sum has one fixed order, which depends on the sizes alone.
-#include "host_common.h"
+// No floating-point atomics: every sum has one fixed order, which depends on the sizes alone.  The workgroup sum, the Gram tile and
+// the entry points' scaffold are task_common.h's.
+#include "task_common.h"
 
 #include <float.h>
 #include <math.h>
@@ -37,6 +38,7 @@ constexpr int kThreads = 256, kWaves = 4;
 constexpr int kLdsDim = 128;                  // Cholesky in LDS up to this D ((D + 1)^2 float64 = 130 KiB), in the workspace above
 constexpr double kArmijo = 1e-4, kMinStep = 1.0 / 1099511627776.0;        // 2^-40
 constexpr double kRoundSlack = 64.0 * DBL_EPSILON;                        // of |f|: what the line search allows for rounding
+static_assert(kWaves == kGramWaves, "lr_hess_kernel");
 enum { kRunning = 0, kConverged = 1, kCapped = 2, kAllZero = 3, kAllOne = 4, kBadPivot = 5, kNoDecrease = 6, kNotRun = 7 };
 
 struct LrDev {
@@ -68,18 +70,6 @@ __device__ __forceinline__ double sigmoid(double z)
 }
 // log(1 + exp(z)) without overflow
 __device__ __forceinline__ double log1pexp(double z) { return (z > 0.0 ? z : 0.0) + log1p(exp(-fabs(z))); }
-
-// sum over the workgroup in one fixed order: wave sums, then the waves in wave order (every thread gets the result)
-__device__ __forceinline__ double block_sum(double v, double *red)
-{
-    v = wave_sum(v);
-    if (lane_id() == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    double r = red[0];
-    for (int w = 1; w < kWaves; ++w) r += red[w];
-    __syncthreads();
-    return r;
-}
 
 __global__ __launch_bounds__(kThreads) void lr_finite_kernel(LrDev a)
 {
@@ -164,7 +154,7 @@ __global__ __launch_bounds__(kThreads) void lr_grad_kernel(LrDev a)
         }
         __syncthreads();
     }
-    const double qtot = block_sum(qsum, red);
+    const double qtot = block_sum<kWaves>(qsum, red);
     part_s[tid] = acc;
     __syncthreads();
     double *out = a.gpart + ((long long)p * a.gsplits + split) * a.Dpad;
@@ -205,42 +195,26 @@ __global__ __launch_bounds__(64) void lr_test_kernel(LrDev a)
     }
 }
 
-// tile t of the upper triangle, rows first: (0,0), (0,1), ..., (0,T-1), (1,1), ...
-__device__ __forceinline__ void tile_of(int t, int T, int &ti, int &tj)
-{
-    ti = 0;
-    for (int width = T; t >= width; --width) { t -= width; ++ti; }
-    tj = ti + t;
-}
-__host__ __device__ inline int tile_index(int ti, int tj, int T) { return ti * T - ti * (ti - 1) / 2 + (tj - ti); }
-
 __global__ __launch_bounds__(kThreads) void lr_hess_kernel(LrDev a)
 {
     __shared__ double red[kWaves][256];
-    const int tile = (int)blockIdx.x, split = (int)blockIdx.y, p = (int)blockIdx.z;
+    const int tile = (int)blockIdx.x, split = (int)blockIdx.y, p = (int)blockIdx.z, jl = lane_id() & 15;
     if (a.pstate[p] != kRunning) return;
-    const int tid = (int)threadIdx.x, lane = lane_id(), wv = tid >> 6, jl = lane & 15, q = lane >> 4;
     int ti, tj;
-    tile_of(tile, a.T, ti, tj);
+    tri_tile_of(tile, a.T, ti, tj);
     const int ca = 16 * ti + jl, cb = 16 * tj + jl;
     const int r0 = split * a.rps, r1 = min(a.N, r0 + a.rps);
     const double *S = a.S + (long long)p * a.N;
-    const f64x4 z4 = {0.0, 0.0, 0.0, 0.0};
-    f64x4 acc0 = z4, acc1 = z4;
-    // a wave's row groups: 4 rows each, groups wv, wv + 4, ...; lane (jl, q) passes A[jl][q] = s x~[row q][ca], B[q][jl] = x~[row q][cb]
-    for (int rb = r0 + 4 * wv; rb < r1; rb += 8 * kWaves) {
-        const int ra = rb + q, rc = rb + 4 * kWaves + q;
-        const bool ina = ra < r1, inc = rc < r1;
-        const int rac = ina ? ra : r1 - 1, rcc = inc ? rc : r1 - 1;  // (rows past the end read the last row, weight 0)
-        const double sa = ina ? S[rac] : 0.0, sc = inc ? S[rcc] : 0.0;
-        const double xa0 = aug(a, rac, ca), xb0 = aug(a, rac, cb), xa1 = aug(a, rcc, ca), xb1 = aug(a, rcc, cb);
-        acc0 = mfma_16x16x4_f64(sa != 0.0 ? sa * xa0 : 0.0, xb0, acc0);
-        acc1 = mfma_16x16x4_f64(sc != 0.0 ? sc * xa1 : 0.0, xb1, acc1);
-    }
-#pragma unroll
-    for (int r = 0; r < 4; ++r) red[wv][(q + 4 * r) * 16 + jl] = acc0[r] + acc1[r];     // c/d[r] = C[q + 4 r][jl]
-    __syncthreads();
-    a.Hpart[(((long long)p * a.splits + split) * a.tiles + tile) * 256 + tid] = ((red[0][tid] + red[1][tid]) + red[2][tid]) + red[3][tid];
+    // A[jl][q] = s x~[row q][ca], B[q][jl] = x~[row q][cb]; rows past the end read the last row, weight 0
+    const double h = gram_tile_f64(
+        r0, r1,
+        [&](int r, bool in) {
+            const int rc = in ? r : r1 - 1;
+            const double s = in ? S[rc] : 0.0, x = aug(a, rc, ca);
+            return s != 0.0 ? s * x : 0.0;
+        },
+        [&](int r, bool in) { return aug(a, in ? r : r1 - 1, cb); }, red);
+    a.Hpart[(((long long)p * a.splits + split) * a.tiles + tile) * 256 + threadIdx.x] = h;
 }
 
 __global__ __launch_bounds__(kThreads) void lr_newton_kernel(LrDev a)
@@ -258,7 +232,7 @@ __global__ __launch_bounds__(kThreads) void lr_newton_kernel(LrDev a)
     for (int e = tid; e < n * n; e += kThreads) {
         const int i = e / n, j = e % n;
         if (i > j) continue;
-        const long long at = (long long)tile_index(i >> 4, j >> 4, a.T) * 256 + (i & 15) * 16 + (j & 15);
+        const long long at = (long long)tri_tile_index(i >> 4, j >> 4, a.T) * 256 + (i & 15) * 16 + (j & 15);
         double s = 0.0;
         for (int k = 0; k < a.splits; ++k) s += a.Hpart[((long long)p * a.splits + k) * a.tiles * 256 + at];
         const double h = a.C * s + (i == j ? (i < a.D ? 1.0 : a.rho) : 0.0);
@@ -308,7 +282,7 @@ __global__ __launch_bounds__(kThreads) void lr_newton_kernel(LrDev a)
         a.d[base + j] = v_s[j];
         part += a.g[base + j] * v_s[j];
     }
-    const double dec = block_sum(part, red);
+    const double dec = block_sum<kWaves>(part, red);
     if (tid == 0) a.dec[p] = dec;
 }
 
@@ -359,7 +333,7 @@ __global__ __launch_bounds__(kThreads) void lr_search_kernel(LrDev a)
             const double z = a.Z[pN + r] - s * a.Zd[pN + r];
             loss += log1pexp(z) - (a.y[(long long)r * a.classes + c] != 0 ? z : 0.0);
         }
-        return block_sum(part + a.C * loss, red);
+        return block_sum<kWaves>(part + a.C * loss, red);
     };
     // Armijo, with the rounding of the two sums allowed for: near the minimiser the decrease of a full Newton step (~ dec / 2) is
     // below the rounding of f itself, and a test on the bare values would halve good steps at random there
@@ -471,23 +445,22 @@ Plan make_plan(int32_t N, int32_t D, int32_t classes, int32_t folds)
     p.splits = (N + p.rps - 1) / p.rps;
     p.grps = (((N + 63) / 64) + 255) & ~255;                      // the gradient's own row splits: at most 64, whole chunks of 256 rows
     p.gsplits = (N + p.grps - 1) / p.grps;
-    auto al = [](int64_t x) { return (x + 255) & ~(int64_t)255; };
-    int64_t o = 0;
+    Carve cv;
     const int64_t PN = (int64_t)p.P * N * 8, vec = (int64_t)p.P * p.Dpad * 8;
-    p.off_Z = o; o = al(o + PN);
-    p.off_Zd = o; o = al(o + PN);
-    p.off_S = o; o = al(o + PN);
-    p.off_Hpart = o; o = al(o + (int64_t)p.P * p.splits * p.tiles * 256 * 8);
-    p.off_Hfull = o; o = al(o + (D > kLdsDim ? (int64_t)p.P * p.Dp * p.Dp * 8 : 0));
-    p.off_gpart = o; o = al(o + vec * p.gsplits);
-    p.off_w = o; o = al(o + vec);
-    p.off_g = o; o = al(o + vec);
-    p.off_d = o; o = al(o + vec);
-    p.off_gmax = o; o = al(o + (int64_t)p.P * 8);
-    p.off_dec = o; o = al(o + (int64_t)p.P * 8);
-    p.off_state = o; o = al(o + (int64_t)p.P * 4);
-    p.off_iter = o; o = al(o + (int64_t)p.P * 4);
-    p.total = o;
+    p.off_Z = cv.take(PN);
+    p.off_Zd = cv.take(PN);
+    p.off_S = cv.take(PN);
+    p.off_Hpart = cv.take((int64_t)p.P * p.splits * p.tiles * 256 * 8);
+    p.off_Hfull = cv.take((D > kLdsDim ? (int64_t)p.P * p.Dp * p.Dp * 8 : 0));
+    p.off_gpart = cv.take(vec * p.gsplits);
+    p.off_w = cv.take(vec);
+    p.off_g = cv.take(vec);
+    p.off_d = cv.take(vec);
+    p.off_gmax = cv.take((int64_t)p.P * 8);
+    p.off_dec = cv.take((int64_t)p.P * 8);
+    p.off_state = cv.take((int64_t)p.P * 4);
+    p.off_iter = cv.take((int64_t)p.P * 4);
+    p.total = cv.total();
     return p;
 }
 
@@ -515,16 +488,10 @@ int check_sizes(const char *who, int32_t N, int32_t D, int32_t classes, int32_t 
 // the checks every entry point shares; fills d and pl; rc < 0 names the member in g_err
 int prepare(const char *who, const gcc_logreg_args *h, void *workspace, int64_t workspace_bytes, int32_t *status, LrDev &d, Plan &pl)
 {
-    if (!h) {
-        snprintf(g_err, kErrLen, "%s: args is NULL", who);
-        return -1;
-    }
-    const int rc = check_sizes(who, h->N, h->D, h->classes, h->folds);
+    int rc = null_member(who, {{h, "args"}});
     if (rc) return rc;
-    if (!status || !h->emb || !h->y || !h->fold_of_row) {
-        snprintf(g_err, kErrLen, "%s: %s is NULL", who, !status ? "status" : !h->emb ? "emb" : !h->y ? "y" : "fold_of_row");
-        return -1;
-    }
+    if ((rc = check_sizes(who, h->N, h->D, h->classes, h->folds))) return rc;
+    if ((rc = null_member(who, {{status, "status"}, {h->emb, "emb"}, {h->y, "y"}, {h->fold_of_row, "fold_of_row"}}))) return rc;
     if (h->ld < h->D) {
         snprintf(g_err, kErrLen, "%s: ld %lld must be at least D (%d)", who, (long long)h->ld, h->D);
         return -7;
@@ -535,17 +502,8 @@ int prepare(const char *who, const gcc_logreg_args *h, void *workspace, int64_t 
         return -7;
     }
     pl = make_plan(h->N, h->D, h->classes, h->folds);
-    if (!workspace || workspace_bytes < pl.total) {
-        snprintf(g_err, kErrLen, "%s: workspace_bytes %lld is less than gcc_logreg_workspace_bytes (%lld)", who,
-                 (long long)(workspace ? workspace_bytes : 0), (long long)pl.total);
-        return -8;
-    }
-    if (((uintptr_t)workspace & 15) != 0) {
-        snprintf(g_err, kErrLen, "%s: workspace must be aligned to 16 bytes", who);
-        return -9;
-    }
-    unsigned char *ws = static_cast<unsigned char *>(workspace);
-    auto f64 = [&](int64_t off) { return reinterpret_cast<double *>(ws + off); };
+    if ((rc = check_workspace(who, "gcc_logreg_workspace_bytes", workspace, workspace_bytes, pl.total))) return rc;
+    auto f64 = [&](int64_t off) { return ws_at<double>(workspace, off); };
     d = LrDev();
     d.emb = h->emb; d.ld = h->ld; d.y = h->y; d.fold = h->fold_of_row;
     d.N = h->N; d.D = h->D; d.classes = h->classes; d.folds = h->folds;
@@ -555,7 +513,7 @@ int prepare(const char *who, const gcc_logreg_args *h, void *workspace, int64_t 
     d.Z = f64(pl.off_Z); d.Zd = f64(pl.off_Zd); d.S = f64(pl.off_S); d.Hpart = f64(pl.off_Hpart); d.Hfull = f64(pl.off_Hfull);
     d.gpart = f64(pl.off_gpart); d.w = f64(pl.off_w); d.g = f64(pl.off_g); d.d = f64(pl.off_d);
     d.gmax = f64(pl.off_gmax); d.dec = f64(pl.off_dec);
-    d.pstate = reinterpret_cast<int32_t *>(ws + pl.off_state); d.piter = reinterpret_cast<int32_t *>(ws + pl.off_iter);
+    d.pstate = ws_at<int32_t>(workspace, pl.off_state); d.piter = ws_at<int32_t>(workspace, pl.off_iter);
     d.pred = h->pred; d.decision = h->decision; d.counts = h->counts; d.coef = h->coef; d.intercept = h->intercept;
     d.grad_out = h->grad; d.iters_out = h->iters; d.state_out = h->state; d.unfinished = h->unfinished;
     d.status = status;
@@ -597,7 +555,7 @@ int32_t gcc_logreg_setup(const gcc_logreg_args *h, void *workspace, int64_t work
     hipLaunchKernelGGL(lr_finite_kernel, dim3((h->N + 63) / 64), dim3(kThreads), 0, s, d);
     hipLaunchKernelGGL(lr_setup_kernel, dim3(pl.P), dim3(64), 0, s, d);
     launch_grad_test(d, false, s);
-    return hipGetLastError() == hipSuccess ? 0 : -10;
+    return launched();
 }
 
 int32_t gcc_logreg_step(const gcc_logreg_args *h, void *workspace, int64_t workspace_bytes, int32_t *status, void *stream)
@@ -605,12 +563,9 @@ int32_t gcc_logreg_step(const gcc_logreg_args *h, void *workspace, int64_t works
     const char *who = "gcc_logreg_step";
     LrDev d;
     Plan pl;
-    const int rc = prepare(who, h, workspace, workspace_bytes, status, d, pl);
+    int rc = prepare(who, h, workspace, workspace_bytes, status, d, pl);
     if (rc) return rc;
-    if (!h->unfinished) {
-        snprintf(g_err, kErrLen, "%s: unfinished is NULL", who);
-        return -1;
-    }
+    if ((rc = null_member(who, {{h->unfinished, "unfinished"}}))) return rc;
     hipStream_t s = (hipStream_t)stream;
     const size_t lds = newton_lds_bytes(d);
 #ifndef GCC_AMD_HIPEMU
@@ -624,7 +579,7 @@ int32_t gcc_logreg_step(const gcc_logreg_args *h, void *workspace, int64_t works
         hipLaunchKernelGGL(lr_search_kernel, dim3(pl.P), dim3(kThreads), 0, s, d);
         launch_grad_test(d, it == h->iters_per_sync - 1, s);
     }
-    return hipGetLastError() == hipSuccess ? 0 : -10;
+    return launched();
 }
 
 int32_t gcc_logreg_predict(const gcc_logreg_args *h, void *workspace, int64_t workspace_bytes, int32_t *status, void *stream)
@@ -632,17 +587,14 @@ int32_t gcc_logreg_predict(const gcc_logreg_args *h, void *workspace, int64_t wo
     const char *who = "gcc_logreg_predict";
     LrDev d;
     Plan pl;
-    const int rc = prepare(who, h, workspace, workspace_bytes, status, d, pl);
+    int rc = prepare(who, h, workspace, workspace_bytes, status, d, pl);
     if (rc) return rc;
-    if (!h->pred) {
-        snprintf(g_err, kErrLen, "%s: pred is NULL", who);
-        return -1;
-    }
+    if ((rc = null_member(who, {{h->pred, "pred"}}))) return rc;
     hipStream_t s = (hipStream_t)stream;
     if (h->counts) (void)hipMemsetAsync(h->counts, 0, (size_t)h->folds * 3 * sizeof(int32_t), s);
     hipLaunchKernelGGL(lr_finish_kernel, dim3(pl.P), dim3(64), 0, s, d);
     hipLaunchKernelGGL(lr_predict_kernel, dim3(h->N), dim3(kThreads), 0, s, d);
-    return hipGetLastError() == hipSuccess ? 0 : -10;
+    return launched();
 }
 
 }  // extern "C"

@@ -14,7 +14,7 @@
 //   pr_norm_kernel       one workgroup: sum s^0.75, threads strided, then the workgroup's sum.     pr_c_kernel: c.
 //   pr_spmm_kernel       THE HOT PATH, y = op x with the tail fused: a group of G = 16 / 32 / 64 lanes per row, lane = column (and
 //       column + 64 for k > 64), the neighbours' rows of x gathered through col_idx.  A row's sum is ordered by the row alone (the
-//       binary counter of include/gcc_amd.h over segments of 32 neighbours).
+//       binary counter of include/gcc_amd.h over segments of 32 neighbours: SumCounter of task_common.h).
 //   pr_spmm_long_kernel  one group per part of a row longer than a chunk -> the workspace.
 //   pr_spmm_comb_kernel  one group per such row: its parts by the same counter, then the same tail.
 //   pr_gram_kernel       grid (upper-triangle 16 x 16 tile, row split): x^T x on v_mfma_f64_16x16x4_f64, four rows per instruction;
@@ -26,8 +26,9 @@
 //       LDS), eigenvalues descending, the top d.
 //   pr_sign_kernel       the column signs from the workgroups' entries in order, sqrt(sigma) scaling, the singular-value check.
 //   pr_finish_kernel     scaled rows, L2-normalised (a zero row stays zero) -> float64 and float32.
-// No floating-point atomics: every sum has one fixed order, which depends on the sizes alone (and not on the chunk).
-#include "host_common.h"
+// No floating-point atomics: every sum has one fixed order, which depends on the sizes alone (and not on the chunk).  The counter, the
+// CSR guards, the Gram tile and the entry points' scaffold are task_common.h's.
+#include "task_common.h"
 
 #include <float.h>
 #include <limits.h>
@@ -47,6 +48,7 @@ constexpr int kMaxSweeps = 40;
 constexpr int kFatal = GCC_STATUS_PRONE_BAD_CSR | GCC_STATUS_PRONE_SPLIT_FULL | GCC_STATUS_PRONE_RANK | GCC_STATUS_PRONE_SINGULAR;
 static_assert((kSeg << (kLv - 1)) == GCC_PRONE_MAX_CHUNK, "the counter holds one part");
 static_assert(kMaxK <= kPartStride && kMaxK <= 128, "two columns per lane");
+static_assert(kWaves == kGramWaves, "pr_gram_kernel");
 
 struct PrDev {
     const int32_t *rp, *ci;
@@ -63,57 +65,8 @@ struct PrDev {
 
 __device__ __forceinline__ bool fatal(const int32_t *status) { return (load_fresh_i32(status) & kFatal) != 0; }
 
-// the entries of row i; a row_ptr that does not fit gives an empty row (pr_rows_kernel reports it)
-__device__ __forceinline__ bool row_range(const PrDev &a, int i, int &b, int &e)
-{
-    b = a.rp[i];
-    e = a.rp[i + 1];
-    if (b < 0 || e < b || e > a.nnz) {
-        b = e = 0;
-        return false;
-    }
-    return true;
-}
-
-// sums of 2^l items at level l, for two columns: push() adds item number t (t items came before), fold() adds what is left
-// from the lowest level up, onto (s0, s1) when `have`
-template <int L> struct Counter {
-    double v0[L], v1[L];
-    __device__ __forceinline__ Counter()
-    {
-#pragma unroll
-        for (int l = 0; l < L; ++l) v0[l] = v1[l] = 0.0;
-    }
-    __device__ __forceinline__ void push(int t, double c0, double c1)
-    {
-        bool go = true;
-#pragma unroll
-        for (int l = 0; l < L; ++l) {
-            if (!go) continue;
-            if ((t >> l) & 1) {
-                c0 = v0[l] + c0;
-                c1 = v1[l] + c1;
-            } else {
-                v0[l] = c0;
-                v1[l] = c1;
-                go = false;
-            }
-        }
-    }
-    __device__ __forceinline__ void fold(int m, bool have, double &s0, double &s1) const
-    {
-#pragma unroll
-        for (int l = 0; l < L; ++l) {
-            if (!((m >> l) & 1)) continue;
-            s0 = have ? v0[l] + s0 : v0[l];
-            s1 = have ? v1[l] + s1 : v1[l];
-            have = true;
-        }
-    }
-};
-
 // entries [e0, e1) of row i (e0 on a segment boundary of the row) for the columns c0 and, if on1, c0 + 64
-__device__ __forceinline__ void range_sum(const PrDev &a, int i, int e0, int e1, int c0, bool on1, double &s0, double &s1)
+__device__ __forceinline__ void range_sum(const PrDev &a, int i, int e0, int e1, int c0, bool on1, double (&s)[2])
 {
     const double ri = a.mode == GCC_PRONE_MODE_F ? a.r[i] : 0.0, ci = a.mode == GCC_PRONE_MODE_FT ? a.c[i] : 0.0;
     auto segment = [&](int f0, int f1, double &t0, double &t1) {
@@ -142,17 +95,17 @@ __device__ __forceinline__ void range_sum(const PrDev &a, int i, int e0, int e1,
     };
     const int nseg = (e1 - e0 + kSeg - 1) / kSeg;
     if (nseg <= 1) {
-        segment(e0, e1, s0, s1);
+        segment(e0, e1, s[0], s[1]);
         return;
     }
-    Counter<kLv> cn;
+    SumCounter<kLv, 2> cn;
     for (int t = 0; t < nseg; ++t) {
         double t0, t1;
         segment(e0 + t * kSeg, min(e0 + (t + 1) * kSeg, e1), t0, t1);
-        cn.push(t, t0, t1);
+        cn.push(t, {t0, t1});
     }
-    s0 = s1 = 0.0;
-    cn.fold(nseg, false, s0, s1);
+    s[0] = s[1] = 0.0;
+    cn.fold(nseg, false, s);
 }
 
 // entry (i, c) of y from the row's sum t: the row's own term and the tail
@@ -184,10 +137,7 @@ __global__ __launch_bounds__(kThreads) void pr_rows_kernel(PrDev a)
     if (i64 >= a.n) return;
     const int i = (int)i64;
     int b, e;
-    bool ok = row_range(a, i, b, e);
-    if (i == 0 && a.rp[0] != 0) ok = false;
-    if (i == a.n - 1 && a.rp[a.n] != a.nnz) ok = false;
-    if (!ok) {
+    if (!csr_row_range(a.rp, a.nnz, i, b, e) || !csr_ends_ok(a.rp, a.n, a.nnz, i)) {
         atomicOr(a.status, (int32_t)GCC_STATUS_PRONE_BAD_CSR);
         return;
     }
@@ -214,20 +164,20 @@ __global__ __launch_bounds__(kThreads) void pr_terms_kernel(PrDev a)
     if (i64 >= a.n) return;                                         // (the whole wave)
     const int i = (int)i64;
     int b, e;
-    row_range(a, i, b, e);
+    csr_row_range(a.rp, a.nnz, i, b, e);
     double s = 0.0;
     int bits = 0;
     for (int e0 = b; e0 < e; e0 += 64) {
         const int q = e0 + lane;
         if (q >= e) continue;
-        const int j = a.ci[q], before = q > b ? a.ci[q - 1] : -1;
-        if ((unsigned)j >= (unsigned)a.n || j == i || before > j) {
+        if (csr_entry_bad(a.ci, b, q, i, a.n)) {
             bits |= GCC_STATUS_PRONE_BAD_CSR;
             continue;
         }
-        if (before == j) bits |= GCC_STATUS_PRONE_DUPLICATE;
+        const int j = a.ci[q];
+        if (q > b && a.ci[q - 1] == j) bits |= GCC_STATUS_PRONE_DUPLICATE;
         int jb, je;
-        if (row_range(a, j, jb, je) && je > jb) s += 1.0 / (double)(je - jb);
+        if (csr_row_range(a.rp, a.nnz, j, jb, je) && je > jb) s += 1.0 / (double)(je - jb);
     }
     if (bits) atomicOr(a.status, (int32_t)bits);
     s = wave_sum(s);
@@ -237,24 +187,12 @@ __global__ __launch_bounds__(kThreads) void pr_terms_kernel(PrDev a)
     }
 }
 
-// sum over the workgroup in one fixed order: wave sums, then the waves in wave order (every thread gets the result)
-__device__ __forceinline__ double block_sum(double v, double *red)
-{
-    v = wave_sum(v);
-    if (lane_id() == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    double r = red[0];
-    for (int w = 1; w < kWaves; ++w) r += red[w];
-    __syncthreads();
-    return r;
-}
-
 __global__ __launch_bounds__(kThreads) void pr_norm_kernel(PrDev a)
 {
     __shared__ double red[kWaves];
     double acc = 0.0;
     for (int i = (int)threadIdx.x; i < a.n; i += kThreads) acc += a.cw[i];
-    const double tot = block_sum(acc, red);
+    const double tot = block_sum<kWaves>(acc, red);
     if (threadIdx.x == 0) a.tot[0] = tot;
 }
 
@@ -272,13 +210,13 @@ __global__ __launch_bounds__(kThreads) void pr_spmm_kernel(PrDev a)
     if (i64 >= a.n || c0 >= a.k) return;
     const int i = (int)i64;
     int b, e;
-    row_range(a, i, b, e);
+    csr_row_range(a.rp, a.nnz, i, b, e);
     if (e - b > a.chunk) return;                                    // (pr_spmm_long_kernel / pr_spmm_comb_kernel)
     const bool on1 = c0 + 64 < a.k;
-    double s0, s1;
-    range_sum(a, i, b, e, c0, on1, s0, s1);
-    finish_entry(a, i, e - b, c0, s0);
-    if (on1) finish_entry(a, i, e - b, c0 + 64, s1);
+    double s[2];
+    range_sum(a, i, b, e, c0, on1, s);
+    finish_entry(a, i, e - b, c0, s[0]);
+    if (on1) finish_entry(a, i, e - b, c0 + 64, s[1]);
 }
 
 __global__ __launch_bounds__(kThreads) void pr_spmm_long_kernel(PrDev a)
@@ -290,13 +228,13 @@ __global__ __launch_bounds__(kThreads) void pr_spmm_long_kernel(PrDev a)
     const int i = a.slot_row[slot];
     if (i < 0) return;
     int b, e;
-    row_range(a, i, b, e);
+    csr_row_range(a.rp, a.nnz, i, b, e);
     const int e0 = b + a.slot_part[slot] * a.chunk, e1 = min(e0 + a.chunk, e);
     const bool on1 = c0 + 64 < a.k;
-    double s0, s1;
-    range_sum(a, i, e0, e1, c0, on1, s0, s1);
-    a.part[slot * kPartStride + c0] = s0;
-    if (on1) a.part[slot * kPartStride + c0 + 64] = s1;
+    double s[2];
+    range_sum(a, i, e0, e1, c0, on1, s);
+    a.part[slot * kPartStride + c0] = s[0];
+    if (on1) a.part[slot * kPartStride + c0 + 64] = s[1];
 }
 
 __global__ __launch_bounds__(kThreads) void pr_spmm_comb_kernel(PrDev a)
@@ -308,64 +246,44 @@ __global__ __launch_bounds__(kThreads) void pr_spmm_comb_kernel(PrDev a)
     const int i = a.long_row[l];
     if (i < 0) return;
     int b, e;
-    row_range(a, i, b, e);
+    csr_row_range(a.rp, a.nnz, i, b, e);
     const int deg = e - b, full = deg / a.chunk;
     const bool ragged = deg % a.chunk != 0, on1 = c0 + 64 < a.k;
     const double *part = a.part + (long long)a.long_first[l] * kPartStride + c0;
-    Counter<kLvParts> cn;
-    for (int p = 0; p < full; ++p) cn.push(p, part[(long long)p * kPartStride], on1 ? part[(long long)p * kPartStride + 64] : 0.0);
-    double s0 = 0.0, s1 = 0.0;
+    SumCounter<kLvParts, 2> cn;
+    for (int p = 0; p < full; ++p) cn.push(p, {part[(long long)p * kPartStride], on1 ? part[(long long)p * kPartStride + 64] : 0.0});
+    double s[2] = {0.0, 0.0};
     if (ragged) {
-        s0 = part[(long long)full * kPartStride];
-        s1 = on1 ? part[(long long)full * kPartStride + 64] : 0.0;
+        s[0] = part[(long long)full * kPartStride];
+        s[1] = on1 ? part[(long long)full * kPartStride + 64] : 0.0;
     }
-    cn.fold(full, ragged, s0, s1);
-    finish_entry(a, i, deg, c0, s0);
-    if (on1) finish_entry(a, i, deg, c0 + 64, s1);
+    cn.fold(full, ragged, s);
+    finish_entry(a, i, deg, c0, s[0]);
+    if (on1) finish_entry(a, i, deg, c0 + 64, s[1]);
 }
-
-// tile t of the upper triangle, rows first: (0,0), (0,1), ..., (0,T-1), (1,1), ...
-__device__ __forceinline__ void tile_of(int t, int T, int &ti, int &tj)
-{
-    ti = 0;
-    for (int width = T; t >= width; --width) { t -= width; ++ti; }
-    tj = ti + t;
-}
-__host__ __device__ inline int tile_index(int ti, int tj, int T) { return ti * T - ti * (ti - 1) / 2 + (tj - ti); }
 
 // part[split][tile][256] = the split's rows of x^T x, a tile in row-major order
 __global__ __launch_bounds__(kThreads) void pr_gram_kernel(const double *X, int n, int k, int T, int rps, double *part, const int32_t *status)
 {
     __shared__ double red[kWaves][256];
     if (fatal(status)) return;
-    const int tile = (int)blockIdx.x, split = (int)blockIdx.y;
-    const int tid = (int)threadIdx.x, lane = lane_id(), wv = tid >> 6, jl = lane & 15, q = lane >> 4;
+    const int tile = (int)blockIdx.x, split = (int)blockIdx.y, jl = lane_id() & 15;
     int ti, tj;
-    tile_of(tile, T, ti, tj);
+    tri_tile_of(tile, T, ti, tj);
     const int ca = 16 * ti + jl, cb = 16 * tj + jl;
     const int r0 = split * rps, r1 = min(n, r0 + rps);
-    const f64x4 z4 = {0.0, 0.0, 0.0, 0.0};
-    f64x4 acc0 = z4, acc1 = z4;
-    // a wave's row groups: 4 rows each, groups wv, wv + 4, ...; lane (jl, q) passes A[jl][q] = x[row q][ca], B[q][jl] = x[row q][cb]
-    for (int rb = r0 + 4 * wv; rb < r1; rb += 8 * kWaves) {
-        const int ra = rb + q, rc = rb + 4 * kWaves + q;
-        const bool ina = ra < r1, inc = rc < r1;
-        const double xa0 = ina && ca < k ? X[(long long)ra * k + ca] : 0.0, xb0 = ina && cb < k ? X[(long long)ra * k + cb] : 0.0;
-        const double xa1 = inc && ca < k ? X[(long long)rc * k + ca] : 0.0, xb1 = inc && cb < k ? X[(long long)rc * k + cb] : 0.0;
-        acc0 = mfma_16x16x4_f64(xa0, xb0, acc0);
-        acc1 = mfma_16x16x4_f64(xa1, xb1, acc1);
-    }
-#pragma unroll
-    for (int r = 0; r < 4; ++r) red[wv][(q + 4 * r) * 16 + jl] = acc0[r] + acc1[r];     // c/d[r] = C[q + 4 r][jl]
-    __syncthreads();
-    part[((long long)split * gridDim.x + tile) * 256 + tid] = ((red[0][tid] + red[1][tid]) + red[2][tid]) + red[3][tid];
+    // A[jl][q] = x[row q][ca], B[q][jl] = x[row q][cb]
+    const double h = gram_tile_f64(
+        r0, r1, [&](int r, bool in) { return in && ca < k ? X[(long long)r * k + ca] : 0.0; },
+        [&](int r, bool in) { return in && cb < k ? X[(long long)r * k + cb] : 0.0; }, red);
+    part[((long long)split * gridDim.x + tile) * 256 + threadIdx.x] = h;
 }
 
 // entry (i, j), i <= j, of the Gram matrix: the splits in order
 __device__ __forceinline__ double gram_entry(const double *part, int splits, int T, int i, int j)
 {
     const int tiles = T * (T + 1) / 2;
-    const long long at = (long long)tile_index(i >> 4, j >> 4, T) * 256 + (i & 15) * 16 + (j & 15);
+    const long long at = (long long)tri_tile_index(i >> 4, j >> 4, T) * 256 + (i & 15) * 16 + (j & 15);
     double s = 0.0;
     for (int sp = 0; sp < splits; ++sp) s += part[(long long)sp * tiles * 256 + at];
     return s;
@@ -624,30 +542,29 @@ Plan make_plan(int64_t n, int64_t nnz, int32_t d)
     p.splits = (int32_t)((n + p.rps - 1) / p.rps);
     p.slot_cap = (int32_t)(2 * (nnz / GCC_PRONE_CHUNK) + 64);
     p.right_wgs = (int32_t)((n + kRightRows - 1) / kRightRows);
-    auto al = [](int64_t x) { return (x + 255) & ~(int64_t)255; };
-    int64_t o = 0;
+    Carve cv;
     const int64_t nk = n * p.k, nd = n * d;
-    p.off_r = o; o = al(o + n * 8);
-    p.off_c = o; o = al(o + n * 8);
-    p.off_tot = o; o = al(o + 8);
-    p.off_cnt = o; o = al(o + 8);
-    p.off_long_row = o; o = al(o + (int64_t)p.slot_cap * 4);
-    p.off_long_first = o; o = al(o + (int64_t)p.slot_cap * 4);
-    p.off_slot_row = o; o = al(o + (int64_t)p.slot_cap * 4);
-    p.off_slot_part = o; o = al(o + (int64_t)p.slot_cap * 4);
-    p.off_part = o; o = al(o + (int64_t)p.slot_cap * kPartStride * 8);
-    p.off_gpart = o; o = al(o + (int64_t)p.splits * p.tiles * 256 * 8);
-    p.off_rinv = o; o = al(o + (int64_t)kMaxK * kMaxK * 8);
-    p.off_rfac = o; o = al(o + (int64_t)kMaxK * kMaxK * 8);
-    p.off_W = o; o = al(o + (int64_t)kMaxK * kMaxK * 8);
-    p.off_ev = o; o = al(o + (int64_t)kMaxK * 8);
-    p.off_scale = o; o = al(o + (int64_t)kMaxK * 8);
-    p.off_cm_abs = o; o = al(o + (int64_t)p.right_wgs * 64 * 8);
-    p.off_cm_val = o; o = al(o + (int64_t)p.right_wgs * 64 * 8);
-    p.off_cm_row = o; o = al(o + (int64_t)p.right_wgs * 64 * 4);
-    p.off_Z = o; o = al(o + nd * 8);
-    p.off_area = o; o = al(o + (2 * nk > 5 * nd ? 2 * nk : 5 * nd) * 8);
-    p.total = o;
+    p.off_r = cv.take(n * 8);
+    p.off_c = cv.take(n * 8);
+    p.off_tot = cv.take(8);
+    p.off_cnt = cv.take(8);
+    p.off_long_row = cv.take((int64_t)p.slot_cap * 4);
+    p.off_long_first = cv.take((int64_t)p.slot_cap * 4);
+    p.off_slot_row = cv.take((int64_t)p.slot_cap * 4);
+    p.off_slot_part = cv.take((int64_t)p.slot_cap * 4);
+    p.off_part = cv.take((int64_t)p.slot_cap * kPartStride * 8);
+    p.off_gpart = cv.take((int64_t)p.splits * p.tiles * 256 * 8);
+    p.off_rinv = cv.take((int64_t)kMaxK * kMaxK * 8);
+    p.off_rfac = cv.take((int64_t)kMaxK * kMaxK * 8);
+    p.off_W = cv.take((int64_t)kMaxK * kMaxK * 8);
+    p.off_ev = cv.take((int64_t)kMaxK * 8);
+    p.off_scale = cv.take((int64_t)kMaxK * 8);
+    p.off_cm_abs = cv.take((int64_t)p.right_wgs * 64 * 8);
+    p.off_cm_val = cv.take((int64_t)p.right_wgs * 64 * 8);
+    p.off_cm_row = cv.take((int64_t)p.right_wgs * 64 * 4);
+    p.off_Z = cv.take(nd * 8);
+    p.off_area = cv.take((2 * nk > 5 * nd ? 2 * nk : 5 * nd) * 8);
+    p.total = cv.total();
     return p;
 }
 
@@ -670,25 +587,19 @@ int check_sizes(const char *who, int64_t n, int64_t nnz, int32_t d)
 }
 
 struct Ws {
-    unsigned char *base;
+    void *base;
     Plan pl;
-    double *f64(int64_t off) const { return reinterpret_cast<double *>(base + off); }
-    int32_t *i32(int64_t off) const { return reinterpret_cast<int32_t *>(base + off); }
+    double *f64(int64_t off) const { return ws_at<double>(base, off); }
+    int32_t *i32(int64_t off) const { return ws_at<int32_t>(base, off); }
 };
 
 // the checks every entry point shares; fills d and ws; rc < 0 names the member in g_err
 int prepare(const char *who, const gcc_prone_args *h, void *workspace, int64_t workspace_bytes, int32_t *status, PrDev &d, Ws &ws)
 {
-    if (!h) {
-        snprintf(g_err, kErrLen, "%s: args is NULL", who);
-        return -1;
-    }
-    const int rc = check_sizes(who, h->n, h->nnz, h->d);
+    int rc = null_member(who, {{h, "args"}});
     if (rc) return rc;
-    if (!status || !h->row_ptr || (!h->col_idx && h->nnz > 0)) {
-        snprintf(g_err, kErrLen, "%s: %s is NULL", who, !status ? "status" : !h->row_ptr ? "row_ptr" : "col_idx");
-        return -1;
-    }
+    if ((rc = check_sizes(who, h->n, h->nnz, h->d))) return rc;
+    if ((rc = null_member(who, {{status, "status"}, {h->row_ptr, "row_ptr"}, {h->col_idx, "col_idx", h->nnz > 0}}))) return rc;
     int32_t chunk = h->chunk == 0 ? GCC_PRONE_CHUNK : h->chunk;
     if (chunk < GCC_PRONE_SEGMENT || chunk > GCC_PRONE_MAX_CHUNK || (chunk & (chunk - 1)) != 0) {
         snprintf(g_err, kErrLen, "%s: chunk %d must be 0 or GCC_PRONE_SEGMENT (%d) times a power of two, at most GCC_PRONE_MAX_CHUNK (%d)",
@@ -696,16 +607,8 @@ int prepare(const char *who, const gcc_prone_args *h, void *workspace, int64_t w
         return -4;
     }
     ws.pl = make_plan(h->n, h->nnz, h->d);
-    if (!workspace || workspace_bytes < ws.pl.total) {
-        snprintf(g_err, kErrLen, "%s: workspace_bytes %lld is less than gcc_prone_workspace_bytes (%lld)", who,
-                 (long long)(workspace ? workspace_bytes : 0), (long long)ws.pl.total);
-        return -8;
-    }
-    if (((uintptr_t)workspace & 15) != 0) {
-        snprintf(g_err, kErrLen, "%s: workspace must be aligned to 16 bytes", who);
-        return -9;
-    }
-    ws.base = static_cast<unsigned char *>(workspace);
+    if ((rc = check_workspace(who, "gcc_prone_workspace_bytes", workspace, workspace_bytes, ws.pl.total))) return rc;
+    ws.base = workspace;
     const Plan &pl = ws.pl;
     d = PrDev();
     d.rp = h->row_ptr; d.ci = h->col_idx; d.n = (int32_t)h->n; d.nnz = (int32_t)h->nnz; d.chunk = chunk; d.slot_cap = pl.slot_cap;
@@ -822,7 +725,7 @@ int32_t gcc_prone_node_terms(const gcc_prone_args *h, void *workspace, int64_t w
     hipStream_t s = (hipStream_t)stream;
     launch_rows(d, s);
     launch_terms(d, s);
-    return hipGetLastError() == hipSuccess ? 0 : -10;
+    return launched();
 }
 
 int32_t gcc_prone_spmm(const gcc_prone_args *h, void *workspace, int64_t workspace_bytes, int32_t *status, void *stream)
@@ -840,10 +743,7 @@ int32_t gcc_prone_spmm(const gcc_prone_args *h, void *workspace, int64_t workspa
     }
     const bool need_z = h->mode == GCC_PRONE_MODE_A1 || h->tail != GCC_PRONE_TAIL_NONE, need_w = h->tail == GCC_PRONE_TAIL_CHEB;
     const bool need_conv = h->tail != GCC_PRONE_TAIL_NONE;
-    if (!h->x || !h->y || (need_z && !h->z) || (need_w && !h->w) || (need_conv && !h->conv)) {
-        snprintf(g_err, kErrLen, "%s: %s is NULL", who, !h->x ? "x" : !h->y ? "y" : need_z && !h->z ? "z" : need_w && !h->w ? "w" : "conv");
-        return -1;
-    }
+    if ((rc = null_member(who, {{h->x, "x"}, {h->y, "y"}, {h->z, "z", need_z}, {h->w, "w", need_w}, {h->conv, "conv", need_conv}}))) return rc;
     if (h->x == h->y) {
         snprintf(g_err, kErrLen, "%s: y must not be x (rows of x are gathered while y is written)", who);
         return -7;
@@ -851,7 +751,7 @@ int32_t gcc_prone_spmm(const gcc_prone_args *h, void *workspace, int64_t workspa
     hipStream_t s = (hipStream_t)stream;
     launch_rows(d, s);
     launch_spmm(d, h->mode, h->tail, h->k, h->x, h->z, h->w, h->y, h->conv, s);
-    return hipGetLastError() == hipSuccess ? 0 : -10;
+    return launched();
 }
 
 int32_t gcc_prone_orthonormalize(const gcc_prone_args *h, void *workspace, int64_t workspace_bytes, int32_t *status, void *stream)
@@ -862,12 +762,9 @@ int32_t gcc_prone_orthonormalize(const gcc_prone_args *h, void *workspace, int64
     int rc = prepare(who, h, workspace, workspace_bytes, status, d, ws);
     if (rc) return rc;
     if ((rc = check_k(who, h))) return rc;
-    if (!h->y) {
-        snprintf(g_err, kErrLen, "%s: y is NULL", who);
-        return -1;
-    }
+    if ((rc = null_member(who, {{h->y, "y"}}))) return rc;
     launch_orth(ws, h->y, d.n, h->k, h->rfac, status, (hipStream_t)stream);
-    return hipGetLastError() == hipSuccess ? 0 : -10;
+    return launched();
 }
 
 int32_t gcc_prone_embed(const gcc_prone_args *h, void *workspace, int64_t workspace_bytes, int32_t *status, void *stream)
@@ -875,16 +772,13 @@ int32_t gcc_prone_embed(const gcc_prone_args *h, void *workspace, int64_t worksp
     const char *who = "gcc_prone_embed";
     PrDev d;
     Ws ws;
-    const int rc = prepare(who, h, workspace, workspace_bytes, status, d, ws);
+    int rc = prepare(who, h, workspace, workspace_bytes, status, d, ws);
     if (rc) return rc;
     if (h->step < 1 || h->step > GCC_PRONE_MAX_STEP) {
         snprintf(g_err, kErrLen, "%s: step %d outside 1..GCC_PRONE_MAX_STEP (%d)", who, h->step, GCC_PRONE_MAX_STEP);
         return -6;
     }
-    if (!h->omega || !h->emb || !h->emb32) {
-        snprintf(g_err, kErrLen, "%s: %s is NULL", who, !h->omega ? "omega" : !h->emb ? "emb" : "emb32");
-        return -1;
-    }
+    if ((rc = null_member(who, {{h->omega, "omega"}, {h->emb, "emb"}, {h->emb32, "emb32"}}))) return rc;
     hipStream_t s = (hipStream_t)stream;
     const Plan &pl = ws.pl;
     const int n = d.n, dd = h->d, k = pl.k;
@@ -930,7 +824,7 @@ int32_t gcc_prone_embed(const gcc_prone_args *h, void *workspace, int64_t worksp
         launch_spmm(d, GCC_PRONE_MODE_A1, 0, dd, a, conv, nullptr, mm, nullptr, s);
         launch_finish(ws, mm, mm, n, dd, dd, true, h->sigma ? h->sigma + dd : nullptr, h->emb, h->emb32, status, s);
     }
-    return hipGetLastError() == hipSuccess ? 0 : -10;
+    return launched();
 }
 
 }  // extern "C"

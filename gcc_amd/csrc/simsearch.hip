@@ -15,7 +15,8 @@
 //       p: position by ballot, shift, write).  Dpad is one of 16 / 32 / 64 / 128 / 256 so that the operand registers are static.
 //   sim_merge_kernel     one wave per query: sums the counters over the splits and merges the S sorted partial lists (lane s
 //       holds the head of list s; k rounds of a wave arg-best under the total order score descending, column ascending).
-#include "host_common.h"
+// The entry point's scaffold (workspace carving, the NULL and workspace checks) is task_common.h's.
+#include "task_common.h"
 
 #include <math.h>
 
@@ -320,19 +321,18 @@ Plan make_plan(int32_t mq, int32_t mc, int32_t D, int32_t k, int32_t splits)
     p.R = (int32_t)(r < 16 ? 16 : r);
     p.S = (int32_t)(((int64_t)mc + p.R - 1) / p.R);
     if (p.S < 1) p.S = 1;
-    auto al = [](int64_t x) { return (x + 255) & ~(int64_t)255; };
-    int64_t o = 0;
-    p.off_qn = o; o = al(o + (int64_t)mq * p.Dpad * 4);
-    p.off_cn = o; o = al(o + (int64_t)mc * p.Dpad * 4);
-    p.off_qflag = o; o = al(o + (int64_t)mq * 4);
-    p.off_cflag = o; o = al(o + (int64_t)mc * 4);
-    p.off_tgt = o; o = al(o + (int64_t)mq * 4);
-    p.off_ts = o; o = al(o + (int64_t)mq * 4);
-    p.off_pg = o; o = al(o + (int64_t)p.S * mq * 4);
-    p.off_pe = o; o = al(o + (int64_t)p.S * mq * 4);
-    p.off_ls = o; o = al(o + (int64_t)p.S * mq * k * 4);
-    p.off_lc = o; o = al(o + (int64_t)p.S * mq * k * 4);
-    p.total = o;
+    Carve cv;
+    p.off_qn = cv.take((int64_t)mq * p.Dpad * 4);
+    p.off_cn = cv.take((int64_t)mc * p.Dpad * 4);
+    p.off_qflag = cv.take((int64_t)mq * 4);
+    p.off_cflag = cv.take((int64_t)mc * 4);
+    p.off_tgt = cv.take((int64_t)mq * 4);
+    p.off_ts = cv.take((int64_t)mq * 4);
+    p.off_pg = cv.take((int64_t)p.S * mq * 4);
+    p.off_pe = cv.take((int64_t)p.S * mq * 4);
+    p.off_ls = cv.take((int64_t)p.S * mq * k * 4);
+    p.off_lc = cv.take((int64_t)p.S * mq * k * 4);
+    p.total = cv.total();
     return p;
 }
 
@@ -392,20 +392,10 @@ int64_t gcc_sim_workspace_bytes(int32_t mq, int32_t mc, int32_t D, int32_t k, in
 int32_t gcc_sim_search(const gcc_sim_args *h, void *workspace, int64_t workspace_bytes, int32_t *status, void *stream)
 {
     const char *who = "gcc_sim_search";
-    if (!h) {
-        snprintf(g_err, kErrLen, "%s: args is NULL", who);
-        return -1;
-    }
-    const int rc = check_sizes(who, h->mq, h->mc, h->D, h->k, h->splits);
+    int rc = null_member(who, {{h, "args"}});
     if (rc) return rc;
-    if (!h->emb_q || !h->emb_c) {
-        snprintf(g_err, kErrLen, "%s: %s is NULL", who, !h->emb_q ? "emb_q" : "emb_c");
-        return -1;
-    }
-    if (!status) {
-        snprintf(g_err, kErrLen, "%s: status is NULL", who);
-        return -1;
-    }
+    if ((rc = check_sizes(who, h->mq, h->mc, h->D, h->k, h->splits))) return rc;
+    if ((rc = null_member(who, {{h->emb_q, "emb_q"}, {h->emb_c, "emb_c"}, {status, "status"}}))) return rc;
     if (h->rows_q < 0 || h->rows_c < 0 || h->ld_q < h->D || h->ld_c < h->D) {
         snprintf(g_err, kErrLen, "%s: rows_q %lld / rows_c %lld must not be negative, ld_q %lld / ld_c %lld must be at least D (%d)",
                  who, (long long)h->rows_q, (long long)h->rows_c, (long long)h->ld_q, (long long)h->ld_c, h->D);
@@ -418,26 +408,17 @@ int32_t gcc_sim_search(const gcc_sim_args *h, void *workspace, int64_t workspace
     }
     if (h->mq == 0 || h->mc == 0) return 0;
     const Plan pl = make_plan(h->mq, h->mc, h->D, h->k, h->splits);
-    if (!workspace || workspace_bytes < pl.total) {
-        snprintf(g_err, kErrLen, "%s: workspace_bytes %lld is less than gcc_sim_workspace_bytes (%lld)", who,
-                 (long long)(workspace ? workspace_bytes : 0), (long long)pl.total);
-        return -8;
-    }
-    if (((uintptr_t)workspace & 15) != 0) {
-        snprintf(g_err, kErrLen, "%s: workspace must be aligned to 16 bytes", who);
-        return -9;
-    }
-    unsigned char *ws = static_cast<unsigned char *>(workspace);
+    if ((rc = check_workspace(who, "gcc_sim_workspace_bytes", workspace, workspace_bytes, pl.total))) return rc;
     SimDev d = {};
     d.emb_q = h->emb_q; d.emb_c = h->emb_c;
     d.rows_q = h->rows_q; d.ld_q = h->ld_q; d.rows_c = h->rows_c; d.ld_c = h->ld_c;
     d.q_idx = h->q_idx; d.c_idx = h->c_idx; d.target = h->target;
     d.mq = h->mq; d.mc = h->mc; d.D = h->D; d.Dpad = pl.Dpad; d.k = h->k; d.normalize = h->normalize; d.S = pl.S; d.R = pl.R;
-    d.qn = reinterpret_cast<float *>(ws + pl.off_qn); d.cn = reinterpret_cast<float *>(ws + pl.off_cn);
-    d.qflag = reinterpret_cast<int32_t *>(ws + pl.off_qflag); d.cflag = reinterpret_cast<int32_t *>(ws + pl.off_cflag);
-    d.tgt = reinterpret_cast<int32_t *>(ws + pl.off_tgt); d.ts = reinterpret_cast<float *>(ws + pl.off_ts);
-    d.part_g = reinterpret_cast<int32_t *>(ws + pl.off_pg); d.part_e = reinterpret_cast<int32_t *>(ws + pl.off_pe);
-    d.part_ls = reinterpret_cast<float *>(ws + pl.off_ls); d.part_lc = reinterpret_cast<int32_t *>(ws + pl.off_lc);
+    d.qn = ws_at<float>(workspace, pl.off_qn); d.cn = ws_at<float>(workspace, pl.off_cn);
+    d.qflag = ws_at<int32_t>(workspace, pl.off_qflag); d.cflag = ws_at<int32_t>(workspace, pl.off_cflag);
+    d.tgt = ws_at<int32_t>(workspace, pl.off_tgt); d.ts = ws_at<float>(workspace, pl.off_ts);
+    d.part_g = ws_at<int32_t>(workspace, pl.off_pg); d.part_e = ws_at<int32_t>(workspace, pl.off_pe);
+    d.part_ls = ws_at<float>(workspace, pl.off_ls); d.part_lc = ws_at<int32_t>(workspace, pl.off_lc);
     d.greater = h->greater; d.equal_before = h->equal_before; d.target_score = h->target_score;
     d.topk_col = h->topk_col; d.topk_score = h->topk_score;
     d.status = status;
@@ -449,7 +430,7 @@ int32_t gcc_sim_search(const gcc_sim_args *h, void *workspace, int64_t workspace
     if (h->k > 0) launch_tiles_nc<true>(d, pl, s);
     else launch_tiles_nc<false>(d, pl, s);
     hipLaunchKernelGGL(sim_merge_kernel, dim3((unsigned)(((long long)h->mq + wpb - 1) / wpb)), dim3(kThreads), 0, s, d);
-    return hipGetLastError() == hipSuccess ? 0 : -10;
+    return launched();
 }
 
 }  // extern "C"

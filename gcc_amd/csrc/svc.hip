@@ -18,7 +18,8 @@
 //   svc_predict_kernel   one workgroup per corpus row: for each class pair of the row's own fold, sum_t alpha_t y_t K(t, r) - rho
 //       in float64 (one wave per pair, lanes strided, fixed order), then libsvm's vote (pairs in (i < j) order, ties to the
 //       lowest class).
-#include "host_common.h"
+// The entry points' scaffold (workspace carving, the NULL and workspace checks) is task_common.h's.
+#include "task_common.h"
 
 #include <float.h>
 #include <math.h>
@@ -474,18 +475,17 @@ Plan make_plan(int32_t N, int32_t classes, int32_t folds, int32_t max_rows)
     p.pairs = classes * (classes - 1) / 2;
     p.P = folds * p.pairs;
     p.cap = max_rows < 1 ? 1 : max_rows;
-    auto al = [](int64_t x) { return (x + 255) & ~(int64_t)255; };
-    int64_t o = 0;
-    p.off_d2 = o; o = al(o + (int64_t)N * N * 4);
-    p.off_pn = o; o = al(o + (int64_t)p.P * 4);
-    p.off_pni = o; o = al(o + (int64_t)p.P * 4);
-    p.off_pdone = o; o = al(o + (int64_t)p.P * 4);
-    p.off_piter = o; o = al(o + (int64_t)p.P * 4);
-    p.off_prho = o; o = al(o + (int64_t)p.P * 8);
-    p.off_idx = o; o = al(o + (int64_t)p.P * p.cap * 4);
-    p.off_alpha = o; o = al(o + (int64_t)p.P * p.cap * 8);
-    p.off_G = o; o = al(o + (int64_t)p.P * p.cap * 8);
-    p.total = o;
+    Carve cv;
+    p.off_d2 = cv.take((int64_t)N * N * 4);
+    p.off_pn = cv.take((int64_t)p.P * 4);
+    p.off_pni = cv.take((int64_t)p.P * 4);
+    p.off_pdone = cv.take((int64_t)p.P * 4);
+    p.off_piter = cv.take((int64_t)p.P * 4);
+    p.off_prho = cv.take((int64_t)p.P * 8);
+    p.off_idx = cv.take((int64_t)p.P * p.cap * 4);
+    p.off_alpha = cv.take((int64_t)p.P * p.cap * 8);
+    p.off_G = cv.take((int64_t)p.P * p.cap * 8);
+    p.total = cv.total();
     return p;
 }
 
@@ -519,40 +519,23 @@ int check_sizes(const char *who, int32_t N, int32_t D, int32_t classes, int32_t 
 int prepare(const char *who, const gcc_svc_args *h, void *workspace, int64_t workspace_bytes, int32_t *status, bool need_labels,
             SvcDev &d, Plan &pl)
 {
-    if (!h) {
-        snprintf(g_err, kErrLen, "%s: args is NULL", who);
-        return -1;
-    }
-    const int rc = check_sizes(who, h->N, h->D, h->classes, h->folds, h->max_rows);
+    int rc = null_member(who, {{h, "args"}});
     if (rc) return rc;
-    if (!status) {
-        snprintf(g_err, kErrLen, "%s: status is NULL", who);
-        return -1;
-    }
-    if (need_labels && (!h->labels || !h->fold_of_row || !h->gamma)) {
-        snprintf(g_err, kErrLen, "%s: %s is NULL", who, !h->labels ? "labels" : !h->fold_of_row ? "fold_of_row" : "gamma");
-        return -1;
-    }
+    if ((rc = check_sizes(who, h->N, h->D, h->classes, h->folds, h->max_rows))) return rc;
+    if ((rc = null_member(who, {{status, "status"}, {h->labels, "labels", need_labels}, {h->fold_of_row, "fold_of_row", need_labels},
+                                {h->gamma, "gamma", need_labels}})))
+        return rc;
     pl = make_plan(h->N, h->classes, h->folds, h->max_rows);
-    if (!workspace || workspace_bytes < pl.total) {
-        snprintf(g_err, kErrLen, "%s: workspace_bytes %lld is less than gcc_svc_workspace_bytes (%lld)", who,
-                 (long long)(workspace ? workspace_bytes : 0), (long long)pl.total);
-        return -8;
-    }
-    if (((uintptr_t)workspace & 15) != 0) {
-        snprintf(g_err, kErrLen, "%s: workspace must be aligned to 16 bytes", who);
-        return -9;
-    }
-    unsigned char *ws = static_cast<unsigned char *>(workspace);
+    if ((rc = check_workspace(who, "gcc_svc_workspace_bytes", workspace, workspace_bytes, pl.total))) return rc;
     d = SvcDev();
     d.emb = h->emb; d.ld = h->ld; d.labels = h->labels; d.fold = h->fold_of_row; d.gamma = h->gamma;
     d.N = h->N; d.D = h->D; d.classes = h->classes; d.folds = h->folds; d.pairs = pl.pairs; d.P = pl.P; d.cap = pl.cap;
     d.budget = h->iters_per_launch; d.iter_cap = h->iter_cap; d.C = h->C; d.eps = h->eps;
-    d.d2 = reinterpret_cast<float *>(ws + pl.off_d2);
-    d.pn = reinterpret_cast<int32_t *>(ws + pl.off_pn); d.pni = reinterpret_cast<int32_t *>(ws + pl.off_pni);
-    d.pdone = reinterpret_cast<int32_t *>(ws + pl.off_pdone); d.piter = reinterpret_cast<int32_t *>(ws + pl.off_piter);
-    d.prho = reinterpret_cast<double *>(ws + pl.off_prho); d.idx = reinterpret_cast<int32_t *>(ws + pl.off_idx);
-    d.alpha = reinterpret_cast<double *>(ws + pl.off_alpha); d.G = reinterpret_cast<double *>(ws + pl.off_G);
+    d.d2 = ws_at<float>(workspace, pl.off_d2);
+    d.pn = ws_at<int32_t>(workspace, pl.off_pn); d.pni = ws_at<int32_t>(workspace, pl.off_pni);
+    d.pdone = ws_at<int32_t>(workspace, pl.off_pdone); d.piter = ws_at<int32_t>(workspace, pl.off_piter);
+    d.prho = ws_at<double>(workspace, pl.off_prho); d.idx = ws_at<int32_t>(workspace, pl.off_idx);
+    d.alpha = ws_at<double>(workspace, pl.off_alpha); d.G = ws_at<double>(workspace, pl.off_G);
     d.pred = h->pred; d.decision = h->decision; d.iters = h->iters; d.rho = h->rho; d.obj = h->obj;
     d.n_free = h->n_free; d.n_bounded = h->n_bounded; d.problem_rows = h->problem_rows; d.unfinished = h->unfinished;
     d.first_rows = h->first_rows; d.rows_out = h->rows_out; d.alpha_out = h->alpha_out;
@@ -586,12 +569,9 @@ int32_t gcc_svc_distances(const gcc_svc_args *h, void *workspace, int64_t worksp
     const char *who = "gcc_svc_distances";
     SvcDev d;
     Plan pl;
-    const int rc = prepare(who, h, workspace, workspace_bytes, status, false, d, pl);
+    int rc = prepare(who, h, workspace, workspace_bytes, status, false, d, pl);
     if (rc) return rc;
-    if (!h->emb) {
-        snprintf(g_err, kErrLen, "%s: emb is NULL", who);
-        return -1;
-    }
+    if ((rc = null_member(who, {{h->emb, "emb"}}))) return rc;
     if (h->ld < h->D) {
         snprintf(g_err, kErrLen, "%s: ld %lld must be at least D (%d)", who, (long long)h->ld, h->D);
         return -7;
@@ -603,7 +583,7 @@ int32_t gcc_svc_distances(const gcc_svc_args *h, void *workspace, int64_t worksp
     const unsigned tiles = (unsigned)((h->N + kTile - 1) / kTile);
     hipLaunchKernelGGL(svc_d2_kernel, dim3(tiles, tiles), dim3(kD2Threads), 0, (hipStream_t)stream, d);
     if (h->labels) hipLaunchKernelGGL(svc_setup_kernel, dim3(pl.P), dim3(64), 0, (hipStream_t)stream, d);
-    return hipGetLastError() == hipSuccess ? 0 : -10;
+    return launched();
 }
 
 int32_t gcc_svc_solve(const gcc_svc_args *h, void *workspace, int64_t workspace_bytes, int32_t *status, void *stream)
@@ -611,12 +591,9 @@ int32_t gcc_svc_solve(const gcc_svc_args *h, void *workspace, int64_t workspace_
     const char *who = "gcc_svc_solve";
     SvcDev d;
     Plan pl;
-    const int rc = prepare(who, h, workspace, workspace_bytes, status, true, d, pl);
+    int rc = prepare(who, h, workspace, workspace_bytes, status, true, d, pl);
     if (rc) return rc;
-    if (!h->unfinished) {
-        snprintf(g_err, kErrLen, "%s: unfinished is NULL", who);
-        return -1;
-    }
+    if ((rc = null_member(who, {{h->unfinished, "unfinished"}}))) return rc;
     if (h->iters_per_launch < 1 || h->iter_cap < 0 || !(h->C > 0.0) || !(h->eps > 0.0)) {
         snprintf(g_err, kErrLen, "%s: iters_per_launch %d must be positive, iter_cap %d not negative, C %g and eps %g positive", who,
                  h->iters_per_launch, h->iter_cap, h->C, h->eps);
@@ -626,7 +603,7 @@ int32_t gcc_svc_solve(const gcc_svc_args *h, void *workspace, int64_t workspace_
     (void)hipMemsetAsync(h->unfinished, 0, sizeof(int32_t), s);
     if (pl.cap <= kOneWaveRows) launch_smo<1>(d, s);
     else launch_smo<4>(d, s);
-    return hipGetLastError() == hipSuccess ? 0 : -10;
+    return launched();
 }
 
 int32_t gcc_svc_predict(const gcc_svc_args *h, void *workspace, int64_t workspace_bytes, int32_t *status, void *stream)
@@ -637,7 +614,7 @@ int32_t gcc_svc_predict(const gcc_svc_args *h, void *workspace, int64_t workspac
     const int rc = prepare(who, h, workspace, workspace_bytes, status, true, d, pl);
     if (rc) return rc;
     hipLaunchKernelGGL(svc_predict_kernel, dim3(h->N), dim3(64 * kPredictWaves), (size_t)pl.pairs * 12, (hipStream_t)stream, d);
-    return hipGetLastError() == hipSuccess ? 0 : -10;
+    return launched();
 }
 
 }  // extern "C"

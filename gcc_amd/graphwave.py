@@ -23,13 +23,13 @@ hub300d8 0.019, multi130d32 0.020, n40d256 0.011, task 0.17 (DESIGN.md section 5
 """
 from __future__ import annotations
 
-import ctypes
 import math
 
 import numpy as np
 import torch
 
 from . import _cabi
+from ._engine import CabiEngine
 
 ORDER = _cabi.GRAPHWAVE_ORDER
 SCALE = 100.0
@@ -119,33 +119,17 @@ def embed_numpy(row_ptr, col_idx, d):
     return dict(chi=chi, chi32=chi.astype(np.float32), heat=heat, live=live)
 
 
-class GraphWaveEngine:
+class GraphWaveEngine(CabiEngine):
     """C-ABI calls of the embedding.  ``lib``/``ptr`` are injectable for the emulator tests only."""
 
     def __init__(self, lib=None, ptr=None, device="cuda:0"):
-        self.lib = lib if lib is not None else _cabi.load()
-        self.ptr = ptr if ptr is not None else _cabi.dev_ptr
-        self.device = torch.device(device)
-        self._workspace = None
-
-    def workspace(self, nbytes):
-        ws = self._workspace
-        if ws is None or ws.numel() < nbytes:
-            self._workspace = None             # (the old one first)
-            ws = self._workspace = torch.empty(max(int(nbytes), 256), dtype=torch.uint8, device=self.device)
-        return ws
-
-    def _put(self, a, dtype):
-        if isinstance(a, torch.Tensor):
-            return a.to(dtype).contiguous()
-        return torch.from_numpy(np.ascontiguousarray(a)).to(dtype).to(self.device).contiguous()
+        super().__init__(lib, ptr, device)
 
     def graph_args(self, row_ptr, col_idx, d, width=0):
         """-> (args with the graph's members, scales' coefficients, time points and threshold filled, the tensors they point to)"""
-        if self.ptr is _cabi.dev_ptr and self.device.type != "cuda":
-            raise RuntimeError("gcc_amd kernels take device (HIP) tensors only; there is no CPU path")
+        self.require_device(self.device)
         host_rp = row_ptr.cpu().numpy() if isinstance(row_ptr, torch.Tensor) else np.asarray(row_ptr)
-        rp, ci = self._put(row_ptr, torch.int32), self._put(col_idx, torch.int32)
+        rp, ci = self.put(row_ptr, torch.int32), self.put(col_idx, torch.int32)
         n_rows, nnz = int(rp.numel()) - 1, int(ci.numel())
         a = _cabi.GccGraphwaveArgs()
         a.row_ptr, a.col_idx = self.ptr(rp), (self.ptr(ci) if nnz else None)
@@ -163,9 +147,7 @@ class GraphWaveEngine:
 
     def call(self, name, a, status, workspace_bytes=None):
         nbytes = _cabi.size_query(self.lib, "gcc_graphwave_workspace_bytes", int(a.n_rows), int(a.nnz), int(a.d), int(a.width))
-        ws = self.workspace(nbytes)
-        _cabi.call(self.lib, name, ctypes.byref(a), self.ptr(ws), ws.numel() if workspace_bytes is None else int(workspace_bytes),
-                   self.ptr(status), _cabi.raw_stream(self.device))
+        self.invoke(name, a, self.workspace(nbytes), status, workspace_bytes)
 
     def panel_width(self, n_rows, d, width=0):
         """the columns of one panel: ``width``, or the default the workspace is sized for"""
@@ -202,6 +184,4 @@ class GraphWaveEngine:
     @staticmethod
     def check_status(result):
         """Raises and names the bits of the call's status word (one host read)."""
-        bits = int(result["status"].cpu()[0])
-        if bits:
-            raise RuntimeError("gcc_graphwave: " + "; ".join(text for bit, text in STATUS_BITS.items() if bits & bit))
+        CabiEngine.raise_status(result, "gcc_graphwave", STATUS_BITS)

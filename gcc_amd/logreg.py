@@ -14,12 +14,11 @@ the iterations are split over host reads.
 """
 from __future__ import annotations
 
-import ctypes
-
 import numpy as np
 import torch
 
 from . import _cabi
+from ._engine import CabiEngine
 
 STATUS_BITS = {_cabi.STATUS_LR_BAD_FOLD: "a fold id outside [0, folds)",
                _cabi.STATUS_LR_NONFINITE: "an embedding is NaN or infinite",
@@ -28,21 +27,8 @@ STATUS_BITS = {_cabi.STATUS_LR_BAD_FOLD: "a fold id outside [0, folds)",
                _cabi.STATUS_LR_LINE_SEARCH: "a problem's line search found no decrease down to a step of 2^-40"}
 
 
-class LogRegEngine:
+class LogRegEngine(CabiEngine):
     """C-ABI calls of the classifier.  ``lib``/``ptr`` are injectable for the emulator tests only."""
-
-    def __init__(self, lib=None, ptr=None):
-        self.lib = lib if lib is not None else _cabi.load()
-        self.ptr = ptr if ptr is not None else _cabi.dev_ptr
-        self._workspace = None
-
-    def workspace(self, nbytes, device):
-        """a buffer of at least ``nbytes`` that later calls reuse (stream-ordered: calls on ONE stream may share it)"""
-        ws = self._workspace
-        if ws is None or ws.numel() < nbytes or ws.device != device:
-            self._workspace = None             # (the old one first)
-            ws = self._workspace = torch.empty(max(int(nbytes), 256), dtype=torch.uint8, device=device)
-        return ws
 
     def fit_predict_folds(self, emb, y, fold_of_row, C=1000.0, tol=1e-9, intercept_penalty=0.0, iters_per_sync=4, iter_cap=200,
                           folds=None):
@@ -52,12 +38,10 @@ class LogRegEngine:
         [folds, classes, D]; intercept float64, iters int32, grad float64 (the final max|g| / C), state int32 [folds, classes];
         status int32 [1]; syncs, the host reads of the unfinished count).  Everything runs on torch's current stream; y and
         fold_of_row may be arrays or tensors."""
-        if emb.dtype != torch.float32 or emb.dim() != 2 or (emb.shape[1] > 1 and emb.stride(1) != 1):
-            raise ValueError("emb must be a float32 matrix with unit stride along its rows")
-        if self.ptr is _cabi.dev_ptr and not emb.is_cuda:
-            raise RuntimeError("gcc_amd kernels take device (HIP) tensors only; there is no CPU path")
+        a = _cabi.GccLogregArgs()
+        a.emb, N, D, a.ld = self.table(emb)
+        a.N, a.D = N, D
         dev = emb.device
-        N, D = int(emb.shape[0]), int(emb.shape[1])
         y_t = y if isinstance(y, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(y))
         fold_t = fold_of_row if isinstance(fold_of_row, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(fold_of_row))
         if y_t.dim() != 2 or y_t.shape[0] != N or fold_t.shape != (N,):
@@ -77,8 +61,6 @@ class LogRegEngine:
                    grad=torch.empty((folds, classes), **f64), state=torch.empty((folds, classes), **i32),
                    status=torch.zeros(1, **i32))
         unfinished = torch.zeros(1, **i32)
-        a = _cabi.GccLogregArgs()
-        a.emb, a.ld, a.N, a.D = emb.data_ptr(), (int(emb.stride(0)) if N > 1 else D), N, D
         a.y, a.fold_of_row, a.classes, a.folds = self.ptr(y_d), self.ptr(fold_d), classes, int(folds)
         a.iters_per_sync, a.iter_cap = int(iters_per_sync), int(iter_cap)
         a.C, a.tol, a.intercept_penalty = float(C), float(tol), float(intercept_penalty)
@@ -86,8 +68,7 @@ class LogRegEngine:
             setattr(a, name, self.ptr(out[name]))
         a.unfinished = self.ptr(unfinished)
         ws = self.workspace(nbytes, dev)
-        stream = _cabi.raw_stream(dev)
-        call = lambda name: _cabi.call(self.lib, name, ctypes.byref(a), self.ptr(ws), ws.numel(), self.ptr(out["status"]), stream)  # noqa: E731
+        call = lambda name: self.invoke(name, a, ws, out["status"])  # noqa: E731
         call("gcc_logreg_setup")
         # every problem ends at its iteration cap at the latest, so the host reads are bounded too
         syncs = 0
@@ -106,8 +87,4 @@ class LogRegEngine:
     def check_status(result, allow_iter_cap=False):
         """Raises and names the bits of the call's status word (one host read).  The iteration cap raises unless allowed: the
         result is then the solver's state at the cap."""
-        bits = int(result["status"].cpu()[0])
-        if allow_iter_cap:
-            bits &= ~_cabi.STATUS_LR_ITER_CAP
-        if bits:
-            raise RuntimeError("gcc_logreg: " + "; ".join(text for bit, text in STATUS_BITS.items() if bits & bit))
+        CabiEngine.raise_status(result, "gcc_logreg", STATUS_BITS, _cabi.STATUS_LR_ITER_CAP if allow_iter_cap else 0)

@@ -11,12 +11,11 @@ magnitude is positive, ties to the lowest row).  Two calls on the same inputs gi
 """
 from __future__ import annotations
 
-import ctypes
-
 import numpy as np
 import torch
 
 from . import _cabi
+from ._engine import CabiEngine
 
 STATUS_BITS = {_cabi.STATUS_PRONE_BAD_CSR: "row_ptr / col_idx are not a sorted CSR without self loops over [0, n)",
                _cabi.STATUS_PRONE_DUPLICATE: "a repeated entry in a row (a multigraph parent: the reference's nx.Graph has none)",
@@ -118,32 +117,15 @@ def embed_numpy(row_ptr, col_idx, d, seed=0, omega=None, step=5, mu=0.2, theta=0
     return dict(emb=emb, emb32=emb.astype(np.float32), sigma=sigma, sigma0=sigma0, fact=fact)
 
 
-class ProNEEngine:
+class ProNEEngine(CabiEngine):
     """C-ABI calls of the embedding.  ``lib``/``ptr`` are injectable for the emulator tests only."""
 
     def __init__(self, lib=None, ptr=None, device="cuda:0"):
-        self.lib = lib if lib is not None else _cabi.load()
-        self.ptr = ptr if ptr is not None else _cabi.dev_ptr
-        self.device = torch.device(device)
-        self._workspace = None
-
-    def workspace(self, nbytes):
-        ws = self._workspace
-        if ws is None or ws.numel() < nbytes:
-            self._workspace = None             # (the old one first)
-            ws = self._workspace = torch.empty(max(int(nbytes), 256), dtype=torch.uint8, device=self.device)
-        return ws
-
-    def _put(self, a, dtype):
-        """a contiguous tensor of ``dtype`` where the kernels run; a tensor that is already one is passed as it is (the product
-        path then refuses a CPU tensor by name)"""
-        if isinstance(a, torch.Tensor):
-            return a.to(dtype).contiguous()
-        return torch.from_numpy(np.ascontiguousarray(a)).to(dtype).to(self.device).contiguous()
+        super().__init__(lib, ptr, device)
 
     def graph_args(self, row_ptr, col_idx, d, chunk=0):
         """-> (args with the graph's members filled, the tensors they point to, n)"""
-        rp, ci = self._put(row_ptr, torch.int32), self._put(col_idx, torch.int32)
+        rp, ci = self.put(row_ptr, torch.int32), self.put(col_idx, torch.int32)
         n, nnz = int(rp.numel()) - 1, int(ci.numel())
         a = _cabi.GccProneArgs()
         a.row_ptr, a.col_idx = self.ptr(rp), (self.ptr(ci) if nnz else None)
@@ -152,16 +134,14 @@ class ProNEEngine:
 
     def call(self, name, a, status, workspace_bytes=None):
         nbytes = _cabi.size_query(self.lib, "gcc_prone_workspace_bytes", int(a.n), int(a.nnz), int(a.d))
-        ws = self.workspace(nbytes)
-        _cabi.call(self.lib, name, ctypes.byref(a), self.ptr(ws), ws.numel() if workspace_bytes is None else int(workspace_bytes),
-                   self.ptr(status), _cabi.raw_stream(self.device))
+        self.invoke(name, a, self.workspace(nbytes), status, workspace_bytes)
 
     def embed(self, row_ptr, col_idx, d, seed=0, omega=None, step=5, mu=0.2, theta=0.5, chunk=0):
         """row_ptr [n + 1], col_idx [nnz] (arrays or tensors); ``omega``: float64 [n, d + 10], default ``draw_omega(n, d, seed)``.
         -> dict(emb float64 [n, d], emb32 float32 [n, d], sigma float64 [d] (the last decomposition's singular values), sigma0
         (the factorisation's), status int32 [1]).  Everything is enqueued on torch's current stream; nothing is read back."""
-        if isinstance(row_ptr, torch.Tensor) and self.ptr is _cabi.dev_ptr and not row_ptr.is_cuda:
-            raise RuntimeError("gcc_amd kernels take device (HIP) tensors only; there is no CPU path")
+        if isinstance(row_ptr, torch.Tensor):
+            self.require_device(row_ptr)
         if not 1 <= int(step) <= _cabi.PRONE_MAX_STEP:
             raise ValueError(f"step {step} outside 1..{_cabi.PRONE_MAX_STEP}")
         a, keep, n = self.graph_args(row_ptr, col_idx, d, chunk)
@@ -171,7 +151,7 @@ class ProNEEngine:
                 omega = np.zeros((max(n, 0), k))
             else:
                 omega = draw_omega(n, int(d), seed)
-        om = self._put(omega, torch.float64)
+        om = self.put(omega, torch.float64)
         if tuple(om.shape) != (n, k):
             raise ValueError(f"omega must be [n, d + 10] = [{n}, {k}], got {tuple(om.shape)}")
         dev = om.device
@@ -195,8 +175,4 @@ class ProNEEngine:
     @staticmethod
     def check_status(result, allow_sweeps=False):
         """Raises and names the bits of the call's status word (one host read)."""
-        bits = int(result["status"].cpu()[0])
-        if allow_sweeps:
-            bits &= ~_cabi.STATUS_PRONE_SWEEPS
-        if bits:
-            raise RuntimeError("gcc_prone: " + "; ".join(text for bit, text in STATUS_BITS.items() if bits & bit))
+        CabiEngine.raise_status(result, "gcc_prone", STATUS_BITS, _cabi.STATUS_PRONE_SWEEPS if allow_sweeps else 0)

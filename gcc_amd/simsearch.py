@@ -8,42 +8,28 @@ so the two can be checked against each other.
 """
 from __future__ import annotations
 
-import ctypes
-
 import torch
 
 from . import _cabi
+from ._engine import CabiEngine
 
 STATUS_BITS = {_cabi.STATUS_SIM_ZERO_ROW: "a selected row has norm 0 (the reference would divide by zero)",
                _cabi.STATUS_SIM_BAD_INDEX: "a q_idx / c_idx entry outside its table or a target outside [-1, mc)"}
 
 
-class SimilarityEngine:
+class SimilarityEngine(CabiEngine):
     """C-ABI calls of the similarity search.  ``lib``/``ptr`` are injectable for the emulator tests only."""
-
-    def __init__(self, lib=None, ptr=None):
-        self.lib = lib if lib is not None else _cabi.load()
-        self.ptr = ptr if ptr is not None else _cabi.dev_ptr
-        self._workspace = None
-
-    def workspace(self, nbytes, device):
-        """a buffer of at least ``nbytes`` that later calls reuse (stream-ordered: calls on ONE stream may share it)"""
-        ws = self._workspace
-        if ws is None or ws.numel() < nbytes or ws.device != device:
-            ws = self._workspace = torch.empty(max(int(nbytes), 256), dtype=torch.uint8, device=device)
-        return ws
 
     def search(self, emb_q, emb_c, q_idx=None, c_idx=None, target=None, k=0, normalize=True, splits=0, stream=None):
         """emb_q [rows_q, D] / emb_c [rows_c, D]: float32, unit stride along D (a row stride larger than D is served).
         q_idx / c_idx: int32 rows of the tables (None: every row in order); target: int32 [mq], the candidate column of each
         query's true match or -1.  -> dict(greater, equal_before int32 [mq]; target_score float32 [mq]; topk_col int32 /
         topk_score float32 [mq, k]; status int32 [1]; mq, mc, k).  Nothing is read back here: see check_status / recall_at_k."""
-        for name, t in (("emb_q", emb_q), ("emb_c", emb_c)):
-            if t.dtype != torch.float32 or t.dim() != 2 or (t.numel() > 0 and t.shape[1] > 1 and t.stride(1) != 1):
-                raise ValueError(f"{name} must be a float32 matrix with unit stride along its rows")
-        if emb_q.shape[1] != emb_c.shape[1]:
-            raise ValueError(f"emb_q has {emb_q.shape[1]} columns, emb_c {emb_c.shape[1]}")
-        D = int(emb_q.shape[1])
+        a = _cabi.GccSimArgs()
+        a.emb_q, a.rows_q, D, a.ld_q = self.table(emb_q, "emb_q")
+        a.emb_c, a.rows_c, Dc, a.ld_c = self.table(emb_c, "emb_c")
+        if D != Dc:
+            raise ValueError(f"emb_q has {D} columns, emb_c {Dc}")
         dev = emb_q.device
         for name, t in (("q_idx", q_idx), ("c_idx", c_idx), ("target", target)):
             if t is not None and (t.dtype != torch.int32 or t.dim() != 1 or not t.is_contiguous()):
@@ -65,26 +51,13 @@ class SimilarityEngine:
         nbytes = _cabi.size_query(self.lib, "gcc_sim_workspace_bytes", mq, mc, D, k, int(splits))
         if not served:                         # nothing to search: the outputs keep their padding
             return out
-        a = _cabi.GccSimArgs()
-        a.emb_q, a.rows_q, a.ld_q = self._table(emb_q)
-        a.emb_c, a.rows_c, a.ld_c = self._table(emb_c)
         a.q_idx, a.c_idx, a.target = self.ptr(q_idx), self.ptr(c_idx), self.ptr(target)
         a.mq, a.mc, a.D, a.k, a.normalize, a.splits = mq, mc, D, k, int(bool(normalize)), int(splits)
         a.greater, a.equal_before, a.target_score = self.ptr(out["greater"]), self.ptr(out["equal_before"]), self.ptr(out["target_score"])
         if k > 0:
             a.topk_col, a.topk_score = self.ptr(out["topk_col"]), self.ptr(out["topk_score"])
-        ws = self.workspace(nbytes, dev)
-        if stream is None:
-            stream = _cabi.raw_stream(dev)
-        _cabi.call(self.lib, "gcc_sim_search", ctypes.byref(a), self.ptr(ws), ws.numel(), self.ptr(out["status"]), stream)
+        self.invoke("gcc_sim_search", a, self.workspace(nbytes, dev), out["status"], stream=stream)
         return out
-
-    def _table(self, t):
-        """(address, rows, row stride) of an embedding table; a view with a row stride larger than D is passed as it is"""
-        if self.ptr is _cabi.dev_ptr and not t.is_cuda:
-            raise RuntimeError("gcc_amd kernels take device (HIP) tensors only; there is no CPU path")
-        rows, D = int(t.shape[0]), int(t.shape[1])
-        return t.data_ptr(), rows, int(t.stride(0)) if rows > 1 else D
 
     @staticmethod
     def recall_at_k(result, ks):
@@ -100,8 +73,4 @@ class SimilarityEngine:
     def check_status(result, allow_zero_rows=False):
         """Raises and names the bits of the call's status word (one host read).  A zero row raises unless allowed: the
         reference would divide by zero there; here it scores 0 against everything."""
-        bits = int(result["status"].cpu()[0])
-        if allow_zero_rows:
-            bits &= ~_cabi.STATUS_SIM_ZERO_ROW
-        if bits:
-            raise RuntimeError("gcc_sim_search: " + "; ".join(text for bit, text in STATUS_BITS.items() if bits & bit))
+        CabiEngine.raise_status(result, "gcc_sim_search", STATUS_BITS, _cabi.STATUS_SIM_ZERO_ROW if allow_zero_rows else 0)

@@ -10,12 +10,11 @@ is reproducible, and the result does not depend on how the iterations are split 
 """
 from __future__ import annotations
 
-import ctypes
-
 import numpy as np
 import torch
 
 from . import _cabi
+from ._engine import CabiEngine
 
 STATUS_BITS = {_cabi.STATUS_SVC_BAD_LABEL: "a label outside [0, classes)",
                _cabi.STATUS_SVC_BAD_FOLD: "a fold id outside [0, folds)",
@@ -36,30 +35,12 @@ def largest_problem(labels, fold_of_row, classes, folds):
     return int((train[:, -1] + train[:, -2]).max())
 
 
-class SVCEngine:
+class SVCEngine(CabiEngine):
     """C-ABI calls of the classifier.  ``lib``/``ptr`` are injectable for the emulator tests only."""
 
-    def __init__(self, lib=None, ptr=None):
-        self.lib = lib if lib is not None else _cabi.load()
-        self.ptr = ptr if ptr is not None else _cabi.dev_ptr
-        self._workspace = None
-
-    def workspace(self, nbytes, device):
-        """a buffer of at least ``nbytes`` that later calls reuse (stream-ordered: calls on ONE stream may share it)"""
-        ws = self._workspace
-        if ws is None or ws.numel() < nbytes or ws.device != device:
-            self._workspace = None             # (the old one first: a corpus of 16,384 rows needs a GiB)
-            ws = self._workspace = torch.empty(max(int(nbytes), 256), dtype=torch.uint8, device=device)
-        return ws
-
     def _emb_args(self, emb):
-        if emb.dtype != torch.float32 or emb.dim() != 2 or (emb.shape[1] > 1 and emb.stride(1) != 1):
-            raise ValueError("emb must be a float32 matrix with unit stride along its rows")
-        if self.ptr is _cabi.dev_ptr and not emb.is_cuda:
-            raise RuntimeError("gcc_amd kernels take device (HIP) tensors only; there is no CPU path")
-        N, D = int(emb.shape[0]), int(emb.shape[1])
         a = _cabi.GccSvcArgs()
-        a.emb, a.ld, a.N, a.D = emb.data_ptr(), (int(emb.stride(0)) if N > 1 else D), N, D
+        a.emb, a.N, a.D, a.ld = self.table(emb)
         return a
 
     def distances(self, emb):
@@ -69,8 +50,7 @@ class SVCEngine:
         nbytes = _cabi.size_query(self.lib, "gcc_svc_workspace_bytes", a.N, a.D, 2, 1, 0)
         ws = self.workspace(nbytes, emb.device)
         status = torch.zeros(1, dtype=torch.int32, device=emb.device)
-        _cabi.call(self.lib, "gcc_svc_distances", ctypes.byref(a), self.ptr(ws), ws.numel(), self.ptr(status),
-                   _cabi.raw_stream(emb.device))
+        self.invoke("gcc_svc_distances", a, ws, status)
         return ws[: a.N * a.N * 4].view(torch.float32).view(a.N, a.N), status
 
     def fit_predict_folds(self, emb, labels, fold_of_row, C=1e5, tol=1e-3, iters_per_launch=65536, iter_cap=0, classes=None,
@@ -119,8 +99,7 @@ class SVCEngine:
         a.unfinished, a.first_rows = self.ptr(unfinished), self.ptr(out["first_rows"])
         a.rows_out, a.alpha_out = self.ptr(out["rows"]), self.ptr(out["alpha"])
         ws = self.workspace(nbytes, dev)
-        stream = _cabi.raw_stream(dev)
-        call = lambda name: _cabi.call(self.lib, name, ctypes.byref(a), self.ptr(ws), ws.numel(), self.ptr(out["status"]), stream)  # noqa: E731
+        call = lambda name: self.invoke(name, a, ws, out["status"])  # noqa: E731
         call("gcc_svc_distances")
         # every problem ends at its iteration cap at the latest, so the launches are bounded too
         cap = iter_cap if iter_cap > 0 else max(10 ** 7, 100 * max_rows)
@@ -154,8 +133,4 @@ class SVCEngine:
     def check_status(result, allow_iter_cap=False):
         """Raises and names the bits of the call's status word (one host read).  The iteration cap raises unless allowed:
         libsvm only warns there, and the result is the solver's state at the cap."""
-        bits = int(result["status"].cpu()[0])
-        if allow_iter_cap:
-            bits &= ~_cabi.STATUS_SVC_ITER_CAP
-        if bits:
-            raise RuntimeError("gcc_svc: " + "; ".join(text for bit, text in STATUS_BITS.items() if bits & bit))
+        CabiEngine.raise_status(result, "gcc_svc", STATUS_BITS, _cabi.STATUS_SVC_ITER_CAP if allow_iter_cap else 0)

@@ -20,21 +20,7 @@ import argparse
 
 import numpy as np
 
-from .similarity_search import load_embedding
-
-FOLDS = 10
-
-
-def fold_ids(labels, seed, folds=FOLDS):
-    """fold_of_row [N] int32: the fold whose test side holds the row, from the reference's StratifiedKFold"""
-    try:
-        from sklearn.model_selection import StratifiedKFold
-    except ImportError as e:                    # never another split silently: the folds are the reference's or none
-        raise RuntimeError("graph classification needs scikit-learn (the reference's StratifiedKFold picks the folds)") from e
-    fold = np.full(len(labels), -1, dtype=np.int32)
-    for f, (_, test) in enumerate(StratifiedKFold(n_splits=folds, shuffle=True, random_state=seed).split(np.zeros(len(labels)), labels)):
-        fold[test] = f
-    return fold
+from ._common import FOLDS, checkpoint_table, fold_ids, load_embedding  # noqa: F401  (fold_ids, load_embedding: importable from here)
 
 
 def classify_sklearn(emb, labels, fold, C):
@@ -98,16 +84,7 @@ def load_labels(a):
 
 def embed_corpus(a, pipeline=None):
     """the corpus embedded with the checkpoint ``--load-path`` (gcc_amd.generate.run) -> float32 [graphs, hidden]"""
-    import torch
-
-    from ..generate import run
-
-    dev = torch.device(a.device)
-    g = argparse.Namespace(load_path=a.load_path, dataset=a.dataset, gpu=dev.index if dev.type == "cuda" else None, edgelist=None,
-                           nodelabel=None, ss_graph=None, ss_dict=None, graph_npz=None, graphs_npz=a.graphs_npz,
-                           tudataset=a.tudataset, edge_multiplicity=0, batch_size=a.batch_size, wide_eval="chain",
-                           graph_batcher="auto")
-    return run(g, pipeline=pipeline, save=False).numpy()
+    return checkpoint_table(a.load_path, a.dataset, a.device, a.batch_size, pipeline, graphs_npz=a.graphs_npz, tudataset=a.tudataset)
 
 
 def main(argv=None, pipeline=None, engine=None):

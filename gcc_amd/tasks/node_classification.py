@@ -33,10 +33,7 @@ import argparse
 
 import numpy as np
 
-from .graph_classification import fold_ids
-from .similarity_search import load_embedding
-
-FOLDS = 10
+from ._common import FOLDS, baseline_table, checkpoint_table, fold_ids, load_embedding
 SOLVERS = {"lbfgs": 0.0, "liblinear": 1.0}      # -> the intercept's penalty
 
 
@@ -133,47 +130,27 @@ def load_labels(a):
 
 def embed_nodes(a, pipeline=None):
     """the nodes embedded with the checkpoint ``--load-path`` (gcc_amd.generate.run) -> float32 [nodes, hidden]"""
-    import torch
-
-    from ..generate import run
-
-    dev = torch.device(a.device)
-    g = argparse.Namespace(load_path=a.load_path, dataset=a.dataset, gpu=dev.index if dev.type == "cuda" else None,
-                           edgelist=a.edgelist, nodelabel=a.nodelabel, ss_graph=None, ss_dict=None, graph_npz=None, graphs_npz=None,
-                           tudataset=None, edge_multiplicity=0, batch_size=a.batch_size, wide_eval="chain", graph_batcher="auto")
-    return run(g, pipeline=pipeline, save=False).numpy()
+    return checkpoint_table(a.load_path, a.dataset, a.device, a.batch_size, pipeline, edgelist=a.edgelist, nodelabel=a.nodelabel)
 
 
 def embed_prone(a, prone_engine=None):
     """the ProNE table of ``--edgelist`` (gcc/tasks/__init__.py: build_model("prone")) -> float32 [nodes, hidden]"""
     from .. import ingest
-    from ..prone import ProNEEngine, embed_numpy
 
     g = ingest.read_edgelist(a.edgelist)
-    d = 64 if a.hidden_size is None else a.hidden_size
-    seed = a.seed if a.prone_seed is None else a.prone_seed
-    if prone_engine is None and str(a.device) == "cpu":
-        return embed_numpy(g["row_ptr"], g["col_idx"], d, seed=seed)["emb32"]
-    engine = prone_engine if prone_engine is not None else ProNEEngine(device=a.device)
-    res = engine.embed(g["row_ptr"], g["col_idx"], d, seed=seed)
-    engine.check_status(res)
-    return res["emb32"].cpu().numpy()
+    return baseline_table("prone", g["row_ptr"], g["col_idx"], 64 if a.hidden_size is None else a.hidden_size, a.device, prone_engine,
+                          seed=a.seed if a.prone_seed is None else a.prone_seed)
 
 
 def embed_graphwave(a, graphwave_engine=None):
     """the GraphWave table of ``--edgelist`` (gcc/tasks/__init__.py: build_model("graphwave")) -> float32 [nodes, hidden]"""
     from .. import ingest
-    from ..graphwave import GraphWaveEngine, check_width, embed_numpy
+    from ..graphwave import check_width
 
     g = ingest.read_edgelist(a.edgelist)
     d = 64 if a.hidden_size is None else a.hidden_size
     check_width(d)
-    if graphwave_engine is None and str(a.device) == "cpu":
-        return embed_numpy(g["row_ptr"], g["col_idx"], d)["chi32"]
-    engine = graphwave_engine if graphwave_engine is not None else GraphWaveEngine(device=a.device)
-    res = engine.embed(g["row_ptr"], g["col_idx"], d)
-    engine.check_status(res)
-    return res["chi32"].cpu().numpy()
+    return baseline_table("graphwave", g["row_ptr"], g["col_idx"], d, a.device, graphwave_engine)
 
 
 def main(argv=None, pipeline=None, engine=None, prone_engine=None, graphwave_engine=None):

@@ -29,6 +29,7 @@ import os
 import numpy as np
 
 from ..ingest import read_ss_graph
+from ._common import baseline_table, checkpoint_table, load_embedding  # noqa: F401  (load_embedding: importable from here)
 
 
 def select_keys(dict_1, dict_2, rows_1, rows_2):
@@ -107,21 +108,6 @@ def evaluate(emb_1, emb_2, dict_1, dict_2, ks=(20, 40), device="cpu", with_topk=
     return result, detail
 
 
-def load_embedding(path):
-    """a ``.npy`` table as ``generate.py`` writes it, or a ``.npz`` that holds one (its only array, or the one named "emb")"""
-    if not os.path.isfile(path):
-        raise FileNotFoundError(f"embedding file not found: {path}")
-    a = np.load(path)
-    if isinstance(a, np.lib.npyio.NpzFile):
-        keys = list(a.keys())
-        if "emb" not in keys and len(keys) != 1:
-            raise ValueError(f"{path}: expected one array or one named 'emb', found {keys}")
-        a = a["emb" if "emb" in keys else keys[0]]
-    if a.ndim != 2:
-        raise ValueError(f"{path}: expected a [nodes, dim] table, found shape {a.shape}")
-    return a
-
-
 def load_dicts(data_root, dataset):
     parts = dataset.split("_")
     if len(parts) != 2 or not all(parts):
@@ -139,36 +125,19 @@ def load_dicts(data_root, dataset):
 def embed_networks(data_root, dataset, load_path, batch_size=256, device="cuda:0", pipeline=None):
     """Both networks of ``dataset`` embedded with the checkpoint ``load_path`` (gcc_amd.generate.run on ``--ss-graph``) ->
     [table 1, table 2], float32 [nodes of the graph file, hidden].  ``pipeline``: generate.py's seam for the emulator tests."""
-    import torch
-
-    from ..generate import run
-
-    dev = torch.device(device)
-    tables = []
-    for name in dataset.split("_"):
-        a = argparse.Namespace(load_path=load_path, dataset=name, gpu=dev.index if dev.type == "cuda" else None, edgelist=None,
-                               nodelabel=None, ss_graph=os.path.join(data_root, name + ".graph"),
-                               ss_dict=os.path.join(data_root, name + ".dict"), graph_npz=None, graphs_npz=None, tudataset=None,
-                               edge_multiplicity=0, batch_size=batch_size, wide_eval="chain", graph_batcher="auto")
-        tables.append(run(a, pipeline=pipeline, save=False).numpy())
-    return tables
+    return [checkpoint_table(load_path, name, device, batch_size, pipeline, ss_graph=os.path.join(data_root, name + ".graph"),
+                             ss_dict=os.path.join(data_root, name + ".dict")) for name in dataset.split("_")]
 
 
 def embed_graphwave(data_root, dataset, hidden_size=64, device="cuda:0", graphwave_engine=None):
     """Both networks of ``dataset`` as GraphWave tables -> [table 1, table 2], float32 [nodes of the graph file, hidden_size]"""
-    from ..graphwave import GraphWaveEngine, check_width, embed_numpy
+    from ..graphwave import check_width
 
     check_width(hidden_size)
     tables = []
     for name in dataset.split("_"):
         g = read_ss_graph(os.path.join(data_root, name + ".graph"), os.path.join(data_root, name + ".dict"), csr=True)
-        if graphwave_engine is None and str(device) == "cpu":
-            tables.append(embed_numpy(g["row_ptr"], g["col_idx"], hidden_size)["chi32"])
-            continue
-        eng = graphwave_engine if graphwave_engine is not None else GraphWaveEngine(device=device)
-        res = eng.embed(g["row_ptr"], g["col_idx"], hidden_size)
-        eng.check_status(res)
-        tables.append(res["chi32"].cpu().numpy())
+        tables.append(baseline_table("graphwave", g["row_ptr"], g["col_idx"], hidden_size, device, graphwave_engine))
     return tables
 
 

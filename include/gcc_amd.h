@@ -988,7 +988,8 @@ int32_t gcc_logreg_predict(const gcc_logreg_args *a, void *workspace, int64_t wo
  * right, the segment sums are added as a binary counter adds them (two sums of 2^l segments each make one of 2^(l+1); what is
  * left at the end is added from the lowest level up).  A row longer than `chunk` neighbours is split into parts of `chunk`, one
  * wave group each, whose sums go to the workspace and are added by the same rule; `chunk` is GCC_PRONE_SEGMENT times a power of
- * two, so every chunk gives the same bits.  No floating-point atomics anywhere: every sum depends on the sizes alone. */
+ * two, so every chunk gives the same bits.  No floating-point atomics anywhere: every sum depends on the sizes alone.  The one
+ * implementation of the counter is SumCounter in gcc_amd/csrc/task_common.h; gcc_graphwave_* sums with it too. */
 #define GCC_PRONE_MAX_DIM 64
 #define GCC_PRONE_OVERSAMPLE 10
 #define GCC_PRONE_MAX_K (GCC_PRONE_MAX_DIM + GCC_PRONE_OVERSAMPLE)
