@@ -263,6 +263,27 @@ STATUS_SVC_ITER_CAP = 16
 STATUS_SVC_OVERFLOW = 32
 
 
+class GccSvcSearchArgs(ctypes.Structure):    # gcc_svc_search_args: the grid search over C (csrc/svc.hip)
+    _fields_ = [
+        ("emb", _VP), ("ld", ctypes.c_int64),
+        ("labels", _VP), ("fold_of_row", _VP), ("inner_of_row", _VP), ("gamma", _VP), ("inner_gamma", _VP), ("Cs", _VP),
+        ("C_of_fold", _VP),
+        ("N", ctypes.c_int32), ("D", ctypes.c_int32), ("classes", ctypes.c_int32), ("folds", ctypes.c_int32),
+        ("inner", ctypes.c_int32), ("candidates", ctypes.c_int32), ("max_rows", ctypes.c_int32), ("max_inner_rows", ctypes.c_int32),
+        ("iters_per_launch", ctypes.c_int32), ("iter_cap", ctypes.c_int32),
+        ("eps", ctypes.c_double),
+        ("unfinished", _VP), ("search_status", _VP), ("correct", _VP), ("search_iters", _VP), ("search_rho", _VP),
+        ("search_problem_rows", _VP), ("search_first_rows", _VP), ("search_rows", _VP), ("search_alpha", _VP),
+        ("pred", _VP), ("decision", _VP), ("iters", _VP), ("rho", _VP), ("obj", _VP), ("n_free", _VP), ("n_bounded", _VP),
+        ("problem_rows", _VP), ("first_rows", _VP), ("rows_out", _VP), ("alpha_out", _VP),
+    ]
+
+
+SVC_SEARCH_MAX_CANDIDATES = 16
+SVC_SEARCH_MAX_INNER = 16
+SVC_SEARCH_MAX_PROBLEMS = 32768
+
+
 class GccLogregArgs(ctypes.Structure):       # gcc_logreg_args: logistic regression on frozen embeddings (csrc/logreg.hip)
     _fields_ = [
         ("emb", _VP), ("ld", ctypes.c_int64),
@@ -514,6 +535,10 @@ SIGNATURES = {
                                        ctypes.c_void_p]),
     "gcc_svc_predict": (ctypes.c_int32, [ctypes.POINTER(GccSvcArgs), ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p,
                                          ctypes.c_void_p]),
+    "gcc_svc_search_workspace_bytes": (ctypes.c_int64, [ctypes.c_int32] * 8),
+    **{name: (ctypes.c_int32, [ctypes.POINTER(GccSvcSearchArgs), ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p])
+       for name in ("gcc_svc_search_setup", "gcc_svc_search_solve", "gcc_svc_search_score", "gcc_svc_search_refit",
+                    "gcc_svc_search_predict")},
     "gcc_logreg_workspace_bytes": (ctypes.c_int64, [ctypes.c_int32] * 4),
     "gcc_logreg_setup": (ctypes.c_int32, [ctypes.POINTER(GccLogregArgs), ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p,
                                           ctypes.c_void_p]),

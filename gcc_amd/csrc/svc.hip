@@ -7,7 +7,7 @@
 //   svc_d2_kernel        64 x 64 tiles of d2[i, j] = sum_c (x_i[c] - x_j[c])^2: the differences themselves, one fmaf chain over
 //       c = 0 .. D-1 per entry, so d2[i, j] and d2[j, i] are the same chain on negated differences (bitwise equal) and the
 //       diagonal is exactly 0.  Flags non-finite embeddings.
-//   svc_setup_kernel     one wave per problem (fold f, class pair ci < cj): the fold's training rows of the two classes in
+//   svc_setup_kernel     one wave per row list (fold f, class pair ci < cj): the fold's training rows of the two classes in
 //       libsvm's order (class ci's rows ascending, then class cj's), alpha = 0, G = -1; checks labels and fold ids.
 //   svc_smo_kernel<W>    one workgroup of W waves per problem, alpha and G (float64) in LDS.  An iteration is two selections
 //       (i = argmax over I_up of -y G; j = argmax over I_low of b^2 / a), each a wave butterfly under the total order (key
@@ -18,6 +18,13 @@
 //   svc_predict_kernel   one workgroup per corpus row: for each class pair of the row's own fold, sum_t alpha_t y_t K(t, r) - rho
 //       in float64 (one wave per pair, lanes strided, fixed order), then libsvm's vote (pairs in (i < j) order, ties to the
 //       lowest class).
+//   svc_score_kernel     the grid search: one workgroup per (corpus row, outer fold other than the row's own); the row's vote under
+//       every candidate C from the problems of its inner fold (svc_predict_kernel's sum and vote), counted into correct[o, c, i]
+//       with integer atomics.
+// A problem is (fold, inner fold or none, class pair, candidate): problems p = g * cands + c of one row list g = (fold * ninner +
+// inner) * pairs + pair share the list and differ in C; the plain call and the search's refit have ninner = cands = 1, so p = g =
+// fold * pairs + pair.  gcc_svc_search_* solves the folds * inner * pairs * candidates problems of sklearn's
+// GridSearchCV(SVC(), {"C": ...}, cv=inner) side by side over the one distance matrix, then the refit at each fold's winner.
 // The entry points' scaffold (workspace carving, the NULL and workspace checks) is task_common.h's.
 #include "task_common.h"
 
@@ -36,21 +43,31 @@ struct SvcDev {
     const float *emb;
     long long ld;
     const int32_t *labels, *fold;
-    const double *gamma;
-    int32_t N, D, classes, folds, pairs, P, cap, budget, iter_cap;
+    const int32_t *inner;                     // [folds][N] the inner fold of a row on the fold's training side, or NULL (no inner folds)
+    const double *gamma;                      // [folds * ninner]
+    const double *Cs, *Cf;                    // [cands] the candidates' C / [folds] one C per fold; both NULL: C
+    int32_t N, D, classes, folds, ninner, cands, pairs, groups, P, cap, budget, iter_cap;
     double C, eps;
     float *d2;                                // [N][N]
-    int32_t *pn, *pni, *pdone, *piter;        // [P]: rows, rows of the first class, state, iterations so far
-    int32_t *idx;                             // [P][cap] corpus rows
+    int32_t *pn, *pni;                        // [groups]: rows, rows of the first class
+    int32_t *pdone, *piter;                   // [P]: state, iterations so far
+    int32_t *idx;                             // [groups][cap] corpus rows
     double *alpha, *G, *prho;                 // [P][cap], [P][cap], [P]
     int32_t *pred;
     double *decision;
     int32_t *iters;
     double *rho, *obj;
     int32_t *n_free, *n_bounded, *problem_rows, *first_rows, *rows_out;
-    double *alpha_out;                        // [P][cap] or NULL, as rows_out
+    double *alpha_out;                        // [P][cap] or NULL; rows_out [groups][cap] or NULL
+    int32_t *correct;                         // [folds][cands][ninner], svc_score_kernel
     int32_t *unfinished, *status;
 };
+
+// the box bound of problem p of row list g
+__device__ __forceinline__ double problem_C(const SvcDev &a, int p, int g)
+{
+    return a.Cs ? a.Cs[p % a.cands] : a.Cf ? a.Cf[g / a.pairs] : a.C;
+}
 
 __global__ __launch_bounds__(kD2Threads) void svc_d2_kernel(SvcDev a)
 {
@@ -110,38 +127,50 @@ __device__ __forceinline__ void pair_classes(int pair, int classes, int &ci, int
     cj = ci + 1 + pair;
 }
 
+// row r on the side of (fold f, inner fold in): 1 = trains, 2 = held out, 0 = neither.  Without inner folds the held-out side is
+// the fold's own rows; with them it is the rows of the fold's training side whose inner fold is `in`.
+__device__ __forceinline__ int row_side(const SvcDev &a, const int32_t *inner, int f, int in, int r, int fo)
+{
+    if (r >= a.N || fo < 0 || fo >= a.folds) return 0;
+    if (!inner) return fo != f ? 1 : 2;
+    if (fo == f) return 0;
+    return inner[r] != in ? 1 : 2;
+}
+
 __global__ __launch_bounds__(64) void svc_setup_kernel(SvcDev a)
 {
-    const int p = (int)blockIdx.x, lane = lane_id();
-    const int f = p / a.pairs;
+    const int g = (int)blockIdx.x, lane = lane_id();
+    const int fi = g / a.pairs, f = fi / a.ninner, in = fi % a.ninner;
+    const int32_t *inner = a.inner ? a.inner + (long long)f * a.N : nullptr;
     int ci, cj;
-    pair_classes(p % a.pairs, a.classes, ci, cj);
+    pair_classes(g % a.pairs, a.classes, ci, cj);
     int ni = 0, nj = 0, ti = 0, tj = 0, bits = 0;
     for (int r0 = 0; r0 < a.N; r0 += 64) {
         const int r = r0 + lane;
         const int lab = r < a.N ? a.labels[r] : -1, fo = r < a.N ? a.fold[r] : -1;
         if (wave_ballot(r < a.N && (lab < 0 || lab >= a.classes))) bits |= GCC_STATUS_SVC_BAD_LABEL;     // (bits: wave-uniform)
         if (wave_ballot(r < a.N && (fo < 0 || fo >= a.folds))) bits |= GCC_STATUS_SVC_BAD_FOLD;
-        const bool live = r < a.N && fo >= 0 && fo < a.folds, train = live && fo != f, test = live && fo == f;
-        ni += __popcll(wave_ballot(train && lab == ci));
-        nj += __popcll(wave_ballot(train && lab == cj));
-        ti += __popcll(wave_ballot(test && lab == ci));
-        tj += __popcll(wave_ballot(test && lab == cj));
+        const int side = row_side(a, inner, f, in, r, fo);
+        if (wave_ballot(inner && side != 0 && (inner[r] < 0 || inner[r] >= a.ninner))) bits |= GCC_STATUS_SVC_BAD_FOLD;
+        ni += __popcll(wave_ballot(side == 1 && lab == ci));
+        nj += __popcll(wave_ballot(side == 1 && lab == cj));
+        ti += __popcll(wave_ballot(side == 2 && lab == ci));
+        tj += __popcll(wave_ballot(side == 2 && lab == cj));
     }
     if ((ni == 0 && ti > 0) || (nj == 0 && tj > 0)) bits |= GCC_STATUS_SVC_MISSING_CLASS;
     const int n = ni + nj;
     const bool fits = n <= a.cap;
     if (!fits) bits |= GCC_STATUS_SVC_OVERFLOW;                     // (the workspace was sized for smaller problems: nothing written)
     const bool solve = fits && ni > 0 && nj > 0;
-    const long long base = (long long)p * a.cap;
+    const long long gbase = (long long)g * a.cap;
     if (solve) {
         int bi = 0, bj = ni;
         for (int r0 = 0; r0 < a.N; r0 += 64) {
             const int r = r0 + lane;
             const int lab = r < a.N ? a.labels[r] : -1, fo = r < a.N ? a.fold[r] : -1;
-            const bool train = r < a.N && fo >= 0 && fo < a.folds && fo != f;
+            const bool train = row_side(a, inner, f, in, r, fo) == 1;
             const unsigned long long mi = wave_ballot(train && lab == ci), mj = wave_ballot(train && lab == cj);
-            const long long at = base + (lab == ci ? bi + __popcll(mi & lanemask_lt()) : bj + __popcll(mj & lanemask_lt()));
+            const long long at = gbase + (lab == ci ? bi + __popcll(mi & lanemask_lt()) : bj + __popcll(mj & lanemask_lt()));
             if (train && (lab == ci || lab == cj)) {
                 a.idx[at] = r;
                 if (a.rows_out) a.rows_out[at] = r;
@@ -149,21 +178,28 @@ __global__ __launch_bounds__(64) void svc_setup_kernel(SvcDev a)
             bi += __popcll(mi);
             bj += __popcll(mj);
         }
-        for (int t = lane; t < n; t += 64) { a.alpha[base + t] = 0.0; a.G[base + t] = -1.0; }
+    }
+    for (int c = 0; c < a.cands; ++c) {                             // the problems of the row list: cold starts
+        const int p = g * a.cands + c;
+        const long long base = (long long)p * a.cap;
+        if (solve)
+            for (int t = lane; t < n; t += 64) { a.alpha[base + t] = 0.0; a.G[base + t] = -1.0; }
+        if (lane == 0) {
+            a.pdone[p] = solve ? kRunning : kSkipped;
+            a.piter[p] = 0;
+            a.prho[p] = 0.0;
+            if (a.iters) a.iters[p] = 0;
+            if (a.rho) a.rho[p] = 0.0;
+            if (a.obj) a.obj[p] = 0.0;
+            if (a.n_free) a.n_free[p] = 0;
+            if (a.n_bounded) a.n_bounded[p] = 0;
+        }
     }
     if (lane == 0) {
-        a.pn[p] = solve ? n : 0;
-        a.pni[p] = solve ? ni : 0;
-        a.pdone[p] = solve ? kRunning : kSkipped;
-        a.piter[p] = 0;
-        a.prho[p] = 0.0;
-        if (a.problem_rows) a.problem_rows[p] = n;
-        if (a.first_rows) a.first_rows[p] = ni;
-        if (a.iters) a.iters[p] = 0;
-        if (a.rho) a.rho[p] = 0.0;
-        if (a.obj) a.obj[p] = 0.0;
-        if (a.n_free) a.n_free[p] = 0;
-        if (a.n_bounded) a.n_bounded[p] = 0;
+        a.pn[g] = solve ? n : 0;
+        a.pni[g] = solve ? ni : 0;
+        if (a.problem_rows) a.problem_rows[g] = n;
+        if (a.first_rows) a.first_rows[g] = ni;
         if (bits) atomicOr(a.status, (int32_t)bits);
     }
 }
@@ -237,13 +273,14 @@ __global__ __launch_bounds__(64 * kWaves) void svc_smo_kernel(SvcDev a)
     int32_t *idx_s = reinterpret_cast<int32_t *>(Qi_s + cap);       // [cap]
     const int p = (int)blockIdx.x, tid = (int)threadIdx.x, lane = lane_id(), wv = tid >> 6;
     if (a.pdone[p] != kRunning) return;                             // (the whole workgroup)
-    const int n = a.pn[p], ni = a.pni[p], iter0 = a.piter[p];
-    const double gamma = a.gamma[p / a.pairs], C = a.C, eps = a.eps;
-    const long long base = (long long)p * cap;
+    const int g = p / a.cands;                                      // the problem's row list
+    const int n = a.pn[g], ni = a.pni[g], iter0 = a.piter[p];
+    const double gamma = a.gamma[g / a.pairs], C = problem_C(a, p, g), eps = a.eps;
+    const long long base = (long long)p * cap, gbase = (long long)g * cap;
     for (int t = tid; t < n; t += T) {
         alpha_s[t] = a.alpha[base + t];
         G_s[t] = a.G[base + t];
-        idx_s[t] = a.idx[base + t];
+        idx_s[t] = a.idx[gbase + t];
     }
     block_sync<kWaves>();                                           // idx_s of the selected rows is read by every thread
     // libsvm's cap: max(10^7, 100 n) iterations, unless the caller passes its own
@@ -416,6 +453,39 @@ __global__ __launch_bounds__(64 * kWaves) void svc_smo_kernel(SvcDev a)
     }
 }
 
+// sum_t alpha_t y_t K(t, row) - rho of problem p of row list g, `row` = the corpus row's distances: one wave, lanes strided, one
+// fixed order (every lane gets the value)
+__device__ __forceinline__ double decision_value(const SvcDev &a, int p, int g, const float *row, int lane)
+{
+    const int n = a.pn[g], ni = a.pni[g];
+    const double gamma = a.gamma[g / a.pairs];
+    const long long base = (long long)p * a.cap, gbase = (long long)g * a.cap;
+    double s = 0.0;
+    for (int t = lane; t < n; t += 64) {
+        const double al = a.alpha[base + t];
+        if (al > 0.0) s += (t < ni ? al : -al) * exp(-gamma * (double)row[a.idx[gbase + t]]);
+    }
+    return wave_sum(s) - a.prho[p];
+}
+
+// libsvm's vote over the solved pairs in (ci < cj) order, ties to the lowest class; -1 without a vote
+__device__ __forceinline__ int vote_of(int classes, const double *dec, const int32_t *live)
+{
+    int votes[GCC_SVC_MAX_CLASSES];
+    for (int c = 0; c < classes; ++c) votes[c] = 0;
+    int pair = 0, any = 0;
+    for (int ci = 0; ci < classes; ++ci)
+        for (int cj = ci + 1; cj < classes; ++cj, ++pair)
+            if (live[pair]) {
+                ++votes[dec[pair] > 0.0 ? ci : cj];
+                any = 1;
+            }
+    int bestc = 0;
+    for (int c = 1; c < classes; ++c)
+        if (votes[c] > votes[bestc]) bestc = c;
+    return any ? bestc : -1;
+}
+
 __global__ __launch_bounds__(64 * kPredictWaves) void svc_predict_kernel(SvcDev a)
 {
     DYN_SMEM(smem);
@@ -429,19 +499,9 @@ __global__ __launch_bounds__(64 * kPredictWaves) void svc_predict_kernel(SvcDev 
         double dec = 0.0;
         int live = 0;
         if (served) {
-            const int p = f * a.pairs + pair;
+            const int p = f * a.pairs + pair;                       // (no inner folds, one candidate: the row list is p too)
             live = a.pdone[p] != kSkipped;
-            if (live) {
-                const int n = a.pn[p], ni = a.pni[p];
-                const double gamma = a.gamma[f];
-                const long long base = (long long)p * a.cap;
-                double s = 0.0;
-                for (int t = lane; t < n; t += 64) {
-                    const double al = a.alpha[base + t];
-                    if (al > 0.0) s += (t < ni ? al : -al) * exp(-gamma * (double)row[a.idx[base + t]]);
-                }
-                dec = wave_sum(s) - a.prho[p];
-            }
+            if (live) dec = decision_value(a, p, p, row, lane);
         }
         if (lane == 0) {
             dec_s[pair] = dec;
@@ -450,41 +510,93 @@ __global__ __launch_bounds__(64 * kPredictWaves) void svc_predict_kernel(SvcDev 
         }
     }
     __syncthreads();
-    if (tid == 0 && a.pred) {
-        int votes[GCC_SVC_MAX_CLASSES];
-        for (int c = 0; c < a.classes; ++c) votes[c] = 0;
-        int pair = 0, any = 0;
-        for (int ci = 0; ci < a.classes; ++ci)
-            for (int cj = ci + 1; cj < a.classes; ++cj, ++pair)
-                if (live_s[pair]) {
-                    ++votes[dec_s[pair] > 0.0 ? ci : cj];
-                    any = 1;
-                }
-        int bestc = 0;
-        for (int c = 1; c < a.classes; ++c)
-            if (votes[c] > votes[bestc]) bestc = c;
-        a.pred[r] = any ? bestc : -1;
+    if (tid == 0 && a.pred) a.pred[r] = vote_of(a.classes, dec_s, live_s);
+}
+
+// grid (N, folds): row r as a held-out row of outer fold f's inner split -- its vote under every candidate, from the problems that
+// left its inner fold out; a right vote adds 1 to correct[f][c][inner fold].  A row of fold f's own test side has no inner fold.
+__global__ __launch_bounds__(64 * kPredictWaves) void svc_score_kernel(SvcDev a)
+{
+    DYN_SMEM(smem);
+    const int items = a.cands * a.pairs;
+    double *dec_s = reinterpret_cast<double *>(smem);               // [cands][pairs]
+    int32_t *live_s = reinterpret_cast<int32_t *>(dec_s + items);   // [cands][pairs]
+    const int r = (int)blockIdx.x, f = (int)blockIdx.y, tid = (int)threadIdx.x, lane = lane_id(), wv = tid >> 6;
+    const int fo = a.fold[r], lab = a.labels[r];
+    if (fo < 0 || fo >= a.folds || fo == f) return;                 // (the whole workgroup, as the next)
+    const int in = a.inner[(long long)f * a.N + r];
+    if (in < 0 || in >= a.ninner) return;
+    const float *row = a.d2 + (long long)r * a.N;
+    for (int item = wv; item < items; item += kPredictWaves) {
+        const int c = item / a.pairs;
+        const int g = (f * a.ninner + in) * a.pairs + item % a.pairs, p = g * a.cands + c;
+        const int live = a.pdone[p] != kSkipped;
+        const double dec = live ? decision_value(a, p, g, row, lane) : 0.0;
+        if (lane == 0) {
+            dec_s[item] = dec;
+            live_s[item] = live;
+        }
+    }
+    __syncthreads();
+    if (tid < a.cands) {
+        const int pred = vote_of(a.classes, dec_s + tid * a.pairs, live_s + tid * a.pairs);
+        if (pred >= 0 && pred == lab) atomicAdd(a.correct + ((long long)f * a.cands + tid) * a.ninner + in, 1);
     }
 }
 
-struct Plan { int32_t pairs, P, cap; int64_t off_d2, off_pn, off_pni, off_pdone, off_piter, off_prho, off_idx, off_alpha, off_G, total; };
+// the state of a set of problems in the workspace: `groups` row lists of `cap` rows, `P` problems
+struct Pieces {
+    int32_t groups, P, cap;
+    int64_t off_pn, off_pni, off_pdone, off_piter, off_prho, off_idx, off_alpha, off_G;
+    void carve(Carve &cv, int32_t groups_, int32_t P_, int32_t max_rows)
+    {
+        groups = groups_;
+        P = P_;
+        cap = max_rows < 1 ? 1 : max_rows;
+        off_pn = cv.take((int64_t)groups * 4);
+        off_pni = cv.take((int64_t)groups * 4);
+        off_pdone = cv.take((int64_t)P * 4);
+        off_piter = cv.take((int64_t)P * 4);
+        off_prho = cv.take((int64_t)P * 8);
+        off_idx = cv.take((int64_t)groups * cap * 4);
+        off_alpha = cv.take((int64_t)P * cap * 8);
+        off_G = cv.take((int64_t)P * cap * 8);
+    }
+    void bind(SvcDev &d, void *workspace) const
+    {
+        d.groups = groups; d.P = P; d.cap = cap;
+        d.pn = ws_at<int32_t>(workspace, off_pn); d.pni = ws_at<int32_t>(workspace, off_pni);
+        d.pdone = ws_at<int32_t>(workspace, off_pdone); d.piter = ws_at<int32_t>(workspace, off_piter);
+        d.prho = ws_at<double>(workspace, off_prho); d.idx = ws_at<int32_t>(workspace, off_idx);
+        d.alpha = ws_at<double>(workspace, off_alpha); d.G = ws_at<double>(workspace, off_G);
+    }
+};
+
+struct Plan { int32_t pairs; int64_t off_d2, total; Pieces pc; };
 
 Plan make_plan(int32_t N, int32_t classes, int32_t folds, int32_t max_rows)
 {
     Plan p;
     p.pairs = classes * (classes - 1) / 2;
-    p.P = folds * p.pairs;
-    p.cap = max_rows < 1 ? 1 : max_rows;
     Carve cv;
     p.off_d2 = cv.take((int64_t)N * N * 4);
-    p.off_pn = cv.take((int64_t)p.P * 4);
-    p.off_pni = cv.take((int64_t)p.P * 4);
-    p.off_pdone = cv.take((int64_t)p.P * 4);
-    p.off_piter = cv.take((int64_t)p.P * 4);
-    p.off_prho = cv.take((int64_t)p.P * 8);
-    p.off_idx = cv.take((int64_t)p.P * p.cap * 4);
-    p.off_alpha = cv.take((int64_t)p.P * p.cap * 8);
-    p.off_G = cv.take((int64_t)p.P * p.cap * 8);
+    p.pc.carve(cv, folds * p.pairs, folds * p.pairs, max_rows);
+    p.total = cv.total();
+    return p;
+}
+
+// the grid search: the refit's problems (folds * pairs, as the plain call's) and the inner problems
+struct SearchPlan { int32_t pairs; int64_t off_d2, total; Pieces refit, inner; };
+
+SearchPlan make_search_plan(int32_t N, int32_t classes, int32_t folds, int32_t inner, int32_t candidates, int32_t max_rows,
+                            int32_t max_inner_rows)
+{
+    SearchPlan p;
+    p.pairs = classes * (classes - 1) / 2;
+    Carve cv;
+    p.off_d2 = cv.take((int64_t)N * N * 4);
+    p.refit.carve(cv, folds * p.pairs, folds * p.pairs, max_rows);
+    p.inner.carve(cv, folds * inner * p.pairs, folds * inner * p.pairs * candidates, max_inner_rows);
     p.total = cv.total();
     return p;
 }
@@ -529,13 +641,10 @@ int prepare(const char *who, const gcc_svc_args *h, void *workspace, int64_t wor
     if ((rc = check_workspace(who, "gcc_svc_workspace_bytes", workspace, workspace_bytes, pl.total))) return rc;
     d = SvcDev();
     d.emb = h->emb; d.ld = h->ld; d.labels = h->labels; d.fold = h->fold_of_row; d.gamma = h->gamma;
-    d.N = h->N; d.D = h->D; d.classes = h->classes; d.folds = h->folds; d.pairs = pl.pairs; d.P = pl.P; d.cap = pl.cap;
+    d.N = h->N; d.D = h->D; d.classes = h->classes; d.folds = h->folds; d.ninner = 1; d.cands = 1; d.pairs = pl.pairs;
     d.budget = h->iters_per_launch; d.iter_cap = h->iter_cap; d.C = h->C; d.eps = h->eps;
     d.d2 = ws_at<float>(workspace, pl.off_d2);
-    d.pn = ws_at<int32_t>(workspace, pl.off_pn); d.pni = ws_at<int32_t>(workspace, pl.off_pni);
-    d.pdone = ws_at<int32_t>(workspace, pl.off_pdone); d.piter = ws_at<int32_t>(workspace, pl.off_piter);
-    d.prho = ws_at<double>(workspace, pl.off_prho); d.idx = ws_at<int32_t>(workspace, pl.off_idx);
-    d.alpha = ws_at<double>(workspace, pl.off_alpha); d.G = ws_at<double>(workspace, pl.off_G);
+    pl.pc.bind(d, workspace);
     d.pred = h->pred; d.decision = h->decision; d.iters = h->iters; d.rho = h->rho; d.obj = h->obj;
     d.n_free = h->n_free; d.n_bounded = h->n_bounded; d.problem_rows = h->problem_rows; d.unfinished = h->unfinished;
     d.first_rows = h->first_rows; d.rows_out = h->rows_out; d.alpha_out = h->alpha_out;
@@ -551,6 +660,93 @@ template <int kWaves> void launch_smo(const SvcDev &d, hipStream_t s)
         (void)hipFuncSetAttribute((const void *)svc_smo_kernel<kWaves>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
 #endif
     hipLaunchKernelGGL((svc_smo_kernel<kWaves>), dim3(d.P), dim3(64 * kWaves), lds, s, d);
+}
+// one launch of every unfinished problem of d: one wave or four by the capacity of a row list
+void launch_solve(const SvcDev &d, hipStream_t s)
+{
+    (void)hipMemsetAsync(d.unfinished, 0, sizeof(int32_t), s);
+    if (d.cap <= kOneWaveRows) launch_smo<1>(d, s);
+    else launch_smo<4>(d, s);
+}
+void launch_predict(const SvcDev &d, hipStream_t s)
+{
+    hipLaunchKernelGGL(svc_predict_kernel, dim3(d.N), dim3(64 * kPredictWaves), (size_t)d.pairs * 12, s, d);
+}
+int check_solver(const char *who, int32_t iters_per_launch, int32_t iter_cap, double C, double eps)
+{
+    if (iters_per_launch < 1 || iter_cap < 0 || !(C > 0.0) || !(eps > 0.0)) {
+        snprintf(g_err, kErrLen, "%s: iters_per_launch %d must be positive, iter_cap %d not negative, C %g and eps %g positive", who,
+                 iters_per_launch, iter_cap, C, eps);
+        return -7;
+    }
+    return 0;
+}
+
+// ------------------------------------------------------------------------------------------------------------ grid search
+int check_search_sizes(const char *who, int32_t N, int32_t D, int32_t classes, int32_t folds, int32_t inner, int32_t candidates,
+                       int32_t max_rows, int32_t max_inner_rows)
+{
+    const int rc = check_sizes(who, N, D, classes, folds, max_rows);
+    if (rc) return rc;
+    if (inner < 2 || inner > GCC_SVC_SEARCH_MAX_INNER) {
+        snprintf(g_err, kErrLen, "%s: inner %d outside 2..GCC_SVC_SEARCH_MAX_INNER (%d)", who, inner, GCC_SVC_SEARCH_MAX_INNER);
+        return -11;
+    }
+    if (candidates < 1 || candidates > GCC_SVC_SEARCH_MAX_CANDIDATES) {
+        snprintf(g_err, kErrLen, "%s: candidates %d outside 1..GCC_SVC_SEARCH_MAX_CANDIDATES (%d)", who, candidates,
+                 GCC_SVC_SEARCH_MAX_CANDIDATES);
+        return -12;
+    }
+    if (max_inner_rows < 0 || max_inner_rows > max_rows) {
+        snprintf(g_err, kErrLen, "%s: max_inner_rows %d outside 0..max_rows (%d): an inner problem is part of its fold's", who,
+                 max_inner_rows, max_rows);
+        return -13;
+    }
+    const int64_t problems = (int64_t)folds * inner * (classes * (classes - 1) / 2) * candidates;
+    if (problems > GCC_SVC_SEARCH_MAX_PROBLEMS) {
+        snprintf(g_err, kErrLen, "%s: %lld inner problems (folds * inner * class pairs * candidates) are more than "
+                 "GCC_SVC_SEARCH_MAX_PROBLEMS (%d)", who, (long long)problems, GCC_SVC_SEARCH_MAX_PROBLEMS);
+        return -14;
+    }
+    return 0;
+}
+
+// the checks every search entry point shares; fills rf (the refit's problems, as the plain call's) and in (the inner problems,
+// whose bits go to search_status)
+int prepare_search(const char *who, const gcc_svc_search_args *h, void *workspace, int64_t workspace_bytes, int32_t *status, SvcDev &rf,
+                   SvcDev &in, SearchPlan &pl)
+{
+    int rc = null_member(who, {{h, "args"}});
+    if (rc) return rc;
+    if ((rc = check_search_sizes(who, h->N, h->D, h->classes, h->folds, h->inner, h->candidates, h->max_rows, h->max_inner_rows)))
+        return rc;
+    if ((rc = null_member(who, {{status, "status"}, {h->search_status, "search_status"}, {h->labels, "labels"},
+                                {h->fold_of_row, "fold_of_row"}, {h->inner_of_row, "inner_of_row"}, {h->gamma, "gamma"},
+                                {h->inner_gamma, "inner_gamma"}, {h->Cs, "Cs"}, {h->unfinished, "unfinished"}})))
+        return rc;
+    if ((rc = check_solver(who, h->iters_per_launch, h->iter_cap, 1.0, h->eps))) return rc;
+    pl = make_search_plan(h->N, h->classes, h->folds, h->inner, h->candidates, h->max_rows, h->max_inner_rows);
+    if ((rc = check_workspace(who, "gcc_svc_search_workspace_bytes", workspace, workspace_bytes, pl.total))) return rc;
+    rf = SvcDev();
+    rf.emb = h->emb; rf.ld = h->ld; rf.labels = h->labels; rf.fold = h->fold_of_row; rf.gamma = h->gamma; rf.Cf = h->C_of_fold;
+    rf.N = h->N; rf.D = h->D; rf.classes = h->classes; rf.folds = h->folds; rf.ninner = 1; rf.cands = 1; rf.pairs = pl.pairs;
+    rf.budget = h->iters_per_launch; rf.iter_cap = h->iter_cap; rf.C = 0.0; rf.eps = h->eps;
+    rf.d2 = ws_at<float>(workspace, pl.off_d2);
+    rf.unfinished = h->unfinished;
+    in = rf;
+    pl.refit.bind(rf, workspace);
+    rf.pred = h->pred; rf.decision = h->decision; rf.iters = h->iters; rf.rho = h->rho; rf.obj = h->obj;
+    rf.n_free = h->n_free; rf.n_bounded = h->n_bounded; rf.problem_rows = h->problem_rows;
+    rf.first_rows = h->first_rows; rf.rows_out = h->rows_out; rf.alpha_out = h->alpha_out;
+    rf.status = status;
+    pl.inner.bind(in, workspace);
+    in.inner = h->inner_of_row; in.gamma = h->inner_gamma; in.Cs = h->Cs; in.Cf = nullptr;
+    in.ninner = h->inner; in.cands = h->candidates;
+    in.iters = h->search_iters; in.rho = h->search_rho; in.problem_rows = h->search_problem_rows;
+    in.first_rows = h->search_first_rows; in.rows_out = h->search_rows; in.alpha_out = h->search_alpha;
+    in.correct = h->correct;
+    in.status = h->search_status;
+    return 0;
 }
 
 }  // namespace
@@ -582,7 +778,7 @@ int32_t gcc_svc_distances(const gcc_svc_args *h, void *workspace, int64_t worksp
     }
     const unsigned tiles = (unsigned)((h->N + kTile - 1) / kTile);
     hipLaunchKernelGGL(svc_d2_kernel, dim3(tiles, tiles), dim3(kD2Threads), 0, (hipStream_t)stream, d);
-    if (h->labels) hipLaunchKernelGGL(svc_setup_kernel, dim3(pl.P), dim3(64), 0, (hipStream_t)stream, d);
+    if (h->labels) hipLaunchKernelGGL(svc_setup_kernel, dim3(d.groups), dim3(64), 0, (hipStream_t)stream, d);
     return launched();
 }
 
@@ -594,15 +790,8 @@ int32_t gcc_svc_solve(const gcc_svc_args *h, void *workspace, int64_t workspace_
     int rc = prepare(who, h, workspace, workspace_bytes, status, true, d, pl);
     if (rc) return rc;
     if ((rc = null_member(who, {{h->unfinished, "unfinished"}}))) return rc;
-    if (h->iters_per_launch < 1 || h->iter_cap < 0 || !(h->C > 0.0) || !(h->eps > 0.0)) {
-        snprintf(g_err, kErrLen, "%s: iters_per_launch %d must be positive, iter_cap %d not negative, C %g and eps %g positive", who,
-                 h->iters_per_launch, h->iter_cap, h->C, h->eps);
-        return -7;
-    }
-    hipStream_t s = (hipStream_t)stream;
-    (void)hipMemsetAsync(h->unfinished, 0, sizeof(int32_t), s);
-    if (pl.cap <= kOneWaveRows) launch_smo<1>(d, s);
-    else launch_smo<4>(d, s);
+    if ((rc = check_solver(who, h->iters_per_launch, h->iter_cap, h->C, h->eps))) return rc;
+    launch_solve(d, (hipStream_t)stream);
     return launched();
 }
 
@@ -613,7 +802,86 @@ int32_t gcc_svc_predict(const gcc_svc_args *h, void *workspace, int64_t workspac
     Plan pl;
     const int rc = prepare(who, h, workspace, workspace_bytes, status, true, d, pl);
     if (rc) return rc;
-    hipLaunchKernelGGL(svc_predict_kernel, dim3(h->N), dim3(64 * kPredictWaves), (size_t)pl.pairs * 12, (hipStream_t)stream, d);
+    launch_predict(d, (hipStream_t)stream);
+    return launched();
+}
+
+int64_t gcc_svc_search_workspace_bytes(int32_t N, int32_t D, int32_t classes, int32_t folds, int32_t inner, int32_t candidates,
+                                       int32_t max_rows, int32_t max_inner_rows)
+{
+    const int rc = check_search_sizes("gcc_svc_search_workspace_bytes", N, D, classes, folds, inner, candidates, max_rows, max_inner_rows);
+    if (rc) return rc;
+    return make_search_plan(N, classes, folds, inner, candidates, max_rows, max_inner_rows).total;
+}
+
+int32_t gcc_svc_search_setup(const gcc_svc_search_args *h, void *workspace, int64_t workspace_bytes, int32_t *status, void *stream)
+{
+    const char *who = "gcc_svc_search_setup";
+    SvcDev rf, in;
+    SearchPlan pl;
+    int rc = prepare_search(who, h, workspace, workspace_bytes, status, rf, in, pl);
+    if (rc) return rc;
+    if ((rc = null_member(who, {{h->emb, "emb"}}))) return rc;
+    if (h->ld < h->D) {
+        snprintf(g_err, kErrLen, "%s: ld %lld must be at least D (%d)", who, (long long)h->ld, h->D);
+        return -7;
+    }
+    hipStream_t s = (hipStream_t)stream;
+    const unsigned tiles = (unsigned)((h->N + kTile - 1) / kTile);
+    hipLaunchKernelGGL(svc_d2_kernel, dim3(tiles, tiles), dim3(kD2Threads), 0, s, rf);
+    hipLaunchKernelGGL(svc_setup_kernel, dim3(rf.groups), dim3(64), 0, s, rf);
+    hipLaunchKernelGGL(svc_setup_kernel, dim3(in.groups), dim3(64), 0, s, in);
+    return launched();
+}
+
+int32_t gcc_svc_search_solve(const gcc_svc_search_args *h, void *workspace, int64_t workspace_bytes, int32_t *status, void *stream)
+{
+    SvcDev rf, in;
+    SearchPlan pl;
+    const int rc = prepare_search("gcc_svc_search_solve", h, workspace, workspace_bytes, status, rf, in, pl);
+    if (rc) return rc;
+    launch_solve(in, (hipStream_t)stream);
+    return launched();
+}
+
+int32_t gcc_svc_search_score(const gcc_svc_search_args *h, void *workspace, int64_t workspace_bytes, int32_t *status, void *stream)
+{
+    const char *who = "gcc_svc_search_score";
+    SvcDev rf, in;
+    SearchPlan pl;
+    int rc = prepare_search(who, h, workspace, workspace_bytes, status, rf, in, pl);
+    if (rc) return rc;
+    if ((rc = null_member(who, {{h->correct, "correct"}}))) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    const size_t lds = (size_t)in.cands * in.pairs * 12;
+#ifndef GCC_AMD_HIPEMU
+    if (lds > 64 * 1024)
+        (void)hipFuncSetAttribute((const void *)svc_score_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+#endif
+    (void)hipMemsetAsync(h->correct, 0, sizeof(int32_t) * (size_t)h->folds * h->candidates * h->inner, s);
+    hipLaunchKernelGGL(svc_score_kernel, dim3(h->N, h->folds), dim3(64 * kPredictWaves), lds, s, in);
+    return launched();
+}
+
+int32_t gcc_svc_search_refit(const gcc_svc_search_args *h, void *workspace, int64_t workspace_bytes, int32_t *status, void *stream)
+{
+    const char *who = "gcc_svc_search_refit";
+    SvcDev rf, in;
+    SearchPlan pl;
+    int rc = prepare_search(who, h, workspace, workspace_bytes, status, rf, in, pl);
+    if (rc) return rc;
+    if ((rc = null_member(who, {{h->C_of_fold, "C_of_fold"}}))) return rc;
+    launch_solve(rf, (hipStream_t)stream);
+    return launched();
+}
+
+int32_t gcc_svc_search_predict(const gcc_svc_search_args *h, void *workspace, int64_t workspace_bytes, int32_t *status, void *stream)
+{
+    SvcDev rf, in;
+    SearchPlan pl;
+    const int rc = prepare_search("gcc_svc_search_predict", h, workspace, workspace_bytes, status, rf, in, pl);
+    if (rc) return rc;
+    launch_predict(rf, (hipStream_t)stream);
     return launched();
 }
 

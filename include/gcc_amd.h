@@ -916,6 +916,69 @@ int32_t gcc_svc_distances(const gcc_svc_args *a, void *workspace, int64_t worksp
 int32_t gcc_svc_solve(const gcc_svc_args *a, void *workspace, int64_t workspace_bytes, int32_t *status, void *stream);
 int32_t gcc_svc_predict(const gcc_svc_args *a, void *workspace, int64_t workspace_bytes, int32_t *status, void *stream);
 
+/* The grid search over C of the same task (svc_classify(x, y, search=True): GridSearchCV(SVC(), {"C": [...]}, cv=inner,
+ * scoring="accuracy") per outer fold, refit at the winner).  inner_of_row[o, r] is the inner fold of row r on outer fold o's
+ * training side (-1 on its test side; the caller computes it, for the reference with StratifiedKFold(inner) over the
+ * training rows in corpus order).  An inner problem is (outer fold o, inner fold i, class pair, candidate c): it trains on the rows
+ * with fold_of_row != o and inner_of_row[o] != i, with C = Cs[c] and gamma = inner_gamma[o, i], from alpha = 0; problem index
+ * ((o * inner + i) * pairs + pair) * candidates + c.  The candidates of one (o, i, pair) share their row list.  All of them are
+ * solved side by side over the ONE distance matrix, one workgroup each, by the solver of gcc_svc_solve:
+ *   gcc_svc_search_setup    the distances, the row lists and cold starts of the inner problems and of the refit's (fold, pair) problems
+ *   gcc_svc_search_solve    at most iters_per_launch iterations of every unfinished inner problem; *unfinished as gcc_svc_solve
+ *   gcc_svc_search_score    every row's vote (gcc_svc_predict's sum and vote) as a held-out row of each outer fold other than its
+ *                           own, under every candidate: correct[o, c, i] = the right votes among the rows of inner fold i (integer
+ *                           atomics; a row none of whose pairs was solved has no vote and counts as wrong).  The caller reads the
+ *                           table, picks the winners and writes C_of_fold
+ *   gcc_svc_search_refit    gcc_svc_solve on the (fold, pair) problems with C = C_of_fold[fold]; *unfinished likewise
+ *   gcc_svc_search_predict  gcc_svc_predict on them
+ * For a fold whose C_of_fold is C the refit's outputs are bit-identical to those of the gcc_svc_* calls with that C.  The bits that
+ * the inner problems raise (MISSING_CLASS where an inner training side lacks a class, ITER_CAP, ...) go to *search_status, those of
+ * the distances and the refit to *status.  Limits: at most GCC_SVC_SEARCH_MAX_CANDIDATES candidates, 2..GCC_SVC_SEARCH_MAX_INNER
+ * inner folds, folds * inner * pairs * candidates <= GCC_SVC_SEARCH_MAX_PROBLEMS (one workgroup and 16 * max_inner_rows bytes of
+ * workspace each), max_inner_rows <= max_rows <= GCC_SVC_MAX_PROBLEM_ROWS. */
+#define GCC_SVC_SEARCH_MAX_CANDIDATES 16
+#define GCC_SVC_SEARCH_MAX_INNER 16
+#define GCC_SVC_SEARCH_MAX_PROBLEMS 32768
+typedef struct gcc_svc_search_args {
+    const float *emb; int64_t ld;          /* device [N, ld], ld >= D */
+    const int32_t *labels, *fold_of_row;   /* device [N], as gcc_svc_args */
+    const int32_t *inner_of_row;           /* device [folds, N] */
+    const double *gamma;                   /* device [folds]: the refit's, as gcc_svc_args */
+    const double *inner_gamma;             /* device [folds, inner] */
+    const double *Cs;                      /* device [candidates], each > 0 */
+    const double *C_of_fold;               /* device [folds], read by gcc_svc_search_refit only */
+    int32_t N, D, classes, folds, inner, candidates;
+    int32_t max_rows;                      /* the largest refit problem's rows */
+    int32_t max_inner_rows;                /* the largest inner problem's rows */
+    int32_t iters_per_launch, iter_cap;    /* as gcc_svc_args, per problem */
+    double eps;
+    int32_t *unfinished;                   /* device int32[1] */
+    int32_t *search_status;                /* device int32[1], OR-ed, zeroed by the caller */
+    int32_t *correct;                      /* device [folds, candidates, inner] out (gcc_svc_search_score zeroes it first) */
+    int32_t *search_iters;                 /* device [folds, inner, pairs, candidates] out or NULL, as search_rho */
+    double *search_rho;
+    int32_t *search_problem_rows, *search_first_rows;   /* device [folds, inner, pairs] out or NULL */
+    int32_t *search_rows;                  /* device [folds * inner * pairs, max_inner_rows] out or NULL */
+    double *search_alpha;                  /* device [folds * inner * pairs * candidates, max_inner_rows] out or NULL */
+    int32_t *pred;                         /* the refit's outputs, as gcc_svc_args: [N] */
+    double *decision;
+    int32_t *iters;
+    double *rho, *obj;
+    int32_t *n_free, *n_bounded, *problem_rows, *first_rows, *rows_out;
+    double *alpha_out;
+} gcc_svc_search_args;
+/* bytes of workspace: N * N * 4 + O(folds * pairs * max_rows + folds * inner * pairs * candidates * max_inner_rows); negative on a
+ * size out of range, and gcc_last_error() names the limit */
+int64_t gcc_svc_search_workspace_bytes(int32_t N, int32_t D, int32_t classes, int32_t folds, int32_t inner, int32_t candidates,
+                                       int32_t max_rows, int32_t max_inner_rows);
+/* as the gcc_svc_* calls: rc < 0 and nothing launched on a size out of range, a NULL member or a short workspace; no host
+ * synchronisation */
+int32_t gcc_svc_search_setup(const gcc_svc_search_args *a, void *workspace, int64_t workspace_bytes, int32_t *status, void *stream);
+int32_t gcc_svc_search_solve(const gcc_svc_search_args *a, void *workspace, int64_t workspace_bytes, int32_t *status, void *stream);
+int32_t gcc_svc_search_score(const gcc_svc_search_args *a, void *workspace, int64_t workspace_bytes, int32_t *status, void *stream);
+int32_t gcc_svc_search_refit(const gcc_svc_search_args *a, void *workspace, int64_t workspace_bytes, int32_t *status, void *stream);
+int32_t gcc_svc_search_predict(const gcc_svc_search_args *a, void *workspace, int64_t workspace_bytes, int32_t *status, void *stream);
+
 /* ------------------------------- logistic regression on frozen embeddings ---
  * gcc/tasks/node_classification.py:53-101 of the reference: StratifiedKFold, then one-vs-rest LogisticRegression(C=1000) per fold
  * over the columns of an indicator matrix y [N, classes], and per held-out row the k classes of highest probability, k = the
