@@ -362,6 +362,36 @@ class GccGraphwaveArgs(ctypes.Structure):    # gcc_graphwave_args: GraphWave nod
     ]
 
 
+GRAPH_BUILD_WAVE_ROW = 64                    # the row classes of gcc_graph_build and its scan tile (csrc/graph_build.hip)
+GRAPH_BUILD_LDS_ROW = 2048
+GRAPH_BUILD_SCAN_TILE = 1024
+STATUS_GRAPH_BUILD_BAD_ID = 1                # gcc_graph_build's own status word
+STATUS_GRAPH_CHECK_SPAN = 1                  # gcc_graph_check's own status word
+STATUS_GRAPH_CHECK_ZERO_DEGREE = 2
+STATUS_GRAPH_CHECK_RANGE = 4
+STATUS_GRAPH_CHECK_UNSORTED = 8
+STATUS_GRAPH_CHECK_SELF_LOOP = 16
+STATUS_GRAPH_CHECK_DUPLICATE = 32
+STATUS_GRAPH_CHECK_ASYMMETRIC = 64
+
+
+class GccGraphBuildArgs(ctypes.Structure):   # gcc_graph_build_args: edge lines -> the contract CSR (csrc/graph_build.hip)
+    _fields_ = [
+        ("pairs", _VP),
+        ("n", ctypes.c_int64), ("m", ctypes.c_int64),
+        ("row_ptr", _VP), ("col_idx", _VP), ("node_map", _VP), ("counts", _VP),
+    ]
+
+
+class GccGraphCheckArgs(ctypes.Structure):   # gcc_graph_check_args: the contract check on the device (csrc/graph_build.hip)
+    _fields_ = [
+        ("row_ptr", _VP), ("col_idx", _VP),
+        ("n", ctypes.c_int64), ("nnz", ctypes.c_int64),
+        ("multigraph", ctypes.c_int32), ("reserved", ctypes.c_int32),
+        ("maxima", _VP),
+    ]
+
+
 CLS_HEAD_MAX_CLASSES = 64
 CLS_HEAD_MAX_DIM = 256
 
@@ -561,6 +591,11 @@ SIGNATURES = {
                                             ctypes.c_void_p]),
     "gcc_graphwave_embed": (ctypes.c_int32, [ctypes.POINTER(GccGraphwaveArgs), ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p,
                                              ctypes.c_void_p]),
+    "gcc_graph_build_workspace_bytes": (ctypes.c_int64, [ctypes.c_int64, ctypes.c_int64]),
+    "gcc_graph_build": (ctypes.c_int32, [ctypes.POINTER(GccGraphBuildArgs), ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p,
+                                         ctypes.c_void_p]),
+    "gcc_graph_check": (ctypes.c_int32, [ctypes.POINTER(GccGraphCheckArgs), ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p,
+                                         ctypes.c_void_p]),
 }
 # symbols declared in the header but not built yet are listed here while the build is in progress
 PENDING = set()

@@ -95,7 +95,8 @@ class DeviceGraph:
     def __init__(self, row_ptr: np.ndarray, col_idx: np.ndarray, rw_hops: int = 256,
                  restart_prob: float = 0.8, device="cuda", validate: bool = True, ltab: np.ndarray = None,
                  shard_off=None, trusted: bool = False, hub_table: bool = True, multigraph: bool = False):
-        """``validate``: check the input contract (x2dgl.py:39-62) on the host before the upload.  ``trusted``: the caller
+        """``validate``: check the input contract (x2dgl.py:39-62) on the host before the upload; ``"device"``: upload first and
+        check there (gcc_graph_check: the same violations, the same messages, no SciPy matrices).  ``trusted``: the caller
         vouches for the contract without the check (graphs of gcc_amd.graphgen, whose generator builds to it).  With
         neither, the graph carries no GCC_GRAPH_CONTRACT_CHECKED bit and the induction scans every member row (the hub-row
         short cut of gcc_sample_params.hub_degree is exact on a symmetric, sorted, duplicate- and loop-free parent only).
@@ -107,7 +108,10 @@ class DeviceGraph:
 
         row_ptr = np.ascontiguousarray(row_ptr, dtype=np.int32)
         col_idx = np.ascontiguousarray(col_idx, dtype=np.int32)
-        if validate:
+        on_device = isinstance(validate, str)
+        if on_device and validate != "device":
+            raise ValueError(f"validate {validate!r}: True (the host check), False or \"device\"")
+        if validate and not on_device:
             (check_multigraph_contract if multigraph else check_contract)(row_ptr, col_idx)
         self.multigraph = bool(multigraph)
         self.contract_checked = bool(validate or trusted) and not self.multigraph
@@ -139,6 +143,10 @@ class DeviceGraph:
         self.lmax = int(ltab.max())
         self.row_ptr = torch.from_numpy(row_ptr).to(self.device)
         self.col_idx = torch.from_numpy(col_idx).to(self.device)
+        if on_device:                           # the same contract, checked where the graph now lives (gcc_graph_check)
+            from .graph_build import GraphBuildEngine
+
+            GraphBuildEngine(device=self.device).validate(self.row_ptr, self.col_idx, multigraph=self.multigraph)
         # worker shards (LoadBalanceGraphDataset): node ranges whose seeds are drawn separately, batch by batch
         self.num_shards = 0
         self.shard_off = None

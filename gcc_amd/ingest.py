@@ -216,6 +216,39 @@ def read_tudataset(folder: str, name: str):
     return dict(graphs=graphs, graph_labels=np.searchsorted(values, labels).astype(np.int64), num_labels=len(values))
 
 
+def read_lscc(path: str):
+    """The text layout of the pre-training networks as ``yuxiao_kdd17_graph_to_dgl`` reads it (x2dgl.py:30-47): a ``<word> n``
+    line, ``n`` vertex lines (zero-based index and raw id: skipped), a ``<word> m`` line, then ``m`` lines ``u v w`` (``w`` is
+    read and dropped, as there).  -> (n, pairs int32 [m, 2]): the lines as they stand, self loops and repeats included -- what
+    ``gcc_amd.graph_build`` takes.  The file is parsed as one array: no Python loop per line."""
+    with open(path, "rb") as f:
+        data = f.read()
+    ends = np.flatnonzero(np.frombuffer(data, dtype=np.uint8) == 10)          # the line ends
+
+    def count_of(line, what):
+        words = line.split()
+        if len(words) < 2 or not words[1].lstrip(b"-").isdigit():
+            raise ValueError(f"{path}: expected a `<word> {what}` line, found {line[:40]!r}")
+        return int(words[1])
+
+    if len(ends) < 1:
+        raise ValueError(f"{path}: truncated: no `<word> n` line")
+    n = count_of(data[:ends[0]], "n")
+    if n < 0 or len(ends) < n + 2:
+        raise ValueError(f"{path}: truncated: {n} vertex lines and a `<word> m` line announced, the file has {len(ends)} lines")
+    m = count_of(data[ends[n] + 1:ends[n + 1]], "m")
+    try:
+        body = np.array(data[ends[n + 1] + 1:].split(), dtype=np.int64)
+    except ValueError as err:
+        raise ValueError(f"{path}: an edge line holds something other than integers ({err})") from None
+    if m < 0 or body.size < 3 * m:
+        raise ValueError(f"{path}: truncated: {m} edge lines `u v w` announced, {body.size // 3} complete ones found")
+    pairs = body[:3 * m].reshape(m, 3)[:, :2]
+    if m and (pairs.min() < -2 ** 31 or pairs.max() >= 2 ** 31):
+        raise ValueError(f"{path}: node ids must fit int32")
+    return n, np.ascontiguousarray(pairs, dtype=np.int32)
+
+
 # ---------------------------------------------------------------------------------------------------------------
 # DGL graph files (``data/small.bin``): what ``dgl.data.utils.save_graphs`` / ``load_graphs`` / ``load_labels`` of
 # dgl 0.4.x write and read -- graph_dataset.py:26-29 (worker_init_fn), graph_dataset.py:58-60 (graph_sizes label),

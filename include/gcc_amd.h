@@ -1153,6 +1153,54 @@ int64_t gcc_graphwave_workspace_bytes(int64_t n_rows, int64_t nnz, int32_t d, in
 int32_t gcc_graphwave_heat(const gcc_graphwave_args *a, void *workspace, int64_t workspace_bytes, int32_t *status, void *stream);
 int32_t gcc_graphwave_embed(const gcc_graphwave_args *a, void *workspace, int64_t workspace_bytes, int32_t *status, void *stream);
 
+/* ---- Raw edge lines -> the sampler's contract CSR, and the contract check on the device (csrc/graph_build.hip).  The rule is the
+ * reference converter's (gcc/utils/x2dgl.py, yuxiao_kdd17_graph_to_dgl): the lines u == v are dropped, both directions of the rest
+ * inserted, one entry kept per non-zero, the nodes without an entry removed, the survivors relabelled in ascending old-id order,
+ * rows sorted ascending.  Integer arithmetic and integer atomics only: the output depends on the set of lines alone, so any order
+ * of the lines and any two calls give the same bits.
+ * ROW CLASSES: a row of up to GCC_GRAPH_BUILD_WAVE_ROW slots (before the repeats are removed) is sorted by one wave in registers,
+ * one of up to GCC_GRAPH_BUILD_LDS_ROW by one workgroup in LDS, a longer one in chunks of GCC_GRAPH_BUILD_LDS_ROW that are merged
+ * in the workspace.  The scans work on tiles of GCC_GRAPH_BUILD_SCAN_TILE words. */
+#define GCC_GRAPH_BUILD_WAVE_ROW 64
+#define GCC_GRAPH_BUILD_LDS_ROW 2048
+#define GCC_GRAPH_BUILD_SCAN_TILE 1024
+#define GCC_STATUS_GRAPH_BUILD_BAD_ID 1  /* a line names an id outside [0, n): the line was ignored */
+typedef struct gcc_graph_build_args {
+    const int32_t *pairs;                  /* device [m][2]: the lines' two ids, either order, repeats and u == v allowed */
+    int64_t n, m;                          /* declared nodes 1..2^31 - 1; lines, 2 m < 2^31 */
+    int32_t *row_ptr, *col_idx;            /* out, device: capacities [n + 1] and [2 m]; counts[0] + 1 and counts[1] words are written */
+    int32_t *node_map;                     /* out, device [n] or NULL: old id -> new id, -1 for a removed node */
+    int64_t *counts;                       /* out, device [6]: nodes kept, entries written, u == v lines dropped, repeated directed
+                                            * slots dropped, nodes removed for having no entry, the longest row */
+} gcc_graph_build_args;
+/* bytes of workspace: six words per node, the scans' tile sums, the two row lists and one copy of the 2 m slots (two when a row
+ * can exceed GCC_GRAPH_BUILD_LDS_ROW).  Negative on a size out of range, gcc_last_error() names it. */
+int64_t gcc_graph_build_workspace_bytes(int64_t n, int64_t m);
+/* status: device int32[1], OR-ed, zeroed by the caller.  A size out of range, a NULL member the call needs and a short workspace
+ * return rc < 0, name the member in gcc_last_error() and launch nothing.  No host synchronisation: the caller reads counts and
+ * status once and slices row_ptr / col_idx. */
+int32_t gcc_graph_build(const gcc_graph_build_args *a, void *workspace, int64_t workspace_bytes, int32_t *status, void *stream);
+
+/* the contract a parent graph must obey, one bit per violation (gcc_amd.graphgen.check_contract / check_multigraph_contract) */
+#define GCC_STATUS_GRAPH_CHECK_SPAN 1          /* row_ptr does not run from 0 to nnz within [0, nnz] */
+#define GCC_STATUS_GRAPH_CHECK_ZERO_DEGREE 2   /* a row without an entry */
+#define GCC_STATUS_GRAPH_CHECK_RANGE 4         /* a column outside [0, n) */
+#define GCC_STATUS_GRAPH_CHECK_UNSORTED 8      /* a row that descends */
+#define GCC_STATUS_GRAPH_CHECK_SELF_LOOP 16
+#define GCC_STATUS_GRAPH_CHECK_DUPLICATE 32    /* a repeated entry (multigraph == 0 only) */
+#define GCC_STATUS_GRAPH_CHECK_ASYMMETRIC 64   /* an entry without its reverse; multigraph: unequal copy counts in the two directions */
+typedef struct gcc_graph_check_args {
+    const int32_t *row_ptr, *col_idx;      /* device [n + 1], [nnz] */
+    int64_t n, nnz;
+    int32_t multigraph, reserved;          /* 1: repeated entries are parallel edges */
+    int32_t *maxima;                       /* out, device int32[2]: the longest row, the most copies of one entry in a row */
+} gcc_graph_check_args;
+/* Writes status and maxima, nothing else; the workspace is not used and may be NULL.  Three steps, each run only on what the one
+ * before it found sound (the status word must come in as 0): row_ptr (SPAN, ZERO_DEGREE, maxima[0]); every entry in its row, found
+ * by a binary search in a row_ptr that climbs (RANGE, UNSORTED, SELF_LOOP, DUPLICATE); the reverse entries, found by a binary
+ * search in sorted rows (ASYMMETRIC, maxima[1]).  The lowest bit set is the violation gcc_amd.graphgen.check_contract names. */
+int32_t gcc_graph_check(const gcc_graph_check_args *a, void *workspace, int64_t workspace_bytes, int32_t *status, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
