@@ -437,6 +437,26 @@ class GccGatPass(ctypes.Structure):
 
 
 # name -> (restype, argtypes); the single source of truth for the symbol test
+GRAPH_TABLES_SCAN_TILE = 2048                # the tiles of gcc_graph_tables (nodes) and gcc_graph_tables_hub_adj (entries)
+GRAPH_TABLES_ENTRY_TILE = 1024
+GRAPH_TABLES_HUB_DEGREE = 512
+GRAPH_TABLES_SUMMARY_WORDS = 8
+STATUS_GRAPH_TABLES_EMPTY_SHARD = 1
+
+
+class GccGraphTablesArgs(ctypes.Structure):  # gcc_graph_tables_args: the sampler's tables on the device (csrc/graph_tables.hip)
+    _fields_ = [
+        ("row_ptr", _VP), ("col_idx", _VP),
+        ("n", ctypes.c_int64), ("nnz", ctypes.c_int64),
+        ("shard_off", _VP),
+        ("num_shards", ctypes.c_int32), ("hub_degree", ctypes.c_int32),
+        ("max_hub_bytes", ctypes.c_int64),
+        ("grid", ctypes.c_int32), ("reserved", ctypes.c_int32),
+        ("summary", _VP), ("seed_cdf", _VP), ("hub_index", _VP), ("hub_adj", _VP),
+        ("num_hubs", ctypes.c_int32), ("hub_words", ctypes.c_int32),
+    ]
+
+
 SIGNATURES = {
     "gcc_abi_version": (ctypes.c_int32, []),
     "gcc_last_error": (ctypes.c_char_p, []),
@@ -596,6 +616,11 @@ SIGNATURES = {
                                          ctypes.c_void_p]),
     "gcc_graph_check": (ctypes.c_int32, [ctypes.POINTER(GccGraphCheckArgs), ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p,
                                          ctypes.c_void_p]),
+    "gcc_graph_tables_workspace_bytes": (ctypes.c_int64, [ctypes.c_int64, ctypes.c_int32]),
+    "gcc_graph_tables": (ctypes.c_int32, [ctypes.POINTER(GccGraphTablesArgs), ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p,
+                                          ctypes.c_void_p]),
+    "gcc_graph_tables_hub_adj": (ctypes.c_int32, [ctypes.POINTER(GccGraphTablesArgs), ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p,
+                                                  ctypes.c_void_p]),
 }
 # symbols declared in the header but not built yet are listed here while the build is in progress
 PENDING = set()

@@ -1,5 +1,5 @@
 """What the engines of the downstream tasks and of the corpus build share (gcc_amd.logreg, svc, simsearch, prone, graphwave,
-graph_build): the library and pointer
+graph_build, graph_tables): the library and pointer
 seam, the reused workspace, the checks on an embedding table, the C-ABI call and the status word.  A new task's engine derives
 from CabiEngine; its C side starts from gcc_amd/csrc/task_common.h."""
 from __future__ import annotations

@@ -1,5 +1,5 @@
 // gcc_amd/csrc/task_common.h -- the kit the downstream-task files share (simsearch.hip, svc.hip, logreg.hip, prone.hip,
-// graphwave.hip; graph_build.hip takes the host scaffold): THE implementation of the fixed-order row sum of include/gcc_amd.h ("ORDER OF A ROW'S SUM"), the CSR guards, the
+// graphwave.hip; graph_build.hip and graph_tables.hip take the host scaffold): THE implementation of the fixed-order row sum of include/gcc_amd.h ("ORDER OF A ROW'S SUM"), the CSR guards, the
 // workgroup sum, the float64 Gram tile on v_mfma_f64_16x16x4_f64, and the host scaffold of an entry point (workspace carving, the
 // NULL / workspace checks with their messages, the launch check).  Everything is file-local: every source file is its own
 // translation unit, in the product and in the emulator build alike.

@@ -358,7 +358,10 @@ class LoadBalanceGraphDataset:
     ``graph`` overrides it: a :class:`DeviceGraph`, or ``(row_ptr, col_idx)``
     arrays, or a list of such pairs -- a multi-graph corpus: laid out in HBM shard
     by shard (``jobs``), batch i draws its seeds from worker shard i % num_workers
-    as the reference's IterableDataset workers do.
+    as the reference's IterableDataset workers do.  The pairs may be int32 DEVICE
+    tensors (``gcc_amd.corpus.build_corpus(keep_on_device=True)``): the same
+    ``jobs``, ``graph_order`` and shards, the union made where the graphs lie and
+    checked there (``DeviceGraph.from_device``); nothing is downloaded.
     """
 
     def __init__(self, rw_hops=64, restart_prob=0.8, positional_embedding_size=32,
@@ -413,10 +416,15 @@ class LoadBalanceGraphDataset:
             # would crash the reference (np.random.choice over nothing); they are left out of the rotation here.
             live = [j for j in jobs if j]
             self.graph_order = [i for j in live for i in j]
-            rp, ci = _disjoint_union([graphs[i] for i in self.graph_order])
             shard_off = np.cumsum([0] + [sum(len(graphs[i][0]) - 1 for i in j) for j in live])
-            self.graph = DeviceGraph(rp, ci, rw_hops=rw_hops, restart_prob=restart_prob, device=device,
-                                     shard_off=shard_off if len(live) > 1 else None)
+            if _is_device_tensor(graphs[0][0]):
+                rp, ci = _disjoint_union_device([graphs[i] for i in self.graph_order])
+                self.graph = DeviceGraph.from_device(rp, ci, rw_hops=rw_hops, restart_prob=restart_prob, validate="device",
+                                                     shard_off=shard_off if len(live) > 1 else None)
+            else:
+                rp, ci = _disjoint_union([graphs[i] for i in self.graph_order])
+                self.graph = DeviceGraph(rp, ci, rw_hops=rw_hops, restart_prob=restart_prob, device=device,
+                                         shard_off=shard_off if len(live) > 1 else None)
         self.total = self.num_samples * num_workers
         self.batch_size = batch_size
         self.run_seed = run_seed
@@ -457,6 +465,31 @@ def _disjoint_union(graphs):
         off += len(rp) - 1
         eoff += int(rp[-1])
     return np.concatenate(rps).astype(np.int32), np.concatenate(cis).astype(np.int32)
+
+
+def _is_device_tensor(x):
+    import torch
+
+    return isinstance(x, torch.Tensor) and x.is_cuda
+
+
+def _disjoint_union_device(graphs):
+    """``_disjoint_union`` of int32 device pairs with torch ops where they lie.  No host read: a graph's entries are counted by
+    ``col_idx``'s length (row_ptr's last word on a CSR that obeys the contract, which the caller checks next)."""
+    import torch
+
+    nodes, entries = sum(len(rp) - 1 for rp, _ in graphs), sum(int(ci.numel()) for _, ci in graphs)
+    if nodes >= 2 ** 31 or entries >= 2 ** 31:
+        raise ValueError(f"the corpus has {nodes} nodes and {entries} entries: both must fit int32")
+    rps, cis, off, eoff = [torch.zeros(1, dtype=torch.int32, device=graphs[0][0].device)], [], 0, 0
+    for rp, ci in graphs:
+        if rp.dtype != torch.int32 or ci.dtype != torch.int32:
+            raise TypeError("device graphs are (row_ptr, col_idx) int32 tensors")
+        rps.append(rp[1:] + eoff)
+        cis.append(ci + off)
+        off += len(rp) - 1
+        eoff += int(ci.numel())
+    return torch.cat(rps), torch.cat(cis)
 
 
 def _load_graph_file(path):

@@ -19,34 +19,9 @@ import os
 import numpy as np
 
 from . import ingest
-from .graph_build import BUILD_STATUS_BITS, build_csr_numpy
+from .corpus import REFERENCE_FILES, build_corpus, build_graph  # noqa: F401  (the names this module has always had)
 
 logger = logging.getLogger(__name__)
-
-# x2dgl.py:88-97
-REFERENCE_FILES = ("ca-DBLP-NetRep.txt.lpm.lscc", "ca-DBLP-SNAP.txtu.lpm.lscc", "ca-IMDB-NetRep.txt.lpm.lscc",
-                   "soc-Academia-NetRep.txt.lpm.lscc", "soc-LiveJournal1-d-SNAP.txtu.lpm.lscc", "soc-Facebook1-NetRep.txt.lpm.lscc")
-
-
-def build_graph(path, device="cuda:0", engine=None):
-    """one file -> dict(name, row_ptr, col_idx (numpy int32), counts): read, built, and the reference's line logged"""
-    n, pairs = ingest.read_lscc(path)
-    logger.info("processing %s", path)
-    logger.info("raw file has %d nodes and %d edges", n, len(pairs))
-    if engine is None and str(device) == "cpu":
-        out = build_csr_numpy(pairs, n)
-    else:
-        if engine is None:
-            from .graph_build import GraphBuildEngine
-
-            engine = GraphBuildEngine(device=device)
-        out = {k: (v.cpu().numpy() if hasattr(v, "cpu") else v) for k, v in engine.build(pairs, n).items()}
-    if int(out["status"][0]):
-        raise SystemExit(f"{path}: " + "; ".join(text for bit, text in BUILD_STATUS_BITS.items() if int(out["status"][0]) & bit))
-    counts = [int(c) for c in out["counts"]]
-    # (the reference counts the two slots of a self-loop line: x2dgl.py:67)
-    logger.info("%d nodes, %d edges, %d self-loop(s) removed, %d zero-degree node(s) removed", counts[0], counts[1], 2 * counts[2], counts[4])
-    return dict(name=os.path.basename(path), row_ptr=np.asarray(out["row_ptr"]), col_idx=np.asarray(out["col_idx"]), counts=counts)
 
 
 def main(argv=None, engine=None):
@@ -60,20 +35,7 @@ def main(argv=None, engine=None):
     parser.add_argument("--save-npz", type=str, default=None, help="folder for one row_ptr / col_idx npz per graph")
     args = parser.parse_args(argv)
     logging.basicConfig(format="%(asctime)s - %(levelname)s - %(name)s - %(message)s", datefmt="%m/%d/%Y %H:%M:%S", level=logging.INFO)
-    if args.files is not None:
-        names = [x for x in args.files.split(",") if x]
-        missing = [x for x in names if not os.path.isfile(os.path.join(args.graph_dir, x))]
-        if missing:
-            raise SystemExit(f"--files: not in {args.graph_dir}: {', '.join(missing)}")
-    else:
-        names = [x for x in REFERENCE_FILES if os.path.isfile(os.path.join(args.graph_dir, x))]
-    if not names:
-        raise SystemExit(f"no graph file to convert in {args.graph_dir} (the reference's names: {', '.join(REFERENCE_FILES)}; others with --files)")
-    graphs = [build_graph(os.path.join(args.graph_dir, x), args.device, engine) for x in names]
-    empty = [g["name"] for g in graphs if g["counts"][0] == 0]
-    if empty:
-        raise SystemExit(f"no edge is left in {', '.join(empty)}: a graph without nodes cannot be sampled")
-    graphs.sort(key=lambda g: (-g["counts"][0], g["name"]))
+    graphs = build_corpus(args.graph_dir, args.files.split(",") if args.files is not None else None, args.device, engine)
     sizes = np.array([g["counts"][0] for g in graphs], dtype=np.int64)
     for i, g in enumerate(graphs):
         print(i, f"{g['name']}: {g['counts'][0]} nodes, {g['counts'][1]} edges", int(sizes[i]))

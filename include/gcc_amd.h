@@ -1201,6 +1201,44 @@ typedef struct gcc_graph_check_args {
  * search in sorted rows (ASYMMETRIC, maxima[1]).  The lowest bit set is the violation gcc_amd.graphgen.check_contract names. */
 int32_t gcc_graph_check(const gcc_graph_check_args *a, void *workspace, int64_t workspace_bytes, int32_t *status, void *stream);
 
+/* ---- The sampler's tables from a CSR that is already in HBM (csrc/graph_tables.hip): what gcc_amd.graph builds on the host at
+ * upload -- the summary a DeviceGraph sizes itself with, the seed cdf (deg^0.75 per worker shard) and the hub index / hub-hub
+ * bitmap of gcc_graph.  Two calls, one host read between them: gcc_graph_tables fills summary, seed_cdf and hub_index; the caller
+ * reads summary (GCC_GRAPH_TABLES_SUMMARY_WORDS int64), sizes hub_adj from summary[3] and calls gcc_graph_tables_hub_adj.
+ * The integer outputs are exact.  THE CDF: float64 sums in an order the tile grid alone fixes (tiles of
+ * GCC_GRAPH_TABLES_SCAN_TILE nodes that never straddle a shard; any grid size and any two calls give the same bits), carried
+ * forward so that the cdf never descends within a shard, ends in exactly 1.0 and stays within (n_s + 64) * 2^-53 of the exact
+ * cdf of a shard of n_s nodes.  The bitmap is built from tiles of GCC_GRAPH_TABLES_ENTRY_TILE entries. */
+#define GCC_GRAPH_TABLES_SCAN_TILE 2048
+#define GCC_GRAPH_TABLES_ENTRY_TILE 1024
+#define GCC_GRAPH_TABLES_HUB_DEGREE 512      /* hub_degree == 0 */
+#define GCC_GRAPH_TABLES_SUMMARY_WORDS 8
+#define GCC_STATUS_GRAPH_TABLES_EMPTY_SHARD 1 /* a shard's total deg^0.75 weight is zero or not finite: its cdf is all 1.0 */
+typedef struct gcc_graph_tables_args {
+    const int32_t *row_ptr, *col_idx;      /* device [n + 1], [nnz] (col_idx: gcc_graph_tables_hub_adj only) */
+    int64_t n, nnz;                        /* 1 <= n, both within int32 */
+    const int64_t *shard_off;              /* HOST [num_shards + 1]: increasing from 0 to n; may be NULL when num_shards <= 1 */
+    int32_t num_shards;                    /* <= 1: one shard covers all nodes */
+    int32_t hub_degree;                    /* rows of at least this many entries are hubs; 0: GCC_GRAPH_TABLES_HUB_DEGREE */
+    int64_t max_hub_bytes;                 /* gcc_graph_tables_hub_adj refuses a larger bitmap; 0: 1 GiB */
+    int32_t grid, reserved;                /* workgroups of the tile kernels; 0: sized from the input (the outputs do not depend on it) */
+    int64_t *summary;                      /* out, device [GCC_GRAPH_TABLES_SUMMARY_WORDS]: the longest row, sum d, sum d^2, hubs, the
+                                            * status bits this call set, num_shards - (the lowest shard without weight), 0, 0 */
+    double *seed_cdf;                      /* out, device [n] */
+    int32_t *hub_index;                    /* out, device [n], or NULL (gcc_graph_tables: not built); in for gcc_graph_tables_hub_adj */
+    uint32_t *hub_adj;                     /* out of gcc_graph_tables_hub_adj, device [num_hubs][hub_words] */
+    int32_t num_hubs, hub_words;           /* gcc_graph_tables_hub_adj: summary[3] and (num_hubs + 31) / 32 */
+} gcc_graph_tables_args;
+/* bytes of workspace of gcc_graph_tables: three words per tile and the shard table.  Negative on a size out of range. */
+int64_t gcc_graph_tables_workspace_bytes(int64_t n, int32_t num_shards);
+/* status: device int32[1], OR-ed, zeroed by the caller.  A size out of range, a NULL member the call needs, a shard_off that does
+ * not run from 0 to n in increasing order and a short workspace return rc < 0, name what is wrong in gcc_last_error() and launch
+ * nothing.  No host synchronisation (shard_off is copied before the call returns). */
+int32_t gcc_graph_tables(const gcc_graph_tables_args *a, void *workspace, int64_t workspace_bytes, int32_t *status, void *stream);
+/* hub_adj of the hubs hub_index numbers: zeroed, then one bit per entry of a hub's row that names a hub.  The workspace is not
+ * used and may be NULL.  Refuses num_hubs < 1, a hub_words that does not fit and a bitmap above max_hub_bytes. */
+int32_t gcc_graph_tables_hub_adj(const gcc_graph_tables_args *a, void *workspace, int64_t workspace_bytes, int32_t *status, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -11,7 +11,8 @@ dataset (gcc_amd/finetune.py); without --finetune only the "dgl" corpus is serve
 
 The pre-training corpus ./data/small.bin (a DGL graph file, train.py:552) is read
 without DGL (gcc_amd/ingest.py).  Extra flags (not in the reference): --dgl-file,
---graph-npz / --synthetic choose another pre-training graph; --edgelist / --nodelabel,
+--graph-npz / --synthetic choose another pre-training graph, --graph-dir [--graph-files]
+builds it on the device from raw .lscc edge files (gcc_amd/corpus.py); --edgelist / --nodelabel,
 --tudataset, --graphs-npz and --edge-multiplicity name the labelled data of --finetune
 (as generate.py's flags do; the dataset files are not bundled).
 Multi-GPU: launch with torch.distributed.run; the seed batch is sharded by rank,
@@ -19,6 +20,7 @@ keys are all-gathered before the enqueue, gradients are all-reduced (RCCL).
 """
 import argparse
 import os
+import sys
 import time
 
 os.environ.setdefault("GPU_MAX_HW_QUEUES", "4")    # few hardware queues: see gcc_amd.train_step.BatchProducer
@@ -121,6 +123,8 @@ def parse_option(argv=None):
     parser.add_argument("--dgl-file", type=str, default="./data/small.bin", help="DGL graph file of the pre-training corpus (train.py:552 hard-codes this path)")
     parser.add_argument("--graph-npz", type=str, default=None, help="npz with row_ptr/col_idx (instead of data/small.bin)")
     parser.add_argument("--synthetic", type=str, default=None, help="V,E of a synthetic power-law graph, e.g. 1000000,10000000")
+    parser.add_argument("--graph-dir", type=str, default=None, help="folder of raw .lscc edge files: the corpus is built, checked and laid out on the device, no .bin is written (instead of --dgl-file)")
+    parser.add_argument("--graph-files", type=str, default=None, help="comma-separated file names inside --graph-dir (default: the reference's six networks)")
     parser.add_argument("--nce-dtype", type=str, default="f32", choices=["f32", "bf16"], help="operands of the MoCo head: f32 = exact (1e-3 parity with the reference), bf16 = matrix-core throughput mode")
     parser.add_argument("--encoder-dtype", type=str, default="f32", choices=["f32", "bf16"], help="operands of the GIN layers' Linears above --hidden-size 64 (forward, data and weight gradients): f32 = exact, bf16 = matrix-core throughput mode")
     parser.add_argument("--max-steps", type=int, default=0, help="stop after this many steps (0 = full schedule)")
@@ -136,6 +140,12 @@ def parse_option(argv=None):
     # fmt: on
 
     opt = parser.parse_args(argv)
+    if opt.graph_dir is not None:
+        given = sys.argv[1:] if argv is None else list(argv)
+        if opt.graph_npz or opt.synthetic or any(a == "--dgl-file" or a.startswith("--dgl-file=") for a in given):
+            parser.error("--graph-dir builds the corpus from raw edge files: not together with --dgl-file, --graph-npz or --synthetic")
+    elif opt.graph_files is not None:
+        parser.error("--graph-files names files inside --graph-dir")
 
     iterations = opt.lr_decay_epochs.split(",")
     opt.lr_decay_epochs = list([])
@@ -178,9 +188,14 @@ def _summary_writer(folder):
         return _NullWriter()
 
 
-def _load_graph(args):
+def _load_graph(args, device=None):
     from gcc_amd.graphgen import powerlaw_graph
 
+    if getattr(args, "graph_dir", None):                  # raw edge files -> device CSRs; the dataset checks their union there
+        from gcc_amd.corpus import build_corpus
+
+        files = args.graph_files.split(",") if args.graph_files else None
+        return [(g["row_ptr"], g["col_idx"]) for g in build_corpus(args.graph_dir, files, device=device, keep_on_device=True)]
     if args.graph_npz:
         z = np.load(args.graph_npz)
         return z["row_ptr"], z["col_idx"]
@@ -312,7 +327,7 @@ def main(args):
             checkpoint = torch.load(args.resume, map_location="cpu", weights_only=False)
             pretrain_args = checkpoint["opt"]
             for name in ("fold_idx", "gpu", "finetune", "resume", "cv", "dataset", "epochs", "num_workers",
-                         "batch_size", "dgl_file", "graph_npz", "synthetic", "max_steps", "producer_lanes", "producer_chunk"):
+                         "batch_size", "dgl_file", "graph_dir", "graph_files", "graph_npz", "synthetic", "max_steps", "producer_lanes", "producer_chunk"):
                 setattr(pretrain_args, name, getattr(args, name))
             args = pretrain_args
         else:
@@ -332,7 +347,7 @@ def main(args):
         rw_hops=args.rw_hops, restart_prob=args.restart_prob,
         positional_embedding_size=args.positional_embedding_size, num_workers=args.num_workers,
         num_samples=args.num_samples, dgl_graphs_file=args.dgl_file, num_copies=args.num_copies,
-        graph=_load_graph(args), batch_size=args.batch_size, run_seed=args.seed, device=dev)
+        graph=_load_graph(args, dev), batch_size=args.batch_size, run_seed=args.seed, device=dev)
 
     model, model_ema = [
         GraphEncoder(                                      # train.py:601-620
