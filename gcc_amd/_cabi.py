@@ -457,6 +457,34 @@ class GccGraphTablesArgs(ctypes.Structure):  # gcc_graph_tables_args: the sample
     ]
 
 
+TEXT_TILE_BYTES = 4096                       # a tile of gcc_text_ints / gcc_text_line_ends and the tiles of a scan pass (csrc/text_ingest.hip)
+TEXT_SCAN_TILES = 1024
+TEXT_MAX_QUERIES = 16
+STATUS_TEXT_NOT_INTEGER = 1                  # gcc_text_ints' own status word
+STATUS_TEXT_INT32_RANGE = 2
+STATUS_TEXT_SHORT = 4
+
+
+class GccTextLineEndsArgs(ctypes.Structure):  # gcc_text_line_ends_args: the newlines that end given lines (csrc/text_ingest.hip)
+    _fields_ = [
+        ("text", _VP),
+        ("nbytes", ctypes.c_int64), ("capacity", ctypes.c_int64),
+        ("lines", ctypes.POINTER(ctypes.c_int64)),
+        ("num_lines", ctypes.c_int32), ("reserved", ctypes.c_int32),
+        ("ends", _VP),
+    ]
+
+
+class GccTextIntsArgs(ctypes.Structure):     # gcc_text_ints_args: tokens of text -> int32 records (csrc/text_ingest.hip)
+    _fields_ = [
+        ("text", _VP),
+        ("nbytes", ctypes.c_int64), ("capacity", ctypes.c_int64),
+        ("first_byte", ctypes.c_int64), ("max_tokens", ctypes.c_int64),
+        ("fields", ctypes.c_int32), ("keep", ctypes.c_int32),
+        ("out", _VP), ("summary", _VP),
+    ]
+
+
 SIGNATURES = {
     "gcc_abi_version": (ctypes.c_int32, []),
     "gcc_last_error": (ctypes.c_char_p, []),
@@ -621,6 +649,12 @@ SIGNATURES = {
                                           ctypes.c_void_p]),
     "gcc_graph_tables_hub_adj": (ctypes.c_int32, [ctypes.POINTER(GccGraphTablesArgs), ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p,
                                                   ctypes.c_void_p]),
+    "gcc_text_line_ends_workspace_bytes": (ctypes.c_int64, [ctypes.c_int64]),
+    "gcc_text_ints_workspace_bytes": (ctypes.c_int64, [ctypes.c_int64]),
+    "gcc_text_line_ends": (ctypes.c_int32, [ctypes.POINTER(GccTextLineEndsArgs), ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p,
+                                            ctypes.c_void_p]),
+    "gcc_text_ints": (ctypes.c_int32, [ctypes.POINTER(GccTextIntsArgs), ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p,
+                                       ctypes.c_void_p]),
 }
 # symbols declared in the header but not built yet are listed here while the build is in progress
 PENDING = set()

@@ -1239,6 +1239,52 @@ int32_t gcc_graph_tables(const gcc_graph_tables_args *a, void *workspace, int64_
  * used and may be NULL.  Refuses num_hubs < 1, a hub_words that does not fit and a bitmap above max_hub_bytes. */
 int32_t gcc_graph_tables_hub_adj(const gcc_graph_tables_args *a, void *workspace, int64_t workspace_bytes, int32_t *status, void *stream);
 
+/* ---- Edge-list text that is already in HBM -> line ends and int32 records (csrc/text_ingest.hip): the first stage of
+ * gcc_amd.ingest.read_lscc on the device.  THE TOKEN RULE is bytes.split()'s: the separators are the six bytes 9, 10, 11, 12, 13
+ * and 32; a token starts at byte i >= first_byte when text[i] is no separator and (i == first_byte or text[i - 1] is one) and runs
+ * to the next separator or the end of the text.  Token r, counted from first_byte, is field r % fields of record r / fields.  A
+ * valid token is at most one '+' or '-' followed by one or more ASCII digits (leading zeros are fine, -0 is 0, an underscore is not
+ * a digit); a token of any length is classified, never wrapped.
+ * THE BUFFER: `text` is aligned to 16 bytes and has a capacity of at least nbytes rounded up to 16 (the kernels load 16 bytes at
+ * a time and never a ragged tail); what the bytes at and above nbytes hold does not matter.
+ * Work is cut into tiles of GCC_TEXT_TILE_BYTES bytes; one workgroup scans the tiles' counts, GCC_TEXT_SCAN_TILES tiles per pass.
+ * Integer min and integer or are the only atomics: any grid and any two calls give the same words. */
+#define GCC_TEXT_TILE_BYTES 4096
+#define GCC_TEXT_SCAN_TILES 1024
+#define GCC_TEXT_MAX_QUERIES 16
+#define GCC_STATUS_TEXT_NOT_INTEGER 1   /* one of the first max_tokens tokens is not an integer: summary[1] */
+#define GCC_STATUS_TEXT_INT32_RANGE 2   /* a kept token's value is outside int32: summary[2] */
+#define GCC_STATUS_TEXT_SHORT 4         /* fewer than max_tokens tokens: summary[0] */
+typedef struct gcc_text_line_ends_args {
+    const uint8_t *text;                   /* device [capacity] */
+    int64_t nbytes, capacity;              /* 1 <= nbytes <= 2^40; capacity >= nbytes rounded up to 16 */
+    const int64_t *lines;                  /* HOST [num_lines]: zero-based line numbers, any order, repeats allowed */
+    int32_t num_lines, reserved;           /* 0..GCC_TEXT_MAX_QUERIES */
+    int64_t *ends;                         /* out, device [num_lines + 1]: the offset of the newline (byte 10) that ends line
+                                            * lines[i], -1 where the text has fewer lines; ends[num_lines]: the newlines of the text */
+} gcc_text_line_ends_args;
+typedef struct gcc_text_ints_args {
+    const uint8_t *text;                   /* device [capacity] */
+    int64_t nbytes, capacity;
+    int64_t first_byte;                    /* 0..nbytes: the bytes below it are not looked at */
+    int64_t max_tokens;                    /* a multiple of fields; max_tokens / fields * keep < 2^31 */
+    int32_t fields, keep;                  /* tokens per record 1..4; the leading fields of a record that are stored, 1..fields */
+    int32_t *out;                          /* out, device [max_tokens / fields][keep]; a kept token that is no integer or outside
+                                            * int32 stores 0; the words of tokens the text does not have are left alone */
+    int64_t *summary;                      /* out, device [4]: tokens in [first_byte, nbytes) (uncapped); the offset of the lowest
+                                            * of the first max_tokens tokens that is not an integer, or -1; the offset of the lowest
+                                            * kept token outside int32, or -1; 0 */
+} gcc_text_ints_args;
+/* bytes of workspace: 24 per tile (a count and an int64 offset for the token starts and for the newlines).  Negative on a size out of range. */
+int64_t gcc_text_line_ends_workspace_bytes(int64_t nbytes);
+int64_t gcc_text_ints_workspace_bytes(int64_t nbytes);
+/* A size out of range, a NULL member the call needs, a capacity below the padded size, a text off its alignment and a short
+ * workspace return rc < 0, name what is wrong in gcc_last_error() and launch nothing.  No host synchronisation (`lines` is copied
+ * before the call returns).  gcc_text_line_ends sets no status bit and accepts a NULL status; gcc_text_ints ORs its bits into
+ * status (device int32[1], zeroed by the caller). */
+int32_t gcc_text_line_ends(const gcc_text_line_ends_args *a, void *workspace, int64_t workspace_bytes, int32_t *status, void *stream);
+int32_t gcc_text_ints(const gcc_text_ints_args *a, void *workspace, int64_t workspace_bytes, int32_t *status, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -125,6 +125,7 @@ def parse_option(argv=None):
     parser.add_argument("--synthetic", type=str, default=None, help="V,E of a synthetic power-law graph, e.g. 1000000,10000000")
     parser.add_argument("--graph-dir", type=str, default=None, help="folder of raw .lscc edge files: the corpus is built, checked and laid out on the device, no .bin is written (instead of --dgl-file)")
     parser.add_argument("--graph-files", type=str, default=None, help="comma-separated file names inside --graph-dir (default: the reference's six networks)")
+    parser.add_argument("--graph-parse", type=str, default="host", choices=["host", "device"], help="--graph-dir: parse the edge files with the host reader, or on the device (gcc_amd.text_ingest: the pairs never visit the host)")
     parser.add_argument("--nce-dtype", type=str, default="f32", choices=["f32", "bf16"], help="operands of the MoCo head: f32 = exact (1e-3 parity with the reference), bf16 = matrix-core throughput mode")
     parser.add_argument("--encoder-dtype", type=str, default="f32", choices=["f32", "bf16"], help="operands of the GIN layers' Linears above --hidden-size 64 (forward, data and weight gradients): f32 = exact, bf16 = matrix-core throughput mode")
     parser.add_argument("--max-steps", type=int, default=0, help="stop after this many steps (0 = full schedule)")
@@ -146,6 +147,8 @@ def parse_option(argv=None):
             parser.error("--graph-dir builds the corpus from raw edge files: not together with --dgl-file, --graph-npz or --synthetic")
     elif opt.graph_files is not None:
         parser.error("--graph-files names files inside --graph-dir")
+    elif opt.graph_parse != "host":
+        parser.error("--graph-parse says where the files of --graph-dir are parsed")
 
     iterations = opt.lr_decay_epochs.split(",")
     opt.lr_decay_epochs = list([])
@@ -195,7 +198,8 @@ def _load_graph(args, device=None):
         from gcc_amd.corpus import build_corpus
 
         files = args.graph_files.split(",") if args.graph_files else None
-        return [(g["row_ptr"], g["col_idx"]) for g in build_corpus(args.graph_dir, files, device=device, keep_on_device=True)]
+        return [(g["row_ptr"], g["col_idx"]) for g in build_corpus(args.graph_dir, files, device=device, keep_on_device=True,
+                                                                     parse=getattr(args, "graph_parse", "host"))]
     if args.graph_npz:
         z = np.load(args.graph_npz)
         return z["row_ptr"], z["col_idx"]
@@ -327,7 +331,7 @@ def main(args):
             checkpoint = torch.load(args.resume, map_location="cpu", weights_only=False)
             pretrain_args = checkpoint["opt"]
             for name in ("fold_idx", "gpu", "finetune", "resume", "cv", "dataset", "epochs", "num_workers",
-                         "batch_size", "dgl_file", "graph_dir", "graph_files", "graph_npz", "synthetic", "max_steps", "producer_lanes", "producer_chunk"):
+                         "batch_size", "dgl_file", "graph_dir", "graph_files", "graph_parse", "graph_npz", "synthetic", "max_steps", "producer_lanes", "producer_chunk"):
                 setattr(pretrain_args, name, getattr(args, name))
             args = pretrain_args
         else:
