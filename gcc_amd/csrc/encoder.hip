@@ -166,28 +166,40 @@ constexpr int kTickWgs = 2048, kTickPhases = 16;
 #define TICK_ADD(kind, ph, v) atomicAdd((unsigned long long *)&L.ticks[((kind) * kTickPhases + (ph)) * kTickWgs + (int)blockIdx.y * 1024 + (int)blockIdx.x], (unsigned long long)(v))
 #define GIN_TICK(ph) do { if (L.ticks && tid == 0) { const long long now_ = device_ticks(); TICK_ADD(a.first ? 0 : 1, ph, now_ - tick_); tick_ = now_; } } while (0)
 
-// (3 workgroups per CU by LDS -- 48.8 KiB with the staged weight -- so up to 168 registers are free: 8 gathered rows in flight)
+// (3 workgroups per CU by LDS -- 48.8 KiB with the staged weight -- so up to 168 registers are free: the gather's ring of 4 + 4 rows)
 #ifndef GIN_IN_PER_CU
 #define GIN_IN_PER_CU 3
 #endif
 #ifndef GIN_GATHER_J
 #define GIN_GATHER_J 8
 #endif
+// four workgroups per CU, a timing variant (tools/build_variant.sh in4 -DGIN_IN_PER_CU=4 -DGIN_GATHER_J=4): 128 registers, 39,824 B
+// of LDS.  Measured against three and not shipped: profiles/gather_ring_bench_ab.txt
+#define GIN_IN_ALIAS (GIN_IN_PER_CU >= 4 && GIN_IN_LDS_W)
 __global__ __launch_bounds__(kThreads, GIN_IN_PER_CU) void gin_in_kernel(InLaunch L)
 {
     TRAIN_STEP_WAVE_PRIORITY();
     __shared__ float T[kTile * kLdt];
-    __shared__ __attribute__((aligned(16))) float part[32 * H];      // (also the fp64 scratch of bn_table)
     __shared__ float red[4 * 2 * H];
     __shared__ int prow[32];
     __shared__ int rpl[kTile + 1], gidl[kTile];
     const InArgs &a = L.p[blockIdx.y];
     const int tid = (int)threadIdx.x, t = tid & 15, gi = tid >> 4, lane = lane_id(), wv = tid >> 6;
     int N;
+#if GIN_IN_ALIAS
+    // 39,824 B instead of 49,040: the side slots are live only inside the gather and lie in the weight's region, which is
+    // stored behind the gather of every tile (its requests go out with the tile's rows); the BatchNorm tables are dead once
+    // ab / ac are in registers and lie in the statistics' reduction scratch
+    __shared__ __attribute__((aligned(16))) float Wl[H * kLdt];
+    __shared__ __attribute__((aligned(16))) float bl[H];
+    float *const part = Wl, *const tabb = red, *const tabc = red + 2 * H;
+#else
+    __shared__ __attribute__((aligned(16))) float part[32 * H];      // (also the fp64 scratch of bn_table)
     __shared__ float tabb[2 * H], tabc[2 * H];
 #if GIN_IN_LDS_W
     __shared__ float Wl[H * kLdt];                 // linears.0 weight, staged once per workgroup
     __shared__ __attribute__((aligned(16))) float bl[H];     // and its bias
+#endif
 #endif
     Aff4 ab, ac;
     long long tick_ = L.ticks ? device_ticks() : 0;
@@ -206,9 +218,23 @@ __global__ __launch_bounds__(kThreads, GIN_IN_PER_CU) void gin_in_kernel(InLaunc
 #pragma unroll
         for (int i = 0; i < kTile / 16; ++i) own[i] = load(cap_row(tile0 + gi + 16 * i, a.cap));
     };
+#if GIN_IN_ALIAS
+    WStage wst = stage_weights_request(a.w0, a.kdim);               // in flight with N and the statistics; again with every further tile
+    // a thread's fragments 0, 1 are rows 0-31 of the weight (the side slots cover rows 0-28: 8 KiB / 288 B): stored behind the
+    // gather; fragments 2, 3 (rows 32-63) are stored once and their 8 registers are free during the gather
+    static_assert(32 * H <= 32 * kLdt, "the side slots end inside the first two fragments' rows");
+    auto stage_frag = [&](int i) {
+        const int idx = tid + i * kThreads, r = idx >> 4, c4 = 4 * (idx & 15);
+        st4(&Wl[r * kLdt + c4], stage_masked(wst, i, a.kdim));
+    };
+    auto stage_hi = [&] { stage_frag(2); stage_frag(3); };
+    auto stage_lo = [&] { stage_frag(0); stage_frag(1); };
+#endif
     {
 #if GIN_IN_LDS_W
+#if !GIN_IN_ALIAS
         const WStage wst = stage_weights_request(a.w0, a.kdim);     // in flight with N and the statistics
+#endif
         const float b_own = a.b0 ? a.b0[tid & (H - 1)] : 0.f;
 #endif
         if (!a.first) {                            // block-uniform
@@ -225,7 +251,11 @@ __global__ __launch_bounds__(kThreads, GIN_IN_PER_CU) void gin_in_kernel(InLaunc
             if (no_tiles(N)) return;
         }
 #if GIN_IN_LDS_W
+#if !GIN_IN_ALIAS
         stage_weights_store(Wl, wst, a.kdim);
+#else
+        stage_hi();
+#endif
         if (tid < H) bl[tid] = b_own;
 #endif
     }
@@ -244,7 +274,12 @@ __global__ __launch_bounds__(kThreads, GIN_IN_PER_CU) void gin_in_kernel(InLaunc
         // 1. own rows; the tile's row pointers and graph ids ride in the same round trip (the pooling and the gather
         //    would otherwise each start with one of their own)
         {
-            if (tw.ti != tf) request(tile0);      // (a launch with more tiles than workgroups)
+            if (tw.ti != tf) {                    // (a launch with more tiles than workgroups)
+                request(tile0);
+#if GIN_IN_ALIAS
+                wst = stage_weights_request(a.w0, a.kdim);   // (rows 32-63 are still in place; asked for again with the rest)
+#endif
+            }
             if (tid <= nrows) rpl[tid] = rp_own;
             if (tid >= 128 && tid - 128 < nrows) gidl[tid - 128] = gid_own;
 #pragma unroll
@@ -269,6 +304,10 @@ __global__ __launch_bounds__(kThreads, GIN_IN_PER_CU) void gin_in_kernel(InLaunc
         gather_tile<GIN_GATHER_J>(T, part, prow, nrows, a.col_idx, load, xform, a.nbr_weight, rpl, pooling);
 #else
         pooling();
+#endif
+#if GIN_IN_ALIAS
+        stage_lo();                               // over the side slots: the gather's closing barrier is behind their last read
+        lds_barrier();
 #endif
         GIN_TICK(3);
         // 4. keep agg for the weight gradient of linears.0

@@ -576,6 +576,7 @@ struct EmbArgs {
     int32_t cap;              // node capacity of the per-node buffers
 };
 
+template <bool B> struct NarrowTag { static constexpr bool value = B; };
 __global__ __launch_bounds__(kThreads) void gin_bwd_emb_kernel(EmbArgs a)
 {
     TRAIN_STEP_WAVE_PRIORITY();
@@ -586,10 +587,24 @@ __global__ __launch_bounds__(kThreads) void gin_bwd_emb_kernel(EmbArgs a)
     __shared__ int prow[32];
     __shared__ int rpl[kTile + 1];
     const int tid = (int)threadIdx.x, t = tid & 15, gi = tid >> 4;
-    // only the degree-embedding columns [pos_dim, pos_dim + emb_dim) of dx0 are used: the lanes whose four columns lie outside them
-    // request nothing (a quarter of the gather's bytes at pos 32 / emb 16) and carry zeros
-    const bool my_cols = 4 * t + 3 >= a.pos_dim && 4 * t < a.pos_dim + a.emb_dim;
-    auto ident = [&](int u) -> F4 { return my_cols ? ld4(a.D + (int64_t)u * H + 4 * t) : zero4(); };
+    // Only the degree-embedding columns [pos_dim, pos_dim + emb_dim) of dx0 are used.  No lane-divergent branch around the row load
+    // in either form: a load under one is waited for at once, and the gather's ring of requests was a chain of round trips here.
+    // kNarrow (emb_dim <= 16, the block-uniform usual case): lane t of a lane group asks for ONE float, embedding column t, and
+    // carries it as the x of its F4 -- 64 bytes a row instead of 256, every lane busy; T and the side slots hold embedding column c
+    // at float 4 c.  The same additions per column in the same order as the wide form: the same bits.
+    // Wide: lanes whose four columns lie outside the embedding ask for the row's first embedding quad again (a line the row's
+    // request fetches anyway); `mine` drops it where the row is used.
+  auto run = [&](auto narrow_tag) {
+    constexpr bool kNarrow = decltype(narrow_tag)::value;
+    const bool my_cols = kNarrow ? t < a.emb_dim : 4 * t + 3 >= a.pos_dim && 4 * t < a.pos_dim + a.emb_dim;
+    const int tq = my_cols ? t : min(a.pos_dim >> 2, H / 4 - 1);                    // (wide; inside the row also at emb_dim 0)
+    const int cx = min(a.pos_dim + min(t, max(a.emb_dim, 1) - 1), H - 1);            // (narrow; inside the row also at emb_dim 0)
+    auto ident = [&](int u) -> F4 {
+        if constexpr (kNarrow) return F4{a.D[(int64_t)u * H + cx], 0.f, 0.f, 0.f};
+        else return ld4(a.D + (int64_t)u * H + 4 * tq);
+    };
+    auto mine = [&](F4 x) -> F4 { return my_cols ? x : zero4(); };
+    auto tcol = [&](int c) { return kNarrow ? 4 * c : a.pos_dim + c; };             // where T keeps embedding column c
     // row pointers, graph ids and the lane group's 4 rows of the FIRST tile: requested together with the node count (clamped to
     // the capacity), stored afterwards (a load under `if (tid < ...)` next to its LDS store is a round trip of its own)
     const int tf = first_tile();
@@ -614,7 +629,7 @@ __global__ __launch_bounds__(kThreads) void gin_bwd_emb_kernel(EmbArgs a)
             if (tid <= nrows) rpl[tid] = rp_own;
             if (tid >= 128 && tid - 128 < nrows) gidl[tid - 128] = gid_own;
 #pragma unroll
-            for (int i = 0; i < kTile / 16; ++i) st4(&T[(gi + 16 * i) * kLdt + 4 * t], gi + 16 * i < nrows ? own[i] : zero4());
+            for (int i = 0; i < kTile / 16; ++i) st4(&T[(gi + 16 * i) * kLdt + 4 * t], gi + 16 * i < nrows ? mine(own[i]) : zero4());
         }
         __syncthreads();
         // (the pooled-path gradients of a batch requested together, graph ids from LDS: 8 dependent round trips before; the first
@@ -632,7 +647,7 @@ __global__ __launch_bounds__(kThreads) void gin_bwd_emb_kernel(EmbArgs a)
 #pragma unroll
             for (int i = 0; i < kIt; ++i) dv[i] = a.dpooled0[(int64_t)gidl[rr[i]] * H + a.pos_dim + cc[i]];
         };
-        gather_tile<BWD_GATHER_J>(T, part, prow, nrows, a.col_idx, ident, [](F4 x) { return x; }, 1.0f, rpl, [&] { pooled_request(0); });
+        gather_tile<BWD_GATHER_J>(T, part, prow, nrows, a.col_idx, ident, mine, 1.0f, rpl, [&] { pooled_request(0); });
         // all threads: add the pooled-path gradient and look the clamped degree up ...
         if (tid < nrows) {
             const int deg = rpl[tid + 1] - rpl[tid];
@@ -642,15 +657,17 @@ __global__ __launch_bounds__(kThreads) void gin_bwd_emb_kernel(EmbArgs a)
             if (base) pooled_request(base);
 #pragma unroll
             for (int i = 0; i < kIt; ++i)
-                if (base + tid + i * kThreads < total) T[rr[i] * kLdt + a.pos_dim + cc[i]] += dv[i];
+                if (base + tid + i * kThreads < total) T[rr[i] * kLdt + tcol(cc[i])] += dv[i];
         }
         __syncthreads();
         // ... then column c is owned by thread c: LDS only, fixed order, no atomics
         if (tid < a.emb_dim)
-            for (int r = 0; r < nrows; ++r) E[dclrow[r] * a.emb_dim + tid] += T[r * kLdt + a.pos_dim + tid];
+            for (int r = 0; r < nrows; ++r) E[dclrow[r] * a.emb_dim + tid] += T[r * kLdt + tcol(tid)];
         __syncthreads();
     }
     for (int i = tid; i < elems; i += kThreads) a.demb_parts[(int64_t)blockIdx.x * elems + i] = E[i];
+  };
+    if (a.emb_dim <= 16) run(NarrowTag<true>{}); else run(NarrowTag<false>{});
 }
 
 // =========================================================================

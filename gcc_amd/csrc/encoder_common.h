@@ -491,9 +491,20 @@ __device__ __forceinline__ void flush_stats(const float *red, double *stats)
 // trips per tile for an average degree of 5; the gather was 49 of gin_in_kernel's 79 us).  A group sums its chunk in
 // edge order; rows that lie inside the chunk are finished there, the chunk's first and last row go to side slots that
 // one wave adds in group order afterwards -- a fixed order, so the result does not depend on timing.
-// kGatherJ = feature rows a lane group has in flight (4 VGPRs each): 8 where the registers are there (backward kernels:
-// 19 / 34 us against 20.5 / 36.5 with 4), 4 in gin_in_kernel, whose feat() carries two BatchNorm affines (8 spills 23
-// VGPRs there: 59.5 against 53.6 us).
+// kGatherJ = registers for feature rows in flight per lane group (4 VGPRs each), 8 in every caller (GIN_GATHER_J,
+// BWD_GATHER_J, the general kernel of encoder_eval.hip).  They are a ring of two halves of kGatherJ / 2 rows: half B is
+// requested before half A is summed and A is requested again as soon as it is summed, so kGatherJ / 2 to kGatherJ rows
+// are in flight all the time.  (Before, a batch of kGatherJ rows was requested, summed to the last row behind
+// vmcnt(kGatherJ - 1) ... vmcnt(0), and only then was the next batch requested: one full round trip per batch, 3 for the
+// average chunk of 20 edges, 5-8 for the chunk of a tile that holds a hub.)  Only WHEN a row is requested changed: every
+// addition and every flush happens in the order it always had, so the sums are bit for bit the same.
+
+// row_arrived(v): the row whose first float is `v` is waited for HERE (an empty statement that reads the register)
+#ifdef GCC_AMD_HIPEMU
+static inline void row_arrived(float) {}
+#else
+__device__ __forceinline__ void row_arrived(float v) { asm volatile("" ::"v"(v)); }
+#endif
 #ifndef GATHER_DBG
 #define GATHER_DBG 0         // timing experiments only (wrong results): 1 no side-slot pass, 2 no row search, 4 no feature loads
 #endif
@@ -509,9 +520,11 @@ __device__ __forceinline__ void gather_tile(float *T, float *part /* [32 * H] */
                                             const int32_t *col_idx, Load load, Xform xform, float nbr_weight,
                                             const int *rp_lds /* [nrows + 1] */, Overlap overlap)
 {
+    constexpr int kHalf = kGatherJ / 2, kHalves = 16 / kHalf;
+    static_assert(kGatherJ == 2 * kHalf && kHalves * kHalf == 16 && kHalves % 2 == 0, "a 16-edge round is an even number of ring halves");
     const int tid = (int)threadIdx.x, t = tid & 15, gi = tid >> 4, gbase = lane_id() & ~15;
     const int ebeg = rp_lds[0], eend = rp_lds[nrows];
-    const int chunk = (eend - ebeg + 15) >> 4;          // edges per group (block-uniform)
+    const int chunk = wave_uniform((eend - ebeg + 15) >> 4);   // edges per group (block-uniform: the ring's branches are scalar)
     const int e0 = ebeg + gi * chunk, e1 = min(e0 + chunk, eend);
     if (t < 2) prow[gi * 2 + t] = -1;
     F4 acc = {0.f, 0.f, 0.f, 0.f};
@@ -531,45 +544,97 @@ __device__ __forceinline__ void gather_tile(float *T, float *part /* [32 * H] */
             st4(dst, o);
         }
     };
-    int idx_next = e0 + t < e1 ? col_idx[e0 + t] : -1;
-    overlap();
-    for (int c = 0; c < chunk; c += 16) {                // block-uniform trip counts (the shuffles need every lane)
-        const int e = e0 + c + t;
-        const bool valid = e < e1;
-        const int idx = idx_next;
-        idx_next = e + 16 < e1 ? col_idx[e + 16] : -1;   // the next 16 targets travel with this round's rows (a round trip per round before)
-        int rid = 0;                                     // last r with rp_lds[r] <= e
-        if (valid && !(GATHER_DBG & 2)) {
-            int hi = nrows;
-            while (hi - rid > 1) {
-                const int mid = (rid + hi) >> 1;
-                if (rp_lds[mid] <= e) rid = mid; else hi = mid;
+    // The ring: two halves, A and B, of kHalf rows each.  While one half is summed the other is on its way, and the half that
+    // was just summed is requested again at once, so a chunk pays one exposed round trip plus issue time, also across the
+    // boundary of a 16-edge round.  Halves are counted through the chunk: half q covers the chunk's edges [q kHalf, (q + 1) kHalf),
+    // an even q lives in A, an odd one in B.
+    F4 fa[kHalf], fb[kHalf];
+    int ua[kHalf], ub[kHalf];
+    auto request = [&](F4 (&f)[kHalf], int (&u)[kHalf], int ids, int eb) {
+#pragma unroll
+        for (int j = 0; j < kHalf; ++j) u[j] = wave_shfl(ids, gbase + eb + j);
+#pragma unroll
+        for (int j = 0; j < kHalf; ++j) f[j] = (GATHER_DBG & 4) ? F4{1.f, 1.f, 1.f, 1.f} : load(u[j] < 0 ? 0 : u[j]);   // branch free: all loads in flight
+    };
+    auto consume = [&](F4 (&f)[kHalf], const int (&u)[kHalf], int rid, int eb) {
+        int rj[kHalf];
+#pragma unroll
+        for (int j = 0; j < kHalf; ++j) rj[j] = wave_shfl(rid, gbase + eb + j);
+#pragma unroll
+        for (int j = 0; j < kHalf; ++j) f[j] = xform(f[j]);
+#pragma unroll
+        for (int j = 0; j < kHalf; ++j) {
+            // (waited for HERE on every path: a row that is only used under the branch stays in flight on the other path, and the
+            //  next request into its registers then waits for everything -- vmcnt(0) in front of every request of layer 0)
+            row_arrived(f[j].x);
+            if (u[j] >= 0) {                             // group-uniform
+                if (rj[j] != cur) {
+                    flush(false);
+                    acc = F4{0.f, 0.f, 0.f, 0.f};
+                    cur = rj[j];
+                }
+                acc = add4(acc, f[j]);
             }
         }
-        if (c == 0) first = wave_shfl(rid, gbase);       // (an empty chunk never flushes)
-        for (int eb = 0; eb < 16 && c + eb < chunk; eb += kGatherJ) {
-            F4 f[kGatherJ];
-            int u[kGatherJ], rj[kGatherJ];
-#pragma unroll
-            for (int j = 0; j < kGatherJ; ++j) {
-                u[j] = wave_shfl(idx, gbase + eb + j);
-                rj[j] = wave_shfl(rid, gbase + eb + j);
-            }
-#pragma unroll
-            for (int j = 0; j < kGatherJ; ++j) f[j] = (GATHER_DBG & 4) ? F4{1.f, 1.f, 1.f, 1.f} : load(u[j] < 0 ? 0 : u[j]);   // branch free: all loads in flight
-#pragma unroll
-            for (int j = 0; j < kGatherJ; ++j) f[j] = xform(f[j]);
-#pragma unroll
-            for (int j = 0; j < kGatherJ; ++j) {
-                if (u[j] >= 0) {                         // group-uniform
-                    if (rj[j] != cur) {
-                        flush(false);
-                        acc = F4{0.f, 0.f, 0.f, 0.f};
-                        cur = rj[j];
-                    }
-                    acc = add4(acc, f[j]);
+    };
+    int idx = e0 + t < e1 ? col_idx[e0 + t] : -1;
+    overlap();
+    if (chunk > 0) {                                     // block-uniform, as every branch below but the search (the shuffles need every lane)
+        const int nh = (chunk + kHalf - 1) / kHalf;      // halves of the chunk
+        int idx_next = e0 + 16 + t < e1 ? col_idx[e0 + 16 + t] : -1;   // the next 16 targets travel with this round's rows (a round trip per round before)
+        int rid = 0;                                     // last r with rp_lds[r] <= e, for the round that is being summed
+        // half q starts a 16-edge round: its rows' ids.  Needs no feature row: called behind the requests of the round's first halves.
+        auto search = [&](int q) {
+            if (q % kHalves) return;
+            const int e = e0 + q * kHalf + t;
+            rid = 0;
+            if (e < e1 && !(GATHER_DBG & 2)) {
+                int hi = nrows;
+                while (hi - rid > 1) {
+                    const int mid = (rid + hi) >> 1;
+                    if (rp_lds[mid] <= e) rid = mid; else hi = mid;
                 }
             }
+            if (q == 0) first = wave_shfl(rid, gbase);
+        };
+        // half q starts a round: its targets are the ones that came with the round before, and the round after it is asked for
+        auto rotate = [&](int q) {
+            if (q % kHalves) return;
+            const int e = e0 + q * kHalf + t;
+            idx = idx_next;
+            idx_next = e + 16 < e1 ? col_idx[e + 16] : -1;
+        };
+        auto eb_of = [&](int q) { return (q % kHalves) * kHalf; };
+        // Every request of the steady state is unconditional and the loop leaves at its head only.  A branch around a request joins
+        // a path on which the half that is summed next is the youngest load, and the compiler places the wait in front of every row
+        // for that path: vmcnt(kHalf - 1) ... vmcnt(0), the serial round again.  (The same happens with exits from the middle of
+        // the loop: they are turned into flags, and on paper the leaving paths run through the steady state's blocks.)  So B is
+        // requested here even where the chunk has one half only (at most kHalf edges per group: row 0, not used).
+        request(fa, ua, idx, 0);
+        request(fb, ub, idx, kHalf);
+        int q = 0;                                       // A holds half q, B half q + 1: both in flight
+        for (; q + 3 < nh; q += 2) {
+            search(q);
+            consume(fa, ua, rid, eb_of(q));
+            rotate(q + 2);
+            request(fa, ua, idx, eb_of(q + 2));
+            SCHED_FENCE();                               // (nothing of B's sums, and none of their waits, in front of A's requests)
+            consume(fb, ub, rid, eb_of(q + 1));
+            request(fb, ub, idx, eb_of(q + 3));
+            SCHED_FENCE();
+        }
+        // the drain: one to three halves are left, two of them in flight
+        search(q);
+        consume(fa, ua, rid, eb_of(q));
+        if (q + 2 < nh) {
+            rotate(q + 2);
+            request(fa, ua, idx, eb_of(q + 2));
+            SCHED_FENCE();
+            consume(fb, ub, rid, eb_of(q + 1));
+            search(q + 2);
+            consume(fa, ua, rid, eb_of(q + 2));
+        } else {
+            consume(fb, ub, rid, eb_of(q + 1));          // (no such half: every target is -1)
         }
     }
     flush(true);

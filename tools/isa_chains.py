@@ -62,6 +62,16 @@ def demangle(name):
     return name
 
 
+def metadata(text, kernel):
+    """the scalar fields of `kernel`'s entry in the amdhsa.kernels metadata of an assembly listing"""
+    meta = text.split("amdhsa.kernels:", 1)[1]
+    for entry in re.split(r"\n\s*- \.", meta):
+        fields = dict(re.findall(r"\.?([a-z_]+):\s+(\S+)", "." + entry))
+        if kernel in fields.get("name", ""):
+            return {k: int(v) if re.fullmatch(r"-?\d+", v) else v for k, v in fields.items()}
+    raise AssertionError(f"{kernel} not in the listing")
+
+
 def chain(body):
     out = []
     in_flight = 0            # vector loads requested and not yet waited for
