@@ -485,6 +485,31 @@ class GccTextIntsArgs(ctypes.Structure):     # gcc_text_ints_args: tokens of tex
     ]
 
 
+STATUS_TEXT_LINE_SHAPE = 8                   # gcc_text_ints_sep with line_records: a record does not sit on a line of its own
+
+
+class GccTextIntsSepArgs(ctypes.Structure):  # gcc_text_ints_sep_args: gcc_text_ints with a seventh separator and records on lines
+    _fields_ = [("ints", GccTextIntsArgs), ("extra_sep", ctypes.c_int32), ("line_records", ctypes.c_int32)]
+
+
+STATUS_TU_DESCENDS = 1                       # gcc_tu_corpus' own status word: a bit per ValueError of ingest.read_tudataset, in its order
+STATUS_TU_GRAPH_COUNT = 2
+STATUS_TU_BAD_ID = 4
+STATUS_TU_SELF_LOOP = 8
+STATUS_TU_CROSS_GRAPH = 16
+STATUS_TU_REPEATED = 32
+STATUS_TU_ASYMMETRIC = 64
+
+
+class GccTuCorpusArgs(ctypes.Structure):     # gcc_tu_corpus_args: a TU dataset's integers -> the resident corpus (csrc/tu_corpus.hip)
+    _fields_ = [
+        ("pairs", _VP), ("indicator", _VP), ("graph_labels", _VP),
+        ("num_nodes", ctypes.c_int64), ("num_lines", ctypes.c_int64), ("num_labels", ctypes.c_int64),
+        ("node_first", _VP), ("edge_first", _VP), ("row_ptr", _VP), ("col_idx", _VP), ("seed_local", _VP), ("labels", _VP),
+        ("counts", _VP),
+    ]
+
+
 SIGNATURES = {
     "gcc_abi_version": (ctypes.c_int32, []),
     "gcc_last_error": (ctypes.c_char_p, []),
@@ -654,6 +679,11 @@ SIGNATURES = {
     "gcc_text_line_ends": (ctypes.c_int32, [ctypes.POINTER(GccTextLineEndsArgs), ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p,
                                             ctypes.c_void_p]),
     "gcc_text_ints": (ctypes.c_int32, [ctypes.POINTER(GccTextIntsArgs), ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p,
+                                       ctypes.c_void_p]),
+    "gcc_text_ints_sep": (ctypes.c_int32, [ctypes.POINTER(GccTextIntsSepArgs), ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p,
+                                           ctypes.c_void_p]),
+    "gcc_tu_corpus_workspace_bytes": (ctypes.c_int64, [ctypes.c_int64, ctypes.c_int64, ctypes.c_int64]),
+    "gcc_tu_corpus": (ctypes.c_int32, [ctypes.POINTER(GccTuCorpusArgs), ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p,
                                        ctypes.c_void_p]),
 }
 # symbols declared in the header but not built yet are listed here while the build is in progress

@@ -20,6 +20,9 @@
 //                      byte.  A token that runs past the halo is read on from global memory.
 //   ti_select_kernel   (gcc_text_line_ends) a workgroup per query: a binary search over the scanned newline offsets for the tile,
 //                      then the rank inside that one tile.
+// gcc_text_ints_sep is gcc_text_ints with two knobs, the same kernels: `extra_sep` makes one more byte value a separator (TU's
+// A.txt: ','), and `line_records` (ti_parse_kernel<true>) asks that token r be the first on its line exactly when r % fields == 0 --
+// the separator run in front of it holds a newline, or it is token 0 -- with the lowest offender's offset in summary[3].
 // The only atomics are an integer min (the lowest offending offset, kept as an unsigned word that starts at all ones: -1 as int64)
 // and an integer or (the status bits), so every output word is the same for any grid size and any two calls.  No kernel keeps scratch.
 #include "task_common.h"
@@ -42,6 +45,8 @@ struct TiDev {
     const unsigned char *text;
     long long nbytes, padded, first_byte, max_tokens;
     int fields, keep, tiles;
+    unsigned extra_sep;                               // a seventh separator, or 256: no byte
+    int line_records;                                 // gcc_text_ints_sep: records follow lines
     int32_t *tile_tok, *tile_nl;                      // per tile: token starts, newlines
     long long *tok_off, *nl_off, *totals;             // their exclusive prefixes; totals[0 .. 1]
     int32_t *out;
@@ -52,7 +57,7 @@ struct TiDev {
     long long *ends;
 };
 
-__device__ __forceinline__ bool is_sep(unsigned c) { return c - 9u < 5u || c == 32u; }
+__device__ __forceinline__ bool is_sep(unsigned c, unsigned extra) { return c - 9u < 5u || c == 32u || c == extra; }
 
 // a lane's 16 bytes of a tile: the bytes themselves, and one bit per byte for a token start and for a newline
 struct Span {
@@ -77,7 +82,7 @@ __device__ __forceinline__ Span tile_span(const TiDev &a, long long base, unsign
 #pragma unroll
     for (int j = 0; j < kLane; ++j) {
         const unsigned c = (w[j >> 2] >> (8 * (j & 3))) & 255u;
-        ns |= (is_sep(c) ? 0u : 1u) << j;
+        ns |= (is_sep(c, a.extra_sep) ? 0u : 1u) << j;
         nl |= (c == 10u ? 1u : 0u) << j;
     }
     ns &= valid;
@@ -88,7 +93,7 @@ __device__ __forceinline__ Span tile_span(const TiDev &a, long long base, unsign
     __syncthreads();
     if (lane == 0) {
         if (wv > 0) before = wave_last[wv - 1];
-        else before = (p0 > a.first_byte && p0 <= a.nbytes) ? (is_sep(a.text[p0 - 1]) ? 0u : 1u) : 0u;
+        else before = (p0 > a.first_byte && p0 <= a.nbytes) ? (is_sep(a.text[p0 - 1], a.extra_sep) ? 0u : 1u) : 0u;
     }
     s.starts = ns & ~((ns << 1) | before);
     return s;
@@ -171,7 +176,7 @@ __global__ __launch_bounds__(kThreads) void ti_scan_kernel(TiDev a)
             a.summary[0] = (unsigned long long)ca;
             a.summary[1] = kNone;
             a.summary[2] = kNone;
-            a.summary[3] = 0;
+            a.summary[3] = a.line_records ? kNone : 0;
             if (ca < a.max_tokens) atomicOr(a.status, (int32_t)GCC_STATUS_TEXT_SHORT);
         }
     }
@@ -190,7 +195,8 @@ template <class U> __device__ __forceinline__ void div_fields(U x, int fields, U
     r = (unsigned)(x - q * (U)fields);
 }
 
-__global__ __launch_bounds__(kThreads) void ti_parse_kernel(TiDev a)
+// kLines: records follow lines (gcc_text_ints_sep's line_records)
+template <bool kLines> __global__ __launch_bounds__(kThreads) void ti_parse_kernel(TiDev a)
 {
     __shared__ unsigned wave_last[kWaves];
     __shared__ int red[2][kWaves];
@@ -213,7 +219,7 @@ __global__ __launch_bounds__(kThreads) void ti_parse_kernel(TiDev a)
         unsigned long long rec0;
         unsigned f0;
         div_fields((unsigned long long)tok0, a.fields, rec0, f0);
-        unsigned long long min_bad = kNone, min_range = kNone;
+        unsigned long long min_bad = kNone, min_range = kNone, min_shape = kNone;
         int bits = 0;
         unsigned rank = (unsigned)ex;
         for (unsigned left = s.starts; left; left &= left - 1, ++rank) {
@@ -233,7 +239,7 @@ __global__ __launch_bounds__(kThreads) void ti_parse_kernel(TiDev a)
                     neg = c == '-';
                     return;
                 }
-                if (is_sep(c)) {
+                if (is_sep(c, a.extra_sep)) {
                     open = false;
                     return;
                 }
@@ -279,9 +285,32 @@ __global__ __launch_bounds__(kThreads) void ti_parse_kernel(TiDev a)
             const unsigned value = neg ? 0u - v : v;
             a.out[(long long)(rec0 + q) * a.keep + field] = (!bad && fits) ? (int32_t)value : 0;
         }
+        if (kLines) {
+            // a loop of its own (inside the parse loop it costs that loop scalar registers).  First on its line: it is token 0, or
+            // the separator run in front of it (which ends at the token before it, at or above first_byte) holds a newline
+            rank = (unsigned)ex;
+            for (unsigned left = s.starts; left; left &= left - 1, ++rank) {
+                if (tok0 + rank >= a.max_tokens) break;
+                const long long off = base + tid * kLane + __builtin_ctz(left);
+                unsigned q, field;
+                div_fields(f0 + rank, a.fields, q, field);
+                bool first = tok0 + rank == 0;
+                if (!first) {
+                    long long p = off - 1;
+                    unsigned c = a.text[p];
+                    while (c != 10u && is_sep(c, a.extra_sep) && p > a.first_byte) c = a.text[--p];
+                    first = c == 10u;
+                }
+                if (first != (field == 0u)) {
+                    bits |= GCC_STATUS_TEXT_LINE_SHAPE;
+                    min_shape = (unsigned long long)off < min_shape ? (unsigned long long)off : min_shape;
+                }
+            }
+        }
         if (bits) atomicOr(a.status, (int32_t)bits);
         if (min_bad != kNone) atomicMin(&a.summary[1], min_bad);
         if (min_range != kNone) atomicMin(&a.summary[2], min_range);
+        if (kLines && min_shape != kNone) atomicMin(&a.summary[3], min_shape);
         __syncthreads();                              // (the next tile overwrites the copy)
     }
 }
@@ -372,6 +401,7 @@ TiDev bind(const Plan &pl, void *workspace, const uint8_t *text, int64_t nbytes)
     d.nbytes = nbytes;
     d.padded = (nbytes + kLane - 1) / kLane * kLane;
     d.fields = d.keep = 1;
+    d.extra_sep = 256u;
     d.tiles = pl.tiles;
     d.tile_tok = ws_at<int32_t>(workspace, pl.off_tile_tok);
     d.tile_nl = ws_at<int32_t>(workspace, pl.off_tile_nl);
@@ -382,6 +412,52 @@ TiDev bind(const Plan &pl, void *workspace, const uint8_t *text, int64_t nbytes)
 }
 
 int tile_grid(const Plan &pl) { return pl.tiles < kGrid ? pl.tiles : kGrid; }
+
+int run_ints(const char *who, const gcc_text_ints_args *h, int32_t extra_sep, int32_t line_records, void *workspace, int64_t workspace_bytes,
+             int32_t *status, void *stream)
+{
+    int rc = null_member(who, {{h, "args"}});
+    if (rc) return rc;
+    if ((rc = check_text(who, h->nbytes))) return rc;
+    if (h->first_byte < 0 || h->first_byte > h->nbytes) {
+        snprintf(g_err, kErrLen, "%s: first_byte %lld outside [0, nbytes = %lld]", who, (long long)h->first_byte, (long long)h->nbytes);
+        return -2;
+    }
+    if (h->fields < 1 || h->fields > 4 || h->keep < 1 || h->keep > h->fields) {
+        snprintf(g_err, kErrLen, "%s: fields %d / keep %d: 1 <= keep <= fields <= 4", who, (int)h->fields, (int)h->keep);
+        return -2;
+    }
+    if (h->max_tokens < 0 || h->max_tokens % h->fields != 0) {
+        snprintf(g_err, kErrLen, "%s: max_tokens %lld is not a multiple of fields %d", who, (long long)h->max_tokens, (int)h->fields);
+        return -2;
+    }
+    // (the quotient first: max_tokens * keep may not fit int64)
+    if (h->max_tokens / h->fields > (int64_t)INT32_MAX / h->keep) {
+        snprintf(g_err, kErrLen, "%s: max_tokens %lld / fields %d * keep %d: the words stored must stay below 2^31", who, (long long)h->max_tokens,
+                 (int)h->fields, (int)h->keep);
+        return -2;
+    }
+    if ((rc = check_buffer(who, h->text, h->nbytes, h->capacity))) return rc;
+    if ((rc = null_member(who, {{status, "status"}, {h->out, "out", h->max_tokens > 0}, {h->summary, "summary"}}))) return rc;
+    const Plan pl = make_plan(h->nbytes);
+    if ((rc = check_workspace(who, "gcc_text_ints_workspace_bytes", workspace, workspace_bytes, pl.total))) return rc;
+    TiDev d = bind(pl, workspace, h->text, h->nbytes);
+    d.first_byte = h->first_byte;
+    d.max_tokens = h->max_tokens;
+    d.fields = h->fields;
+    d.keep = h->keep;
+    d.out = h->out;
+    d.summary = reinterpret_cast<unsigned long long *>(h->summary);
+    d.status = status;
+    d.extra_sep = extra_sep ? (unsigned)extra_sep : 256u;
+    d.line_records = line_records;
+    hipStream_t s = (hipStream_t)stream;
+    hipLaunchKernelGGL(ti_count_kernel, dim3(tile_grid(pl)), dim3(kThreads), 0, s, d);
+    hipLaunchKernelGGL(ti_scan_kernel, dim3(1), dim3(kThreads), 0, s, d);
+    if (h->max_tokens > 0 && line_records) hipLaunchKernelGGL(ti_parse_kernel<true>, dim3(tile_grid(pl)), dim3(kThreads), 0, s, d);
+    else if (h->max_tokens > 0) hipLaunchKernelGGL(ti_parse_kernel<false>, dim3(tile_grid(pl)), dim3(kThreads), 0, s, d);
+    return launched();
+}
 
 }  // namespace
 
@@ -429,45 +505,24 @@ int32_t gcc_text_line_ends(const gcc_text_line_ends_args *h, void *workspace, in
 
 int32_t gcc_text_ints(const gcc_text_ints_args *h, void *workspace, int64_t workspace_bytes, int32_t *status, void *stream)
 {
-    const char *who = "gcc_text_ints";
-    int rc = null_member(who, {{h, "args"}});
+    return run_ints("gcc_text_ints", h, 0, 0, workspace, workspace_bytes, status, stream);
+}
+
+int32_t gcc_text_ints_sep(const gcc_text_ints_sep_args *h, void *workspace, int64_t workspace_bytes, int32_t *status, void *stream)
+{
+    const char *who = "gcc_text_ints_sep";
+    const int rc = null_member(who, {{h, "args"}});
     if (rc) return rc;
-    if ((rc = check_text(who, h->nbytes))) return rc;
-    if (h->first_byte < 0 || h->first_byte > h->nbytes) {
-        snprintf(g_err, kErrLen, "%s: first_byte %lld outside [0, nbytes = %lld]", who, (long long)h->first_byte, (long long)h->nbytes);
+    const int32_t c = h->extra_sep;
+    if (c < 0 || c > 255 || (c >= 9 && c <= 13) || c == 32 || (c >= '0' && c <= '9') || c == '+' || c == '-') {
+        snprintf(g_err, kErrLen, "%s: extra_sep %d: 0, or a byte 1..255 that is no separator, digit or sign", who, (int)c);
         return -2;
     }
-    if (h->fields < 1 || h->fields > 4 || h->keep < 1 || h->keep > h->fields) {
-        snprintf(g_err, kErrLen, "%s: fields %d / keep %d: 1 <= keep <= fields <= 4", who, (int)h->fields, (int)h->keep);
+    if (h->line_records != 0 && h->line_records != 1) {
+        snprintf(g_err, kErrLen, "%s: line_records %d is neither 0 nor 1", who, (int)h->line_records);
         return -2;
     }
-    if (h->max_tokens < 0 || h->max_tokens % h->fields != 0) {
-        snprintf(g_err, kErrLen, "%s: max_tokens %lld is not a multiple of fields %d", who, (long long)h->max_tokens, (int)h->fields);
-        return -2;
-    }
-    // (the quotient first: max_tokens * keep may not fit int64)
-    if (h->max_tokens / h->fields > (int64_t)INT32_MAX / h->keep) {
-        snprintf(g_err, kErrLen, "%s: max_tokens %lld / fields %d * keep %d: the words stored must stay below 2^31", who, (long long)h->max_tokens,
-                 (int)h->fields, (int)h->keep);
-        return -2;
-    }
-    if ((rc = check_buffer(who, h->text, h->nbytes, h->capacity))) return rc;
-    if ((rc = null_member(who, {{status, "status"}, {h->out, "out", h->max_tokens > 0}, {h->summary, "summary"}}))) return rc;
-    const Plan pl = make_plan(h->nbytes);
-    if ((rc = check_workspace(who, "gcc_text_ints_workspace_bytes", workspace, workspace_bytes, pl.total))) return rc;
-    TiDev d = bind(pl, workspace, h->text, h->nbytes);
-    d.first_byte = h->first_byte;
-    d.max_tokens = h->max_tokens;
-    d.fields = h->fields;
-    d.keep = h->keep;
-    d.out = h->out;
-    d.summary = reinterpret_cast<unsigned long long *>(h->summary);
-    d.status = status;
-    hipStream_t s = (hipStream_t)stream;
-    hipLaunchKernelGGL(ti_count_kernel, dim3(tile_grid(pl)), dim3(kThreads), 0, s, d);
-    hipLaunchKernelGGL(ti_scan_kernel, dim3(1), dim3(kThreads), 0, s, d);
-    if (h->max_tokens > 0) hipLaunchKernelGGL(ti_parse_kernel, dim3(tile_grid(pl)), dim3(kThreads), 0, s, d);
-    return launched();
+    return run_ints(who, &h->ints, c, h->line_records, workspace, workspace_bytes, status, stream);
 }
 
 }  // extern "C"

@@ -100,6 +100,63 @@ class DeviceGraphCorpus:
             self._ring.append(slot)
         self._next = 0
 
+    @classmethod
+    def from_device(cls, corpus, batch_size, with_labels=True, pos_dim=0, expand=1, device=None, num_buffers=3, node_cap=None,
+                    edge_cap=None, placeholder=True, lib=None, ptr=None):
+        """The corpus that is already resident (``TUIngestEngine.read_tudataset(...)["corpus"]``: node_first, row_ptr, col_idx,
+        seed_local, labels as int32 device tensors; sizes, entries as host int64): the same members as ``__init__`` fills, with
+        no per-graph loop and no upload.  ``with_labels=False``: the unlabelled corpus (``labels=None`` of ``__init__``)."""
+        import torch
+
+        from . import _cabi
+
+        self = cls.__new__(cls)
+        self.lib = lib if lib is not None else _cabi.load()
+        self.ptr = ptr if ptr is not None else _cabi.dev_ptr
+        self.device = device if device is not None else corpus["row_ptr"].device
+        self.batch_size, self.pos_dim, self.expand = int(batch_size), int(pos_dim), max(int(expand), 1)
+        if not 1 <= self.batch_size <= _cabi.PACK_GRAPHS_MAX_BATCH:
+            raise ValueError(f"the device batcher packs 1..{_cabi.PACK_GRAPHS_MAX_BATCH} graphs per batch "
+                             f"(GCC_PACK_GRAPHS_MAX_BATCH), got batch_size {self.batch_size}; use batcher=\"host\"")
+        if self.pos_dim and (self.pos_dim < 2 or self.pos_dim % 2):
+            raise ValueError(f"positional rows must have an even size of at least 2 (got {self.pos_dim})")
+        self.sizes = np.asarray(corpus["sizes"], dtype=np.int64)
+        self.entries = np.asarray(corpus["entries"], dtype=np.int64)
+        self.first = np.concatenate([[0], np.cumsum(self.sizes)])
+        G = len(self.sizes)
+        for name, words in (("node_first", G + 1), ("row_ptr", int(self.first[-1]) + 1), ("col_idx", max(int(self.entries.sum()), 1)),
+                            ("seed_local", G), ("labels", G)):
+            t = corpus[name]
+            if t.dtype != torch.int32 or t.dim() != 1 or t.numel() != words or not t.is_contiguous():
+                raise ValueError(f"corpus[{name!r}] must be a contiguous int32 tensor of {words} words")
+        self.node_first, self.row_ptr, self.col_idx = corpus["node_first"], corpus["row_ptr"], corpus["col_idx"]
+        self.seed_local = corpus["seed_local"]
+        self.labels = corpus["labels"] if with_labels else None
+        self.pos = None
+        self.c = _cabi.GccGraphCorpus(num_graphs=G, pos_dim=self.pos_dim, node_first=self.ptr(self.node_first),
+                                      row_ptr=self.ptr(self.row_ptr), col_idx=self.ptr(self.col_idx),
+                                      seed_local=self.ptr(self.seed_local),
+                                      labels=self.ptr(self.labels) if self.labels is not None else None, pos=None)
+        B = self.batch_size
+        largest, most = int(self.sizes.max()) if G else 0, int(self.entries.max()) if G else 0
+        self.node_cap = int(node_cap) if node_cap is not None else B * (largest + 1)
+        self.edge_cap = int(edge_cap) if edge_cap is not None else max(B * most * self.expand, 1)
+        i32 = dict(dtype=torch.int32, device=self.device)
+        self.status = torch.zeros(1, **i32)
+        self.parent_nid = torch.zeros(self.node_cap, **i32)
+        self._placeholder = torch.zeros(self.expand, **i32) if placeholder else None
+        self._ring = []
+        for _ in range(max(int(num_buffers), 1)):
+            slot = dict(node_off=torch.zeros(B + 1, **i32), edge_off=torch.zeros(B + 1, **i32),
+                        graph_id=torch.zeros(self.node_cap, **i32), row_ptr=torch.zeros(self.node_cap + 1, **i32),
+                        col_idx=torch.zeros(self.edge_cap, **i32), seed_local=torch.zeros(B, **i32),
+                        labels=torch.full((B,), -1, **i32))
+            if self.pos_dim:
+                slot["pos"] = torch.zeros(self.node_cap, self.pos_dim, dtype=torch.float32, device=self.device)
+            self._ring.append(slot)
+        self._next = 0
+        return self
+
     def set_pos(self, pos):
         """the table of every graph's positional rows [sum of nodes, pos_dim] (float32, on the device), once it exists"""
         import torch
@@ -222,28 +279,37 @@ class NodeClassificationDataset:
 class GraphClassificationDataset:
     def __init__(self, dataset=None, rw_hops=64, subgraph_size=64, restart_prob=0.8, positional_embedding_size=32,
                  step_dist=(1.0, 0.0, 0.0), graphs=None, edge_multiplicity=1, batch_size=256, device="cuda", batcher="auto",
-                 num_buffers=2):
+                 num_buffers=2, corpus=None):
         """``graphs``: list of (row_ptr, col_idx) of simple symmetric graphs (what TUDataset holds for
         imdb-binary / imdb-multi / rdt-b / rdt-5k / collab); the dataset files themselves are not bundled.
         ``batcher``: ``"device"`` (gcc_pack_graphs from a resident corpus into a ring of ``num_buffers`` buffer sets; what
-        ``"auto"`` means on a GPU) or ``"host"`` (the NumPy loop below; ``"auto"`` off the GPU)."""
+        ``"auto"`` means on a GPU) or ``"host"`` (the NumPy loop below; ``"auto"`` off the GPU).
+        ``corpus``: instead of ``graphs``, the tables that are already on the device
+        (``TUIngestEngine.read_tudataset(...)["corpus"]``); the batcher is then the device one and the host list does not exist."""
         if list(step_dist) != [1.0, 0.0, 0.0]:
             raise NotImplementedError("step_dist other than [1, 0, 0]")
         assert positional_embedding_size > 1
-        if graphs is None:
-            raise ValueError("pass graphs=[(row_ptr, col_idx), ...]")
+        if graphs is None and corpus is None:
+            raise ValueError("pass graphs=[(row_ptr, col_idx), ...] or corpus= (the resident tables of TUIngestEngine)")
+        if graphs is not None and corpus is not None:
+            raise ValueError("pass graphs= or corpus=, not both")
+        if corpus is not None and batcher == "host":
+            raise ValueError('batcher="host" needs graphs=: a resident corpus= holds no host list to batch from')
         self.dataset, self.entire_graph = dataset, True               # graph_dataset.py:320
         self.rw_hops, self.subgraph_size, self.restart_prob = rw_hops, subgraph_size, restart_prob
         self.positional_embedding_size = positional_embedding_size
-        self.graphs = [(np.asarray(rp, dtype=np.int64), np.asarray(ci, dtype=np.int64)) for rp, ci in graphs]
-        self.length = self.total = len(self.graphs)
+        self.corpus_tables = corpus
+        self.graphs = ([(np.asarray(rp, dtype=np.int64), np.asarray(ci, dtype=np.int64)) for rp, ci in graphs]
+                       if corpus is None else None)
+        self.length = self.total = len(self.graphs) if corpus is None else len(corpus["sizes"])
         self.edge_multiplicity = int(edge_multiplicity)
         self.batch_size = int(batch_size)
         self.device = device
         # capacity convention of the pipeline (as DeviceRWRSampler: B * (largest subgraph + 1)): the eigensolver sizes its
         # per-subgraph workspace as node_cap / batch_size
-        self.node_cap = self.batch_size * (max(len(rp) - 1 for rp, _ in self.graphs) + 1)
-        self.batcher = resolve_batcher(batcher, device)
+        largest = max(len(rp) - 1 for rp, _ in self.graphs) if corpus is None else int(np.max(corpus["sizes"]))
+        self.node_cap = self.batch_size * (largest + 1)
+        self.batcher = resolve_batcher(batcher if corpus is None else "device", device)
         self.num_buffers = int(num_buffers)
         self._corpus = None                                           # DeviceGraphCorpus, uploaded on first use
 
@@ -251,16 +317,24 @@ class GraphClassificationDataset:
         return self.length
 
     def _device_corpus(self):
+        if self._corpus is None and self.corpus_tables is not None:
+            self._corpus = DeviceGraphCorpus.from_device(self.corpus_tables, self.batch_size, with_labels=False, device=self.device,
+                                                         num_buffers=self.num_buffers, node_cap=self.node_cap, placeholder=False)
         if self._corpus is None:
             self._corpus = DeviceGraphCorpus(self.graphs, self.batch_size, device=self.device, num_buffers=self.num_buffers,
                                              node_cap=self.node_cap, placeholder=False)
         return self._corpus
+
+    def _need_graphs(self, what):
+        if self.graphs is None:
+            raise RuntimeError(f"{what} needs the host list graphs=; this dataset was built from a resident corpus=")
 
     def check_status(self):
         if self._corpus is not None:
             self._corpus.check_status()
 
     def _convert_idx(self, idx):                                      # :326-329
+        self._need_graphs("_convert_idx")
         rp, _ = self.graphs[idx]
         return idx, int(np.argmax(np.diff(rp)))
 
@@ -272,6 +346,7 @@ class GraphClassificationDataset:
 
         from .sampler import BatchedCSR
 
+        self._need_graphs("_batch_of")
         B = self.batch_size
         node_off, edge_off, rows, cols, seeds = [0], [0], [np.zeros(1, dtype=np.int64)], [np.zeros(0, dtype=np.int64)], []
         for i in idx:
@@ -419,23 +494,30 @@ class GraphClassificationDatasetLabeled(GraphClassificationDataset):
 
     def __init__(self, dataset=None, rw_hops=64, subgraph_size=64, restart_prob=0.8, positional_embedding_size=32,
                  graphs=None, labels=None, edge_multiplicity=1, batch_size=32, run_seed=0, device="cuda", batcher="auto",
-                 num_buffers=3):
+                 num_buffers=3, corpus=None):
         super().__init__(dataset=dataset, rw_hops=rw_hops, subgraph_size=subgraph_size, restart_prob=restart_prob,
                          positional_embedding_size=positional_embedding_size, graphs=graphs,
                          edge_multiplicity=edge_multiplicity, batch_size=batch_size, device=device, batcher=batcher,
-                         num_buffers=num_buffers)
+                         num_buffers=num_buffers, corpus=corpus)
+        if labels is None and corpus is not None:
+            labels = corpus["labels"].cpu().numpy()                    # (the corpus' own, re-indexed 0..C-1)
         if labels is None:
             raise ValueError("pass labels (graph_labels of the TU dataset)")
         self.labels = np.asarray(labels).astype(np.int64)
         assert len(self.labels) == self.length, "one label per graph"
         self.num_classes = int(self.labels.max()) + 1
         self.run_seed = run_seed
-        self.sizes = np.array([len(rp) - 1 for rp, _ in self.graphs], dtype=np.int64)
+        self.sizes = (np.array([len(rp) - 1 for rp, _ in self.graphs], dtype=np.int64) if corpus is None
+                      else np.asarray(corpus["sizes"], dtype=np.int64))
         self.first = np.concatenate([[0], np.cumsum(self.sizes)])
         self._pos = None                                               # [sum of nodes, P] on the device, every graph once
         self.posemb = None
 
     def _device_corpus(self):
+        if self._corpus is None and self.corpus_tables is not None:
+            self._corpus = DeviceGraphCorpus.from_device(self.corpus_tables, self.batch_size, pos_dim=self.positional_embedding_size,
+                                                         expand=self.edge_multiplicity, device=self.device,
+                                                         num_buffers=self.num_buffers, node_cap=self.node_cap)
         if self._corpus is None:
             self._corpus = DeviceGraphCorpus(self.graphs, self.batch_size, labels=self.labels,
                                              pos_dim=self.positional_embedding_size, expand=self.edge_multiplicity,

@@ -32,7 +32,7 @@ def apply_resume(args, checkpoint_opt):
     """train.py:487-505: the checkpoint's options, with these of the command line"""
     pretrain_args = checkpoint_opt
     for name in ("fold_idx", "gpu", "finetune", "resume", "cv", "dataset", "epochs", "num_workers", "batch_size",
-                 "edgelist", "nodelabel", "tudataset", "graphs_npz", "edge_multiplicity", "no_prefetch", "graph_batcher"):
+                 "edgelist", "nodelabel", "tudataset", "graphs_npz", "edge_multiplicity", "no_prefetch", "graph_batcher", "tu_parse"):
         setattr(pretrain_args, name, getattr(args, name, None))
     if args.dataset in GRAPH_CLASSIFICATION_DSETS:
         pretrain_args.num_workers = 0           # train.py:500-502
@@ -48,6 +48,20 @@ def load_labelled(args, device):
               positional_embedding_size=args.positional_embedding_size, batch_size=args.batch_size, device=device)
     mult = getattr(args, "edge_multiplicity", 0) or 0
     if args.dataset in GRAPH_CLASSIFICATION_DSETS:
+        tu_parse = getattr(args, "tu_parse", None) or "host"
+        batcher = getattr(args, "graph_batcher", None) or "auto"
+        if tu_parse not in ("host", "device"):
+            raise SystemExit(f"--tu-parse {tu_parse!r}: host or device")
+        if tu_parse == "device":
+            if not getattr(args, "tudataset", None):
+                raise SystemExit("--tu-parse device says where the files of --tudataset are parsed: pass --tudataset")
+            if batcher == "host":
+                raise SystemExit("--tu-parse device builds the resident corpus of the device batcher: not with --graph-batcher host")
+            from .tu_ingest import TUIngestEngine
+
+            d = TUIngestEngine(device=device).read_tudataset(args.tudataset, args.dataset)
+            return GraphClassificationDatasetLabeled(corpus=d["corpus"], labels=d["graph_labels"], edge_multiplicity=max(mult, 1),
+                                                     run_seed=args.seed, batcher=batcher, **kw)
         if getattr(args, "tudataset", None):
             d = ingest.read_tudataset(args.tudataset, args.dataset)
             graphs, labels = d["graphs"], d["graph_labels"]

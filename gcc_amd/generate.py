@@ -87,7 +87,20 @@ def run(args_test, pipeline=None, save=True):
 
     graphs = None
     multigraph = False
-    if args_test.tudataset:
+    tu_corpus = None
+    tu_parse = getattr(args_test, "tu_parse", None) or "host"
+    if tu_parse not in ("host", "device"):
+        raise SystemExit(f"--tu-parse {tu_parse!r}: host or device")
+    if tu_parse == "device":
+        if not args_test.tudataset:
+            raise SystemExit("--tu-parse device says where the files of --tudataset are parsed: pass --tudataset")
+        if (getattr(args_test, "graph_batcher", None) or "auto") == "host":
+            raise SystemExit("--tu-parse device builds the resident corpus of the device batcher: not with --graph-batcher host")
+        from .tu_ingest import TUIngestEngine
+
+        tu_corpus = TUIngestEngine(device=args.device).read_tudataset(args_test.tudataset, args_test.dataset)["corpus"]
+        graph, mult = None, max(args_test.edge_multiplicity, 1)
+    elif args_test.tudataset:
         graphs = ingest.read_tudataset(args_test.tudataset, args_test.dataset)["graphs"]
         graph, mult = None, max(args_test.edge_multiplicity, 1)
     elif args_test.graphs_npz:
@@ -112,11 +125,11 @@ def run(args_test, pipeline=None, save=True):
         raise SystemExit("pass --edgelist data/<name>/<name>.edgelist, --ss-graph data/panther/<name>.graph, --graph-npz, --graphs-npz or --tudataset (dataset files are not bundled)")
     if args_test.edge_multiplicity:
         mult = args_test.edge_multiplicity
-    if graphs is not None:
+    if graphs is not None or tu_corpus is not None:
         train_dataset = GraphClassificationDataset(                  # generate.py:75-82
             dataset=args_test.dataset, rw_hops=args.rw_hops, subgraph_size=args.subgraph_size,
             restart_prob=args.restart_prob, positional_embedding_size=args.positional_embedding_size,
-            graphs=graphs, edge_multiplicity=mult, batch_size=args_test.batch_size, device=args.device,
+            graphs=graphs, corpus=tu_corpus, edge_multiplicity=mult, batch_size=args_test.batch_size, device=args.device,
             batcher=getattr(args_test, "graph_batcher", None) or "auto")
         node_cap = train_dataset.node_cap
     else:
@@ -130,7 +143,7 @@ def run(args_test, pipeline=None, save=True):
     del checkpoint
     posemb = pipeline.posemb(args_test.batch_size, node_cap, args.positional_embedding_size, getattr(args, "seed", 0))
     emb = test_moco(train_dataset, model, posemb, args)
-    if graphs is None:
+    if graphs is None and tu_corpus is None:
         check_sampler()
     else:
         train_dataset.check_status()

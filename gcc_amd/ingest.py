@@ -216,6 +216,36 @@ def read_tudataset(folder: str, name: str):
     return dict(graphs=graphs, graph_labels=np.searchsorted(values, labels).astype(np.int64), num_labels=len(values))
 
 
+def write_tudataset(folder: str, name: str, graphs, graph_labels, sep: str = ", "):
+    """The inverse of :func:`read_tudataset`: ``graphs`` = [(row_ptr, col_idx), ...] with ids local to each graph and
+    ``graph_labels`` (any integers, one per graph) -> ``<TU name>_A.txt`` (one line ``u<sep>v`` per entry, 1-based global
+    ids, rows in order), ``_graph_indicator.txt`` (graph ids 1..G) and ``_graph_labels.txt``.  -> the three paths."""
+    import os
+
+    tu = TU_NAMES.get(name, name)
+    base = os.path.join(folder, tu + "_")
+    if len(graphs) != len(graph_labels):
+        raise ValueError(f"{len(graphs)} graphs but {len(graph_labels)} graph labels")
+    os.makedirs(folder, exist_ok=True)
+    src, dst, indicator, first = [], [], [], 0
+    for g, (rp, ci) in enumerate(graphs):
+        rp, ci = np.asarray(rp, dtype=np.int64), np.asarray(ci, dtype=np.int64)
+        n = len(rp) - 1
+        src.append(np.repeat(np.arange(n, dtype=np.int64), np.diff(rp)) + first + 1)
+        dst.append(ci + first + 1)
+        indicator.append(np.full(n, g + 1, dtype=np.int64))
+        first += n
+    src = np.concatenate(src) if src else np.zeros(0, dtype=np.int64)
+    dst = np.concatenate(dst) if dst else np.zeros(0, dtype=np.int64)
+    with open(base + "A.txt", "w") as f:
+        f.write("".join(f"{u}{sep}{v}\n" for u, v in zip(src.tolist(), dst.tolist())))
+    with open(base + "graph_indicator.txt", "w") as f:
+        f.write("".join(f"{x}\n" for x in (np.concatenate(indicator).tolist() if indicator else [])))
+    with open(base + "graph_labels.txt", "w") as f:
+        f.write("".join(f"{int(x)}\n" for x in graph_labels))
+    return base + "A.txt", base + "graph_indicator.txt", base + "graph_labels.txt"
+
+
 def read_lscc(path: str):
     """The text layout of the pre-training networks as ``yuxiao_kdd17_graph_to_dgl`` reads it (x2dgl.py:30-47): a ``<word> n``
     line, ``n`` vertex lines (zero-based index and raw id: skipped), a ``<word> m`` line, then ``m`` lines ``u v w`` (``w`` is

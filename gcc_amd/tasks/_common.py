@@ -37,7 +37,7 @@ def fold_ids(labels, seed, folds=FOLDS):
     return fold
 
 
-def generate_namespace(load_path, dataset, device, batch_size, **source):
+def generate_namespace(load_path, dataset, device, batch_size, tu_parse="host", **source):
     """the arguments of gcc_amd.generate.run; ``source``: the members that name the input (edgelist and nodelabel, ss_graph and
     ss_dict, graphs_npz, tudataset), the others are None"""
     import torch
@@ -48,15 +48,15 @@ def generate_namespace(load_path, dataset, device, batch_size, **source):
         raise TypeError(f"unknown input members {sorted(set(source) - set(inputs))}")
     inputs.update(source)
     return argparse.Namespace(load_path=load_path, dataset=dataset, gpu=dev.index if dev.type == "cuda" else None, edge_multiplicity=0,
-                              batch_size=batch_size, wide_eval="chain", graph_batcher="auto", **inputs)
+                              batch_size=batch_size, wide_eval="chain", graph_batcher="auto", tu_parse=tu_parse, **inputs)
 
 
-def checkpoint_table(load_path, dataset, device, batch_size, pipeline=None, **source):
+def checkpoint_table(load_path, dataset, device, batch_size, pipeline=None, tu_parse="host", **source):
     """the input embedded with the checkpoint ``load_path`` -> float32 [rows, hidden] on the host.  ``pipeline``: generate.py's
     seam for the emulator tests."""
     from ..generate import run
 
-    return run(generate_namespace(load_path, dataset, device, batch_size, **source), pipeline=pipeline, save=False).numpy()
+    return run(generate_namespace(load_path, dataset, device, batch_size, tu_parse=tu_parse, **source), pipeline=pipeline, save=False).numpy()
 
 
 def baseline_table(kind, row_ptr, col_idx, d, device, engine=None, **kw):

@@ -132,6 +132,10 @@ def evaluate(emb, labels, seed=0, C=1e5, device="cpu", engine=None, folds=FOLDS,
 def load_labels(a):
     from .. import ingest
 
+    if a.tudataset and getattr(a, "tu_parse", "host") == "device":   # (all three files: the errors are those of --load-path)
+        from ..tu_ingest import TUIngestEngine
+
+        return TUIngestEngine(device=a.device).read_tudataset(a.tudataset, a.dataset)["graph_labels"]
     if a.tudataset:
         return ingest.read_tudataset(a.tudataset, a.dataset)["graph_labels"]
     z = np.load(a.graphs_npz)
@@ -142,7 +146,7 @@ def load_labels(a):
 
 def embed_corpus(a, pipeline=None):
     """the corpus embedded with the checkpoint ``--load-path`` (gcc_amd.generate.run) -> float32 [graphs, hidden]"""
-    return checkpoint_table(a.load_path, a.dataset, a.device, a.batch_size, pipeline, graphs_npz=a.graphs_npz, tudataset=a.tudataset)
+    return checkpoint_table(a.load_path, a.dataset, a.device, a.batch_size, pipeline, tu_parse=a.tu_parse, graphs_npz=a.graphs_npz, tudataset=a.tudataset)
 
 
 def main(argv=None, pipeline=None, engine=None):
@@ -153,6 +157,7 @@ def main(argv=None, pipeline=None, engine=None):
     ap.add_argument("--batch-size", type=int, default=256, help="--load-path: graphs embedded per batch")
     ap.add_argument("--tudataset", default=None, metavar="DIR")
     ap.add_argument("--graphs-npz", default=None)
+    ap.add_argument("--tu-parse", choices=["host", "device"], default="host", help="--tudataset: parse the three files on the host (np.loadtxt) or on the device (gcc_text_ints_sep, gcc_tu_corpus)")
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--device", default="cuda:0")
     ap.add_argument("--C", type=float, default=None, help="the box bound (default 100000); not with --search")
@@ -170,6 +175,10 @@ def main(argv=None, pipeline=None, engine=None):
         ap.error("pass --emb-path, or --load-path to embed the corpus")
     if (a.tudataset is None) == (a.graphs_npz is None):
         ap.error("pass --tudataset DIR or --graphs-npz F (the labels come from the corpus; dataset files are not bundled)")
+    if a.tu_parse == "device" and a.tudataset is None:
+        ap.error("--tu-parse device says where the files of --tudataset are parsed: pass --tudataset")
+    if a.tu_parse == "device" and str(a.device) == "cpu":
+        ap.error("--tu-parse device needs a GPU --device: the TU reader has no CPU path")
     if a.search and a.C is not None:
         ap.error("--C and --search exclude each other: the search picks C from --search-C")
     try:

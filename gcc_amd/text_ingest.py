@@ -34,6 +34,7 @@ INTS_STATUS_BITS = {
     _cabi.STATUS_TEXT_NOT_INTEGER: "a token is not an integer",
     _cabi.STATUS_TEXT_INT32_RANGE: "a kept token's value is outside int32",
     _cabi.STATUS_TEXT_SHORT: "the text holds fewer tokens than max_tokens",
+    _cabi.STATUS_TEXT_LINE_SHAPE: "a record does not sit on a line of its own (line_records)",
 }
 HEAD_BYTES = 4096                                     # where the first line's newline is looked for
 SEPARATORS = b"\t\n\x0b\x0c\r "
@@ -158,6 +159,32 @@ class TextIngestEngine(CabiEngine):
         report = torch.zeros(5, dtype=torch.int64, device=text.device)
         summary, status = report[:4], report[4:].view(torch.int32)[:1]
         self.ints_into(text, nbytes, first_byte, max_tokens, fields, keep, out, summary, status)
+        return dict(out=out, summary=summary, status=status, report=report)
+
+    def ints_sep_into(self, text, nbytes, first_byte, max_tokens, fields, keep, out, summary, status, extra_sep=0, line_records=0,
+                      workspace_bytes=None, capacity=None):
+        """``ints_into`` through gcc_text_ints_sep: ``extra_sep`` is a seventh separator (0: none), ``line_records`` ties records to
+        lines (``summary[3]``: the lowest offending token, or -1).  ``out`` may be None with ``max_tokens == 0``: the count-only call."""
+        a = _cabi.GccTextIntsSepArgs()
+        a.ints.text = self.ptr(text) if text is not None else None
+        a.ints.nbytes, a.ints.capacity = int(nbytes), int(text.numel() if capacity is None else capacity)
+        a.ints.first_byte, a.ints.max_tokens, a.ints.fields, a.ints.keep = int(first_byte), int(max_tokens), int(fields), int(keep)
+        a.ints.out = self.ptr(out) if out is not None and out.numel() else None
+        a.ints.summary = self.ptr(summary) if summary is not None else None
+        a.extra_sep, a.line_records = int(extra_sep), int(line_records)
+        need = _cabi.size_query(self.lib, "gcc_text_ints_workspace_bytes", int(nbytes))
+        self.invoke("gcc_text_ints_sep", a, self.workspace(need, status.device), status, workspace_bytes)
+
+    def ints_sep(self, text, nbytes, first_byte, max_tokens, fields, keep, extra_sep=0, line_records=0):
+        """``ints`` with the two knobs of gcc_text_ints_sep -> the same dict"""
+        self._check_text(text)
+        max_tokens, fields, keep = int(max_tokens), int(fields), int(keep)
+        records = max_tokens // fields if 1 <= fields <= 4 and max_tokens >= 0 and max_tokens % fields == 0 else 0
+        words = records * keep if 1 <= keep <= fields and records * keep < 2 ** 31 else 0          # (the call refuses the rest by name)
+        out = torch.empty((words // keep if words else 0, keep if words else max(keep, 1)), dtype=torch.int32, device=text.device)
+        report = torch.zeros(5, dtype=torch.int64, device=text.device)
+        summary, status = report[:4], report[4:].view(torch.int32)[:1]
+        self.ints_sep_into(text, nbytes, first_byte, max_tokens, fields, keep, out, summary, status, extra_sep, line_records)
         return dict(out=out, summary=summary, status=status, report=report)
 
     @staticmethod

@@ -33,6 +33,7 @@ if __name__ == "__main__":
     parser.add_argument("--edge-multiplicity", type=int, default=0, help="copies of every edge in the reference's DGL graph (edge lists: detected; npz: default 2)")
     parser.add_argument("--batch-size", type=int, default=256)
     parser.add_argument("--graph-batcher", choices=["auto", "host", "device"], default="auto", help="--graphs-npz / --tudataset: assemble batches on the device (gcc_pack_graphs; auto on a GPU) or with the host loop")
+    parser.add_argument("--tu-parse", choices=["host", "device"], default="host", help="--tudataset: parse the three TU files on the host (np.loadtxt) or on the device (gcc_text_ints_sep, gcc_tu_corpus); refused by gcc_amd.generate.run without --tudataset or with --graph-batcher host")
     parser.add_argument("--wide-eval", choices=["chain", "resident"], default="chain", help="wide GIN checkpoints: the any-width eval chain (f32 or the checkpoint's --encoder-dtype), or one LDS-resident bf16 call per batch (gcc_ginw_embed; f32 readout)")
     # fmt: on
     a = parser.parse_args()

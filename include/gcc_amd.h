@@ -1284,6 +1284,58 @@ int64_t gcc_text_ints_workspace_bytes(int64_t nbytes);
  * status (device int32[1], zeroed by the caller). */
 int32_t gcc_text_line_ends(const gcc_text_line_ends_args *a, void *workspace, int64_t workspace_bytes, int32_t *status, void *stream);
 int32_t gcc_text_ints(const gcc_text_ints_args *a, void *workspace, int64_t workspace_bytes, int32_t *status, void *stream);
+/* gcc_text_ints with two knobs (the same kernels; gcc_text_ints is this call with both off).
+ * extra_sep: 0, or one byte value in 1..255 that is none of the six separators and no digit, '+' or '-': a seventh separator
+ * (TU's A.txt separates its two fields with ','; "1,,2" and "1 2" are then two fields as well).
+ * line_records: with 1, token r counted from first_byte must be the first token on its line exactly when r % fields == 0.  "First
+ * on its line": the separator run in front of it holds a byte 10, or it is the first token at or after first_byte; blank lines
+ * pass, a line of more or fewer than `fields` tokens does not.  A violation among the first max_tokens tokens sets
+ * GCC_STATUS_TEXT_LINE_SHAPE and summary[3] holds the offset of the lowest offending token, -1 when there is none (0 with
+ * line_records == 0).  max_tokens == 0 with out == NULL counts the tokens (summary[0]) under the same separators.
+ * The workspace is gcc_text_ints_workspace_bytes(nbytes). */
+#define GCC_STATUS_TEXT_LINE_SHAPE 8    /* line_records: a record does not sit on a line of its own: summary[3] */
+typedef struct gcc_text_ints_sep_args {
+    gcc_text_ints_args ints;
+    int32_t extra_sep, line_records;
+} gcc_text_ints_sep_args;
+int32_t gcc_text_ints_sep(const gcc_text_ints_sep_args *a, void *workspace, int64_t workspace_bytes, int32_t *status, void *stream);
+
+/* ---- TU dataset tables -> the resident corpus of gcc_pack_graphs (csrc/tu_corpus.hip): what gcc_amd.ingest.read_tudataset and
+ * DeviceGraphCorpus.__init__ build on the host, from the integers of <NAME>_A.txt, _graph_indicator.txt and _graph_labels.txt.
+ * Integer arithmetic and integer atomics only: the outputs are a function of the SET of lines, never of their order or the grid.
+ * Graph ids need not start at 1 or be contiguous; a node or a graph without an entry is legal; label values may be negative or
+ * sparse.  Rows of any length are served (the row classes of gcc_graph_build).
+ * STATUS (device int32[1], zeroed by the caller, OR-ed): one bit per ValueError of the host reader, in the host's order, so the
+ * lowest set bit names the error the host raises first.  A step runs only on what the steps before it found sound: DESCENDS and
+ * GRAPH_COUNT stop everything behind them, BAD_ID stops the four behind it, SELF_LOOP and CROSS_GRAPH are found together,
+ * REPEATED and ASYMMETRIC need the sorted rows and are looked for only on a clean word.  With any bit set the tables are not
+ * promised; with GRAPH_COUNT set counts[0] still is. */
+#define GCC_STATUS_TU_DESCENDS 1        /* graph_indicator descends somewhere */
+#define GCC_STATUS_TU_GRAPH_COUNT 2     /* the distinct indicator values (counts[0]) are not num_labels many */
+#define GCC_STATUS_TU_BAD_ID 4          /* a line of A.txt names an id outside [1, N] */
+#define GCC_STATUS_TU_SELF_LOOP 8       /* a line u, u */
+#define GCC_STATUS_TU_CROSS_GRAPH 16    /* a line joins nodes of two graphs */
+#define GCC_STATUS_TU_REPEATED 32       /* a line stands twice */
+#define GCC_STATUS_TU_ASYMMETRIC 64     /* a line u, v without its v, u */
+typedef struct gcc_tu_corpus_args {
+    const int32_t *pairs;                  /* device [m][2]: the 1-based ids as A.txt has them, any line order; NULL when m == 0 */
+    const int32_t *indicator;              /* device [N]: the file's graph id of every node, in file order */
+    const int32_t *graph_labels;           /* device [L]: the raw label values */
+    int64_t num_nodes, num_lines, num_labels;  /* 1 <= N < 2^31 - 1, 0 <= m < 2^31, 1 <= L < 2^31 - 1 */
+    int32_t *node_first;                   /* out, device [L + 1] */
+    int32_t *edge_first;                   /* out, device [L + 1]: edge_first[g] = row_ptr[node_first[g]] */
+    int32_t *row_ptr;                      /* out, device [N + 1]: global offsets */
+    int32_t *col_idx;                      /* out, device [m]: ids local to their graph, every row ascending; NULL when m == 0 */
+    int32_t *seed_local;                   /* out, device [L]: the first maximum of the degrees, 0 for a graph without entries */
+    int32_t *labels;                       /* out, device [L]: 0..C-1 in ascending order of the distinct raw values */
+    int64_t *counts;                       /* out, device [8]: G, C, the most nodes of a graph, the most entries of a graph, the
+                                            * longest row, 0, 0, 0 */
+} gcc_tu_corpus_args;
+/* bytes of workspace; negative on a size out of range, gcc_last_error() names it */
+int64_t gcc_tu_corpus_workspace_bytes(int64_t num_nodes, int64_t num_lines, int64_t num_labels);
+/* A size out of range, a NULL member the call needs and a short workspace return rc < 0, name the member in gcc_last_error() and
+ * launch nothing.  No host synchronisation: everything is enqueued on `stream`. */
+int32_t gcc_tu_corpus(const gcc_tu_corpus_args *a, void *workspace, int64_t workspace_bytes, int32_t *status, void *stream);
 
 #ifdef __cplusplus
 }

@@ -14,7 +14,8 @@ without DGL (gcc_amd/ingest.py).  Extra flags (not in the reference): --dgl-file
 --graph-npz / --synthetic choose another pre-training graph, --graph-dir [--graph-files]
 builds it on the device from raw .lscc edge files (gcc_amd/corpus.py); --edgelist / --nodelabel,
 --tudataset, --graphs-npz and --edge-multiplicity name the labelled data of --finetune
-(as generate.py's flags do; the dataset files are not bundled).
+(as generate.py's flags do; the dataset files are not bundled); --tu-parse device parses
+the files of --tudataset on the device (gcc_amd/tu_ingest.py; the default is the host reader).
 Multi-GPU: launch with torch.distributed.run; the seed batch is sharded by rank,
 keys are all-gathered before the enqueue, gradients are all-reduced (RCCL).
 """
@@ -138,9 +139,14 @@ def parse_option(argv=None):
     parser.add_argument("--edge-multiplicity", type=int, default=0, help="copies of every edge in the reference's DGL graph (edge lists: detected)")
     parser.add_argument("--no-prefetch", action="store_true", help="--finetune: make each batch on the step's stream")
     parser.add_argument("--graph-batcher", choices=["auto", "host", "device"], default="auto", help="--finetune on graph-classification datasets: assemble batches on the device (gcc_pack_graphs; auto on a GPU) or with the host loop")
+    parser.add_argument("--tu-parse", choices=["host", "device"], default="host", help="--finetune with --tudataset: parse the three TU files on the host (np.loadtxt) or on the device (gcc_text_ints_sep, gcc_tu_corpus)")
     # fmt: on
 
     opt = parser.parse_args(argv)
+    if opt.tu_parse == "device" and not opt.tudataset:
+        parser.error("--tu-parse device says where the files of --tudataset are parsed: pass --tudataset")
+    if opt.tu_parse == "device" and opt.graph_batcher == "host":
+        parser.error("--tu-parse device builds the resident corpus of the device batcher: not with --graph-batcher host")
     if opt.graph_dir is not None:
         given = sys.argv[1:] if argv is None else list(argv)
         if opt.graph_npz or opt.synthetic or any(a == "--dgl-file" or a.startswith("--dgl-file=") for a in given):
