@@ -51,25 +51,31 @@ class NceEngine:
         a.dtype = {"f32": 0, "bf16": 1}[self.dtype]
         return a
 
+    MOCO_DEFERRED = 2                 # GCC_NCE_POS_MOCO_DEFERRED
+
     def forward(self, q, k, mem, T, pos_mode, dense=False, lse_rows=None, patch=None, patch_index=0, stream=None,
-                prof=None):
+                prof=None, defer_means=False):
+        """``defer_means`` (MoCo head, no dense output): ``loss`` / ``prob`` are written by :meth:`backward` called with the
+        same flag, not here -- for a caller that reads them only after the backward call."""
+        assert not defer_means or (pos_mode == 0 and not dense)
         B, K = q.shape[0], mem.shape[0]
         f32 = dict(dtype=torch.float32, device=q.device)
         outs = dict(lse=torch.empty(lse_rows or B, **f32), pos=torch.empty(B, **f32), loss=torch.empty(1, **f32),
                     prob=torch.empty(1, **f32))
         out = torch.empty(B, K + (1 if pos_mode == 0 else 0), **f32) if dense else None
         ws, nbytes = self._workspace(B, K, q.device)
-        a = self._args(q, k, mem, 1.0 / T, pos_mode, patch, patch_index, outs, out)
+        a = self._args(q, k, mem, 1.0 / T, self.MOCO_DEFERRED if defer_means else pos_mode, patch, patch_index, outs, out)
         _cabi.call(self.lib, "gcc_nce_forward", ctypes.byref(a), self.ptr(ws), nbytes, prof.handle if prof else None, stream)
         outs["out"] = out
         return outs
 
     def backward(self, q, k, mem, T, pos_mode, outs, dloss, patch=None, patch_index=0, by_mem_row=False,
-                 stream=None, prof=None):
+                 stream=None, prof=None, defer_means=False):
+        assert not defer_means or (pos_mode == 0 and not by_mem_row)
         B, K = q.shape[0], mem.shape[0]
         dq = torch.empty_like(q)
         ws, nbytes = self._workspace(B, K, q.device)
-        a = self._args(q, k, mem, 1.0 / T, pos_mode, patch, patch_index, outs, None)
+        a = self._args(q, k, mem, 1.0 / T, self.MOCO_DEFERRED if defer_means else pos_mode, patch, patch_index, outs, None)
         dloss = dloss.reshape(1).to(torch.float32).contiguous()
         _cabi.call(self.lib, "gcc_nce_backward", ctypes.byref(a), self.ptr(dloss), int(by_mem_row), self.ptr(dq), self.ptr(ws),
                    nbytes, prof.handle if prof else None, stream)

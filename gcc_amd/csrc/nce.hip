@@ -42,6 +42,7 @@ struct NceDev {
     const float *q, *k, *mem, *patch;
     int32_t patch_index, patch_rows, B, K, pos_mode;
     int32_t bf16;            // operands rounded to bf16 (f32 accumulation): gcc_nce_args.dtype
+    int32_t defer;           // the means are formed in the backward call (gcc_nce_args.pos_mode 2; pos_mode here is 0 then)
     float inv_T;
     float *lse, *pos, *loss, *prob, *out_dense;
     int32_t S, R;             // slices and rows per slice (multiple of kChunk)
@@ -350,17 +351,11 @@ __global__ __launch_bounds__(kThreads) void nce_onepass_kernel(NceDev a)
     }
 }
 
-// mean loss / mean positive logit by the workgroup that arrives last, in index order (deterministic); every workgroup has
-// written its lse / pos before it calls this
-__device__ __forceinline__ void nce_mean_by_last(const NceDev &a, double *red, int *last)
+// mean loss / mean positive logit by ONE workgroup, in index order (deterministic), from lse / pos that are visible to it: the
+// workgroup that arrives last (nce_mean_by_last), or a workgroup of a later launch (nce_dq_kernel's extra one)
+__device__ __forceinline__ void nce_means(const NceDev &a, double *red /* [8] */)
 {
     const int tid = (int)threadIdx.x, lane = lane_id(), wv = tid >> 6;
-    device_fence();                                              // lse / pos of this workgroup are visible device wide
-    __syncthreads();
-    if (tid == 0) *last = atomicAdd(a.ticket, 1) == (int)gridDim.x - 1;
-    __syncthreads();
-    if (!*last) return;
-    device_fence();
     double lsum = 0.0, psum = 0.0;
     for (int i = tid; i < a.B; i += kThreads) {
         const float lse = load_fresh(a.lse + i), pos = load_fresh(a.pos + i);
@@ -374,8 +369,21 @@ __device__ __forceinline__ void nce_mean_by_last(const NceDev &a, double *red, i
     if (tid == 0) {
         a.loss[0] = (float)((red[0] + red[1] + red[2] + red[3]) / (double)a.B);    // reduction="mean"
         a.prob[0] = (float)((red[4] + red[5] + red[6] + red[7]) / (double)a.B);    // out[:, 0].mean(), train.py:394
-        *a.ticket = 0;
     }
+}
+
+// nce_means by the workgroup that arrives last; every workgroup has written its lse / pos before it calls this
+__device__ __forceinline__ void nce_mean_by_last(const NceDev &a, double *red, int *last)
+{
+    const int tid = (int)threadIdx.x;
+    device_fence();                                              // lse / pos of this workgroup are visible device wide
+    __syncthreads();
+    if (tid == 0) *last = atomicAdd(a.ticket, 1) == (int)gridDim.x - 1;
+    __syncthreads();
+    if (!*last) return;
+    device_fence();
+    nce_means(a, red);
+    if (tid == 0) *a.ticket = 0;
 }
 
 #ifndef NCE_MERGE_BATCH
@@ -481,27 +489,11 @@ __global__ __launch_bounds__(kThreads) void nce_combine_kernel(NceDev a)
             if (a.pos_mode == 0 && a.out_dense) a.out_dense[(int64_t)b * ld_out] = pos;
         }
     }
-    device_fence();                                              // lse / pos of this workgroup are visible device wide
-    __syncthreads();
-    if (tid == 0) last = atomicAdd(a.ticket, 1) == (int)gridDim.x - 1;
-    __syncthreads();
-    if (!last) return;
-    device_fence();
-    double lsum = 0.0, psum = 0.0;
-    for (int i = tid; i < a.B; i += kThreads) {
-        const float lse = load_fresh(a.lse + i), pos = load_fresh(a.pos + i);
-        lsum += (double)(lse - pos);                             // CrossEntropyLoss row term
-        psum += (double)pos;
-    }
-    lsum = wave_sum(lsum);
-    psum = wave_sum(psum);
-    if (lane == 0) { red[wv] = lsum; red[4 + wv] = psum; }
-    __syncthreads();
-    if (tid == 0) {
-        a.loss[0] = (float)((red[0] + red[1] + red[2] + red[3]) / (double)a.B);    // reduction="mean"
-        a.prob[0] = (float)((red[4] + red[5] + red[6] + red[7]) / (double)a.B);    // out[:, 0].mean(), train.py:394
-        *a.ticket = 0;
-    }
+    // Nothing on the stream reads loss / prob before the step's meters.  Deferred: the kernel ends here and nce_dq_kernel's
+    // extra workgroup forms the two means (the ticket, zeroed by the forward slice kernel, is not touched); otherwise the
+    // workgroup that arrives last does -- a fence, a returning atomic and a second fence behind every workgroup's stores.
+    if (a.defer) return;                                         // (uniform)
+    nce_mean_by_last(a, red, &last);
 }
 
 #ifndef NCE_DQ_BATCH
@@ -510,6 +502,11 @@ __global__ __launch_bounds__(kThreads) void nce_combine_kernel(NceDev a)
 __global__ __launch_bounds__(kThreads) void nce_dq_kernel(NceDev a)
 {
     TRAIN_STEP_WAVE_PRIORITY();
+    __shared__ double red[8];
+    if (a.defer && blockIdx.x == gridDim.x - 1) {              // (block-uniform) the extra workgroup of a deferred head: the means
+        nce_means(a, red);                                       // that nce_combine_kernel left out, beside the 16 that sum the slabs
+        return;
+    }
     const int gid = (int)blockIdx.x * kThreads + (int)threadIdx.x;
     const int b = gid >> 4, c4 = (gid & 15) * 4;
     if (b >= a.B) return;
@@ -731,8 +728,9 @@ __global__ void step_meters_kernel(double *acc, int32_t *mx, const float *loss, 
 
 inline int fill_dev(const gcc_nce_args *a, void *workspace, int64_t workspace_bytes, NceDev &d, Plan &pl)
 {
-    if (!a || !a->q || !a->mem || a->B < 1 || a->K < 1 || (a->pos_mode == 0 && !a->k) ||
-        (a->pos_mode == 1 && a->K < a->B) || !a->lse || !a->pos) {
+    if (!a || !a->q || !a->mem || a->B < 1 || a->K < 1 || (a->pos_mode != 1 && !a->k) ||
+        (a->pos_mode == 1 && a->K < a->B) || !a->lse || !a->pos || a->pos_mode < 0 || a->pos_mode > GCC_NCE_POS_MOCO_DEFERRED ||
+        (a->pos_mode == GCC_NCE_POS_MOCO_DEFERRED && (!a->loss || !a->prob || a->out_dense))) {
         snprintf(g_err, kErrLen, "gcc_nce: bad argument");
         return -1;
     }
@@ -743,7 +741,8 @@ inline int fill_dev(const gcc_nce_args *a, void *workspace, int64_t workspace_by
     }
     d.q = a->q; d.k = a->k; d.mem = a->mem; d.patch = a->patch;
     d.patch_index = a->patch_index; d.patch_rows = a->patch ? a->patch_rows : 0;
-    d.B = a->B; d.K = a->K; d.pos_mode = a->pos_mode; d.inv_T = a->inv_T;
+    d.defer = a->pos_mode == GCC_NCE_POS_MOCO_DEFERRED ? 1 : 0;
+    d.B = a->B; d.K = a->K; d.pos_mode = d.defer ? 0 : a->pos_mode; d.inv_T = a->inv_T;
     d.bf16 = a->dtype == GCC_NCE_BF16 ? 1 : 0;
     d.lse = a->lse; d.pos = a->pos; d.loss = a->loss; d.prob = a->prob; d.out_dense = a->out_dense;
     d.S = pl.S; d.R = pl.R;
@@ -798,7 +797,7 @@ int32_t gcc_nce_backward(const gcc_nce_args *a, const float *dloss, int32_t by_m
     prof_mark(prof, 0, s);
     if (d.bf16) hipLaunchKernelGGL((nce_slice_kernel<true, true>), dim3(pl.S, pl.QB), dim3(kThreads), 0, s, d);
     else hipLaunchKernelGGL((nce_slice_kernel<true, false>), dim3(pl.S, pl.QB), dim3(kThreads), 0, s, d);
-    hipLaunchKernelGGL(nce_dq_kernel, dim3((a->B * 16 + kThreads - 1) / kThreads), dim3(kThreads), 0, s, d);
+    hipLaunchKernelGGL(nce_dq_kernel, dim3((a->B * 16 + kThreads - 1) / kThreads + d.defer), dim3(kThreads), 0, s, d);
     prof_mark(prof, 1, s);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) { snprintf(g_err, kErrLen, "gcc_nce_backward: %s", hipGetErrorString(e)); return -10; }

@@ -867,9 +867,13 @@ class MoCoTrainStep(_GraphedStep):
                 S["outs"], dq = self.nce.forward_backward(feat_q, feat_k, mem, c.T, self.one, stream=st,
                                                           prof_fwd=pr.get("nce_fwd"), prof_bwd=pr.get("nce_bwd"))
             else:
-                S["outs"] = self.nce.forward(feat_q, feat_k, mem, c.T, 0, stream=st, prof=pr.get("nce_fwd"))   # train.py:393,407
+                # loss / prob are read by the meters only (in or after the Adam launch): on the f32 head the backward call's
+                # last launch forms them, and the forward call ends without its arrival counter (bf16 keeps it)
+                defer = self.nce.dtype == "f32"
+                S["outs"] = self.nce.forward(feat_q, feat_k, mem, c.T, 0, stream=st, prof=pr.get("nce_fwd"),
+                                             defer_means=defer)                   # train.py:393,407
                 dq = self.nce.backward(feat_q, feat_k, mem, c.T, 0, S["outs"], self.one, stream=st,
-                                       prof=pr.get("nce_bwd"))                    # loss.backward(), train.py:408
+                                       prof=pr.get("nce_bwd"), defer_means=defer) # loss.backward(), train.py:408
             kw = {} if self.wide else dict(prof=pr.get("gin_bwd"))
             if self.fold and scalars is not None and not self.collectives:
                 # nothing touches the gradient between the backward's last kernel and Adam: its sum of squares is taken there

@@ -591,7 +591,8 @@ typedef struct gcc_nce_args {
     int32_t patch_index;     /*   mem are read from here (queue rows already overwritten by the */
     int32_t patch_rows;      /*   enqueue that follows the forward, memory_moco.py:55-61)       */
     int32_t B, K;
-    int32_t pos_mode;        /* 0: MoCo, 1: E2E diagonal                                        */
+    int32_t pos_mode;        /* 0: MoCo, 1: E2E diagonal, GCC_NCE_POS_MOCO_DEFERRED: MoCo whose  */
+                             /*   two means are formed by the backward call (below)             */
     float inv_T;             /* 1 / nce_t (train.py:87)                                         */
     float *lse, *pos;        /* device [B] out: row log-sum-exp and positive logit               */
     float *loss, *prob;      /* device [1] out: mean(lse - pos) and mean(pos) (train.py:394,407) */
@@ -603,6 +604,10 @@ typedef struct gcc_nce_args {
 } gcc_nce_args;
 #define GCC_NCE_F32 0
 #define GCC_NCE_BF16 1
+/* pos_mode of a MoCo head (out_dense NULL) whose caller reads loss / prob only after the backward call: gcc_nce_forward ends
+ * with lse / pos -- no arrival counter, no last workgroup -- and gcc_nce_backward's last launch forms loss[0] and prob[0] in
+ * one extra workgroup, with the additions of pos_mode 0 in their order (the same bits).  Both calls take the same args. */
+#define GCC_NCE_POS_MOCO_DEFERRED 2
 
 int64_t gcc_nce_workspace_bytes(int32_t B, int32_t K);
 int32_t gcc_nce_forward(const gcc_nce_args *a, void *workspace, int64_t workspace_bytes, gcc_prof *prof,

@@ -1,0 +1,13 @@
+"""The backward tail's degree-embedding gradient on the device: tests/bwd_tail_check.py's cases against the fixed tree over the
+partial tables, float64 sums and, bit for bit, the recording of this tier (tests/golden/bwd_tail_bits_gpu.npz)."""
+import pytest
+
+from tests import bwd_tail_check as C
+from tests import gather_ring_check as K
+
+pytestmark = pytest.mark.gpu
+
+
+@pytest.mark.parametrize("name", list(C.cases()))
+def test_bwd_tail_case_on_the_device(name):
+    C.check_case(K.Tier("gpu"), name)
