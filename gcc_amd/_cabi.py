@@ -625,6 +625,18 @@ SIGNATURES = {
     "gcc_adam_clipvalue_step": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                                  ctypes.c_int64, ctypes.c_float, ctypes.c_float, ctypes.c_float, ctypes.c_float,
                                                  ctypes.c_float, ctypes.c_int32, ctypes.c_float, ctypes.c_float, ctypes.c_void_p]),
+    # rule, param, grad, state, n, lr, hyper, weight_decay, max_norm, grad_scale, grad_norm, scratch, [ema, n_ema, ema_m, meters,] stream
+    "gcc_opt_step": (ctypes.c_int32, [ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64] +
+                     [ctypes.c_float] * 5 + [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    "gcc_opt_ema_step": (ctypes.c_int32, [ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64] +
+                         [ctypes.c_float] * 5 + [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_float,
+                                                 ctypes.POINTER(GccStepMetersArgs), ctypes.c_void_p]),
+    "gcc_opt_ema_step_scalars": (ctypes.c_int32, [ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64] +
+                                 [ctypes.c_float] * 4 + [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64,
+                                                         ctypes.c_float, ctypes.POINTER(GccStepMetersArgs), ctypes.c_void_p,
+                                                         ctypes.c_void_p]),
+    "gcc_opt_clipvalue_step": (ctypes.c_int32, [ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64] +
+                               [ctypes.c_float] * 5 + [ctypes.c_void_p]),
     "gcc_pack_graphs": (ctypes.c_int32, [ctypes.POINTER(GccGraphCorpus), ctypes.c_void_p, ctypes.c_int32,
                                          ctypes.POINTER(GccBatchOut), ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                          ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p]),

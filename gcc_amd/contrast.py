@@ -181,6 +181,29 @@ class NceEngine:
                    self.ptr(ema) if ema is not None else None, ema.numel() if ema is not None else 0,
                    float(ema_m), ctypes.byref(ma) if ma is not None else None, stream)
 
+    def opt_step(self, rule, param, grad, state, lr, hyper, weight_decay, max_norm, grad_norm, scratch, stream=None,
+                 grad_scale=1.0, ema=None, ema_src=None, ema_m=0.0, meters=None, scalars=None):
+        """gcc_opt_step / gcc_opt_ema_step[_scalars]: :meth:`adam` / :meth:`adam_ema` with SGD's (``rule`` 1: ``state`` the
+        momentum buffer, ``hyper`` the momentum) or Adagrad's (2: the sum of squares, eps; ``lr`` = the step's clr) update."""
+        head = (int(rule), self.ptr(param), self.ptr(grad), self.ptr(state), param.numel())
+        mid = (float(hyper), float(weight_decay), float(max_norm), float(grad_scale), self.ptr(grad_norm), self.ptr(scratch))
+        if ema is None and meters is None and scalars is None:
+            _cabi.call(self.lib, "gcc_opt_step", *head, float(lr), *mid, stream)
+            return
+        ma = None
+        if meters is not None:
+            acc, mx, loss, prob, q, k = meters
+            ma = _cabi.GccStepMetersArgs(self.ptr(acc), self.ptr(mx), self.ptr(loss), self.ptr(prob), self.ptr(q.node_off),
+                                         self.ptr(q.edge_off), self.ptr(k.node_off), int(q.batch_size))
+        if ema is not None and (ema_src is None or ema_src.data_ptr() != param.data_ptr() or ema.numel() != ema_src.numel()):
+            raise ValueError("opt_step: param must be a prefix of ema_src, and ema the same size as ema_src")
+        tail = (self.ptr(ema) if ema is not None else None, ema.numel() if ema is not None else 0, float(ema_m),
+                ctypes.byref(ma) if ma is not None else None)
+        if scalars is not None:                      # the rate from the device struct (replayed step)
+            _cabi.call(self.lib, "gcc_opt_ema_step_scalars", *head, *mid, *tail, self.ptr(scalars), stream)
+        else:
+            _cabi.call(self.lib, "gcc_opt_ema_step", *head, float(lr), *mid, *tail, stream)
+
     def meters(self, acc, mx, loss, prob, grad_norm, q, k, stream=None):
         _cabi.call(self.lib, "gcc_step_meters", self.ptr(acc), self.ptr(mx), self.ptr(loss), self.ptr(prob), self.ptr(grad_norm),
                    self.ptr(q.node_off), self.ptr(q.edge_off), self.ptr(k.node_off),

@@ -709,6 +709,96 @@ __global__ __launch_bounds__(kThreads) void adam_kernel(float *p, float *g, floa
     }
 }
 
+// ---- --optimizer sgd / adagrad (train.py:658-679) over the same flat buffers: adam_kernel's unfolded tail (the sum of squares
+// from a gradnorm_kernel launch; the enqueue stays a launch of its own) with torch.optim.SGD's / torch.optim.Adagrad's update.
+// ``s``: the momentum buffer / the sum of squared gradients; ``hyper``: the momentum / eps; ``lr``: Adagrad's clr of this step
+// (lr / (1 + (t - 1) lr_decay), formed by the host in double as torch forms it).  x.parts / x.q_mem are not used here.
+template <int kRule>
+__device__ __forceinline__ float opt_update(float p0, float gc, float s0, float lr, float hyper, float wd, float &s1)
+{
+    const float gi = fmaf(wd, p0, gc);                         // weight_decay: grad = grad + wd * param (after the clip, as torch)
+    if (kRule == GCC_OPT_SGD) {
+        s1 = fmaf(hyper, s0, gi);                              // buf.mul_(momentum).add_(grad); buf = 0 gives torch's first step
+        return fmaf(-lr, s1, p0);                              // param.add_(buf, alpha=-lr)
+    }
+    s1 = fmaf(gi, gi, s0);                                     // state_sum.addcmul_(grad, grad)
+    return p0 - lr * gi / (sqrtf(s1) + hyper);                 // param.addcdiv_(grad, sqrt(sum) + eps, value=-clr): 0 / eps = 0
+}
+
+template <int kRule>
+__global__ __launch_bounds__(kThreads) void opt_kernel(float *p, float *g, float *s, int64_t n, float lr, float hyper, float wd,
+                                                       float max_norm, float grad_scale, const double *sumsq, float *grad_norm,
+                                                       AdamExtras x)
+{
+    TRAIN_STEP_WAVE_PRIORITY();
+    const double ss = sumsq[0];
+    if (x.sc) lr = x.sc->lr;                                   // (uniform: one scalar load, in flight with the rest)
+    // this thread's first element rides in the same round trip as the norm
+    const int64_t stride = (int64_t)gridDim.x * kThreads, i0 = (int64_t)blockIdx.x * kThreads + threadIdx.x;
+    const int64_t ic = i0 < n ? i0 : n - 1;
+    float g0 = g[ic], p0 = p[ic], s0 = s[ic];
+    const float e0 = x.ema ? x.ema[i0 < x.n_ema ? i0 : x.n_ema - 1] : 0.f;      // (block-uniform branch)
+    const float norm = grad_scale * (float)sqrt(ss);
+    float coef = 1.f;
+    if (max_norm > 0.f) {                                      // torch.nn.utils.clip_grad_norm_
+        coef = max_norm / (norm + 1e-6f);
+        coef = coef > 1.f ? 1.f : coef;
+    }
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        grad_norm[0] = norm;
+        if (x.acc) {                                           // train.py:418-428's meters (gcc_step_meters)
+            const int32_t nq = x.node_off_q[x.B], nk = x.node_off_k[x.B], eq = x.edge_off_q[x.B];
+            x.acc[0] += (double)x.loss[0];
+            x.acc[1] += (double)x.prob[0];
+            x.acc[2] += (double)norm;
+            x.acc[3] += (double)nq + (double)nk;
+            x.acc[4] += 1.0;
+            x.mx[0] = nq > x.mx[0] ? nq : x.mx[0];
+            x.mx[1] = eq > x.mx[1] ? eq : x.mx[1];
+        }
+    }
+    coef *= grad_scale;
+    const int64_t nmax = x.ema && x.n_ema > n ? x.n_ema : n;
+    for (int64_t i = i0; i < nmax; i += stride) {
+        float pi, ei = 0.f;
+        if (i != i0) {
+            const int64_t j = i < n ? i : n - 1;
+            g0 = g[j]; p0 = p[j]; s0 = s[j];
+            if (x.ema) ei = x.ema[i < x.n_ema ? i : x.n_ema - 1];
+        } else {
+            ei = e0;
+        }
+        if (i < n) {
+            const float gc = g0 * coef;
+            g[i] = gc;                                         // the clipped gradient stays visible, as in torch
+            float si;
+            pi = opt_update<kRule>(p0, gc, s0, lr, hyper, wd, si);
+            s[i] = si;
+            p[i] = pi;
+        } else {
+            pi = p[i];                                         // parameters past the live prefix: only averaged
+        }
+        if (x.ema && i < x.n_ema) x.ema[i] = ei * x.ema_m + (1.f - x.ema_m) * pi;   // p2.mul_(m).add_(1 - m, p1), train.py:169-172
+    }
+}
+
+// clip_grad_value_ + the same two rules: the fine-tuning tail (gcc_adam_clipvalue_step's twin), one launch, no norm pass
+template <int kRule>
+__global__ __launch_bounds__(kThreads) void opt_clipvalue_kernel(float *p, float *g, float *s, int64_t n, float lr, float hyper,
+                                                                 float wd, float clip, float grad_scale)
+{
+    TRAIN_STEP_WAVE_PRIORITY();
+    const int64_t stride = (int64_t)gridDim.x * kThreads;
+    for (int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x; i < n; i += stride) {
+        float gc = g[i] * grad_scale;
+        if (clip > 0.f) gc = gc < -clip ? -clip : (gc > clip ? clip : gc);   // clip_grad_value_ (NaN passes, as clamp_)
+        g[i] = gc;                                           // the clipped gradient stays visible, as in torch
+        float si;
+        p[i] = opt_update<kRule>(p[i], gc, s[i], lr, hyper, wd, si);
+        s[i] = si;
+    }
+}
+
 // ---- per-step meters of train.py:418-428 (loss / prob / gnorm / graph sizes) accumulated on the device: one thread
 __global__ void step_meters_kernel(double *acc, int32_t *mx, const float *loss, const float *prob, const float *gnorm,
                                    const int32_t *node_off_q, const int32_t *edge_off_q, const int32_t *node_off_k,
@@ -1015,6 +1105,97 @@ int32_t gcc_adam_ema_enqueue_step_scalars(float *param, float *grad, float *exp_
     const AdamFold fold = {sumsq_parts, nparts, queue, keys, K, nkeys};
     return adam_ema_launch(who, param, grad, exp_avg, exp_avg_sq, n, 0.f, beta1, beta2, eps, weight_decay, 0, max_norm, grad_scale,
                            grad_norm, scratch, ema, n_ema, ema_m, meters, scalars, stream, &fold);
+}
+
+static int32_t opt_check(const char *who, int32_t rule, const float *param, const float *grad, const float *state, int64_t n,
+                         float grad_scale)
+{
+    if (rule != GCC_OPT_SGD && rule != GCC_OPT_ADAGRAD) {
+        snprintf(g_err, kErrLen, "%s: unknown rule %d (GCC_OPT_SGD = 1, GCC_OPT_ADAGRAD = 2)", who, rule);
+        return -2;
+    }
+    if (n < 1) { snprintf(g_err, kErrLen, "%s: n = %lld, at least one element is needed", who, (long long)n); return -1; }
+    if (!param || !grad || !state) {
+        snprintf(g_err, kErrLen, "%s: %s is NULL", who, !param ? "param" : !grad ? "grad" : "state");
+        return -1;
+    }
+    if (!(grad_scale > 0.f)) { snprintf(g_err, kErrLen, "%s: grad_scale must be positive", who); return -1; }
+    return 0;
+}
+
+static int32_t opt_launch(const char *who, int32_t rule, float *param, float *grad, float *state, int64_t n, float lr, float hyper,
+                          float weight_decay, float max_norm, float grad_scale, float *grad_norm, double *scratch, float *ema,
+                          int64_t n_ema, float ema_m, const gcc_step_meters_args *meters, const gcc_step_scalars *scalars,
+                          void *stream)
+{
+    const int32_t rc = opt_check(who, rule, param, grad, state, n, grad_scale);
+    if (rc) return rc;
+    if (!grad_norm || !scratch || (ema && n_ema < n) ||
+        (meters && (!meters->acc || !meters->mx || !meters->loss || !meters->prob || !meters->node_off_q ||
+                    !meters->edge_off_q || !meters->node_off_k || meters->batch_size < 1))) {
+        snprintf(g_err, kErrLen, "%s: bad argument (grad_norm / scratch NULL, n_ema < n, or an incomplete meters struct)", who);
+        return -1;
+    }
+    hipStream_t s = (hipStream_t)stream;
+    hipLaunchKernelGGL(gradnorm_kernel, dim3(kNormBlocks), dim3(kThreads), 0, s, (const float *)grad, n, scratch);
+    AdamExtras x = {};
+    x.sc = scalars;
+    if (ema) { x.ema = ema; x.n_ema = n_ema; x.ema_m = ema_m; }
+    if (meters) {
+        x.acc = meters->acc; x.mx = meters->mx; x.loss = meters->loss; x.prob = meters->prob;
+        x.node_off_q = meters->node_off_q; x.edge_off_q = meters->edge_off_q; x.node_off_k = meters->node_off_k;
+        x.B = meters->batch_size;
+    }
+    const int64_t nmax = ema ? n_ema : n;
+    int blocks = (int)((nmax + kThreads - 1) / kThreads);
+    if (blocks > 512) blocks = 512;
+    if (rule == GCC_OPT_SGD)
+        hipLaunchKernelGGL(opt_kernel<GCC_OPT_SGD>, dim3(blocks), dim3(kThreads), 0, s, param, grad, state, n, lr, hyper, weight_decay,
+                           max_norm, grad_scale, (const double *)scratch, grad_norm, x);
+    else
+        hipLaunchKernelGGL(opt_kernel<GCC_OPT_ADAGRAD>, dim3(blocks), dim3(kThreads), 0, s, param, grad, state, n, lr, hyper,
+                           weight_decay, max_norm, grad_scale, (const double *)scratch, grad_norm, x);
+    return hipGetLastError() == hipSuccess ? 0 : -10;
+}
+
+int32_t gcc_opt_step(int32_t rule, float *param, float *grad, float *state, int64_t n, float lr, float hyper, float weight_decay,
+                     float max_norm, float grad_scale, float *grad_norm, double *scratch, void *stream)
+{
+    return opt_launch("gcc_opt_step", rule, param, grad, state, n, lr, hyper, weight_decay, max_norm, grad_scale, grad_norm, scratch,
+                      nullptr, 0, 0.f, nullptr, nullptr, stream);
+}
+
+int32_t gcc_opt_ema_step(int32_t rule, float *param, float *grad, float *state, int64_t n, float lr, float hyper, float weight_decay,
+                         float max_norm, float grad_scale, float *grad_norm, double *scratch, float *ema, int64_t n_ema, float ema_m,
+                         const gcc_step_meters_args *meters, void *stream)
+{
+    return opt_launch("gcc_opt_ema_step", rule, param, grad, state, n, lr, hyper, weight_decay, max_norm, grad_scale, grad_norm,
+                      scratch, ema, n_ema, ema_m, meters, nullptr, stream);
+}
+
+int32_t gcc_opt_ema_step_scalars(int32_t rule, float *param, float *grad, float *state, int64_t n, float hyper, float weight_decay,
+                                 float max_norm, float grad_scale, float *grad_norm, double *scratch, float *ema, int64_t n_ema,
+                                 float ema_m, const gcc_step_meters_args *meters, const gcc_step_scalars *scalars, void *stream)
+{
+    if (!scalars) { snprintf(g_err, kErrLen, "gcc_opt_ema_step_scalars: scalars is NULL"); return -1; }
+    return opt_launch("gcc_opt_ema_step_scalars", rule, param, grad, state, n, 0.f, hyper, weight_decay, max_norm, grad_scale,
+                      grad_norm, scratch, ema, n_ema, ema_m, meters, scalars, stream);
+}
+
+int32_t gcc_opt_clipvalue_step(int32_t rule, float *param, float *grad, float *state, int64_t n, float lr, float hyper,
+                               float weight_decay, float clip_value, float grad_scale, void *stream)
+{
+    const int32_t rc = opt_check("gcc_opt_clipvalue_step", rule, param, grad, state, n, grad_scale);
+    if (rc) return rc;
+    int blocks = (int)((n + kThreads - 1) / kThreads);
+    if (blocks > 512) blocks = 512;
+    if (rule == GCC_OPT_SGD)
+        hipLaunchKernelGGL(opt_clipvalue_kernel<GCC_OPT_SGD>, dim3(blocks), dim3(kThreads), 0, (hipStream_t)stream, param, grad, state,
+                           n, lr, hyper, weight_decay, clip_value, grad_scale);
+    else
+        hipLaunchKernelGGL(opt_clipvalue_kernel<GCC_OPT_ADAGRAD>, dim3(blocks), dim3(kThreads), 0, (hipStream_t)stream, param, grad,
+                           state, n, lr, hyper, weight_decay, clip_value, grad_scale);
+    return hipGetLastError() == hipSuccess ? 0 : -10;
 }
 
 int32_t gcc_step_meters(double *acc, int32_t *mx, const float *loss, const float *prob, const float *grad_norm,

@@ -8,6 +8,8 @@
 No host synchronisation inside a step: loss, correct predictions and graph sizes are accumulated on the device (the head's
 launch updates the meters) and read when a log line is due.  The reference's two torch.optim.Adam (encoder and output layer,
 same hyperparameters, same step count) are two launches over two flat buffers.
+``--optimizer sgd`` / ``adagrad`` (with ``--step-path fused``) select the ENCODER's rule (gcc_opt_clipvalue_step, one launch as well);
+the output layer's optimizer stays Adam, as in the reference (train.py:645-650).
 """
 from __future__ import annotations
 
@@ -19,7 +21,7 @@ import torch.nn as nn
 
 from . import _cabi
 from .encoder import H
-from .train_step import flat_grad_views, flatten_parameters
+from .train_step import OPT_RULES, FlatRuleState, flat_grad_views, flatten_parameters
 
 
 class ClsHeadEngine:
@@ -72,6 +74,12 @@ class ClsHeadEngine:
                    param.numel(), lr, betas[0], betas[1], eps, weight_decay, int(step),
                    clip_value, grad_scale, stream)
 
+    def opt_clipvalue(self, rule, param, grad, state, lr, hyper, weight_decay, clip_value, grad_scale=1.0, stream=None):
+        """gcc_opt_clipvalue_step: ``rule`` 1 = SGD (``state`` the momentum buffer, ``hyper`` the momentum), 2 = Adagrad (the sum
+        of squares, eps; ``lr`` = the step's clr)"""
+        _cabi.call(self.lib, "gcc_opt_clipvalue_step", int(rule), self.ptr(param), self.ptr(grad), self.ptr(state), param.numel(),
+                   lr, hyper, weight_decay, clip_value, grad_scale, stream)
+
 
 class FlatAdamClipValue:
     """clip_grad_value_(params, clip_value) + torch.optim.Adam(lr, betas, eps=1e-8, weight_decay) over one flat buffer
@@ -97,6 +105,33 @@ class FlatAdamClipValue:
     def state_dict(self):
         return dict(state=dict(step=self.steps, exp_avg=self.exp_avg, exp_avg_sq=self.exp_avg_sq),
                     param_groups=self.param_groups)
+
+
+class _FlatClipValue(FlatRuleState):
+    """clip_grad_value_(params, clip_value) + the rule's update over one flat buffer, one launch (gcc_opt_clipvalue_step)"""
+
+    def __init__(self, rule, param, grad, lr, weight_decay, clip_value, engine, **hyper):
+        super().__init__(rule, param, grad, lr, weight_decay, engine, **hyper)
+        self.clip_value = clip_value
+
+    def step(self, stream=None):
+        self.steps += 1
+        self.engine.opt_clipvalue(OPT_RULES[self.rule], self.param, self.grad, self.state, self.rate(self.steps), self.hyper(),
+                                  self.param_groups[0]["weight_decay"], self.clip_value, stream=stream)
+
+
+class FlatSGDClipValue(_FlatClipValue):
+    """clip_grad_value_ + torch.optim.SGD(lr, momentum, weight_decay) (train.py:232-246,658-666 of the reference)"""
+
+    def __init__(self, param, grad, lr, momentum, weight_decay, clip_value, engine):
+        super().__init__("sgd", param, grad, lr, weight_decay, clip_value, engine, momentum=momentum)
+
+
+class FlatAdagradClipValue(_FlatClipValue):
+    """clip_grad_value_ + torch.optim.Adagrad(lr, lr_decay, weight_decay) (train.py:232-246,673-679 of the reference)"""
+
+    def __init__(self, param, grad, lr, lr_decay, weight_decay, clip_value, engine, eps=1e-10):
+        super().__init__("adagrad", param, grad, lr, weight_decay, clip_value, engine, lr_decay=lr_decay, eps=eps)
 
 
 def clear_bn(model):
@@ -131,11 +166,12 @@ def _meter_buffers(dev):
 
 class FinetuneTrainStep:
     """One step of train_finetune (train.py:204-246 of the reference) as a fixed sequence of launches on the step stream.
-    ``model`` must be a GraphEncoder served by the fused 64-channel kernels (hidden size up to 64); wider models and the
-    SGD / Adagrad optimizers take the API path (:func:`api_step`)."""
+    ``model`` must be a GraphEncoder served by the fused 64-channel kernels (hidden size up to 64); wider models
+    take the API path (:func:`api_step`).  ``optimizer``: the ENCODER's -- "adam", "sgd" (``momentum``) or "adagrad"
+    (``lr_decay``); the head's stays Adam, as in the reference (train.py:645-650)."""
 
     def __init__(self, model, head: nn.Linear, learning_rate=0.005, betas=(0.9, 0.999), weight_decay=1e-5, clip_value=1.0,
-                 engine=None):
+                 engine=None, optimizer="adam", momentum=0.9, lr_decay=0.0):
         if model.wide:
             raise NotImplementedError("the fused fine-tuning step runs the 64-channel kernels; wider models take the API path")
         self.model, self.head = model, head
@@ -146,7 +182,14 @@ class FinetuneTrainStep:
         self.hflat, self.hgrad, self.dW, self.db = flatten_head(head)
         self.gin = model.engine()
         self.eng = engine if engine is not None else ClsHeadEngine()
-        self.optimizer = FlatAdamClipValue(self.live, self.flat_grad, learning_rate, betas, weight_decay, clip_value, self.eng)
+        if optimizer == "adam":
+            self.optimizer = FlatAdamClipValue(self.live, self.flat_grad, learning_rate, betas, weight_decay, clip_value, self.eng)
+        elif optimizer == "sgd":
+            self.optimizer = FlatSGDClipValue(self.live, self.flat_grad, learning_rate, momentum, weight_decay, clip_value, self.eng)
+        elif optimizer == "adagrad":
+            self.optimizer = FlatAdagradClipValue(self.live, self.flat_grad, learning_rate, lr_decay, weight_decay, clip_value, self.eng)
+        else:
+            raise ValueError(f"unknown optimizer {optimizer!r} (adam, sgd, adagrad)")
         self.head_optimizer = FlatAdamClipValue(self.hflat, self.hgrad, learning_rate, betas, weight_decay, clip_value, self.eng)
         self.mask_fn = None          # tests inject explicit dropout keep-masks [L + 1, B, 64] here; default = in-kernel Philox
         self.dropout_seed = 0x5EED1000

@@ -32,7 +32,8 @@ def apply_resume(args, checkpoint_opt):
     """train.py:487-505: the checkpoint's options, with these of the command line"""
     pretrain_args = checkpoint_opt
     for name in ("fold_idx", "gpu", "finetune", "resume", "cv", "dataset", "epochs", "num_workers", "batch_size",
-                 "edgelist", "nodelabel", "tudataset", "graphs_npz", "edge_multiplicity", "no_prefetch", "graph_batcher", "tu_parse"):
+                 "edgelist", "nodelabel", "tudataset", "graphs_npz", "edge_multiplicity", "no_prefetch", "graph_batcher", "tu_parse",
+                 "step_path"):
         setattr(pretrain_args, name, getattr(args, name, None))
     if args.dataset in GRAPH_CLASSIFICATION_DSETS:
         pretrain_args.num_workers = 0           # train.py:500-502
@@ -102,10 +103,14 @@ def _summary_writer(folder):
 def main_finetune(args, option_update):
     from .encoder import encoder_from_opt
     from .finetune import FinetuneTrainStep, LabeledProducer, clear_bn, cls_head_loss, evaluate
-    from .train_step import flatten_parameters
+    from .train_step import flatten_parameters, resolve_step_path
 
     if int(os.environ.get("WORLD_SIZE", "1")) > 1:
         raise NotImplementedError("--finetune runs on one GPU (the reference's fine-tuning is single-GPU)")
+    args.step_path = step_path = getattr(args, "step_path", "auto")
+    if not args.resume:                                             # refusals before any device work
+        resolve_step_path(step_path, optimizer=args.optimizer, gat=args.model == "gat", wide=args.hidden_size > 64, moco=False,
+                          finetune=True)
     np.random.seed(args.seed)                                       # train.py:482-485
     torch.manual_seed(args.seed)
     torch.cuda.manual_seed(args.seed)
@@ -133,7 +138,8 @@ def main_finetune(args, option_update):
 
     contrast = MemoryMoCo(args.hidden_size, None, args.nce_k, args.nce_t, use_softmax=True).to(dev)   # (checkpointed only)
     output_layer = nn.Linear(in_features=args.hidden_size, out_features=dataset.num_classes).to(dev)  # train.py:637-646
-    fused = args.optimizer == "adam" and not model.wide and model.gnn_model == "gin"
+    fused = resolve_step_path(step_path, optimizer=args.optimizer, gat=model.gnn_model != "gin", wide=model.wide, moco=False,
+                              finetune=True) == "fused"
     if fused:
         flatten_parameters(model)
     clear_bn(model)                                                 # train.py:651-655 (before the resume, as there)
@@ -146,9 +152,10 @@ def main_finetune(args, option_update):
         torch.cuda.empty_cache()
     if fused:
         trainer = FinetuneTrainStep(model, output_layer, learning_rate=args.learning_rate, betas=(args.beta1, args.beta2),
-                                    weight_decay=args.weight_decay, clip_value=1.0)
+                                    weight_decay=args.weight_decay, clip_value=1.0, optimizer=args.optimizer,
+                                    momentum=args.momentum, lr_decay=args.lr_decay_rate)
         optimizer, head_optimizer = trainer.optimizer, trainer.head_optimizer
-    else:                                                           # API path: SGD / Adagrad, wide and GAT models (train.py:658-679)
+    else:                                                           # API path: wide and GAT models, SGD / Adagrad by default (train.py:658-679)
         trainer = None
         head_optimizer = torch.optim.Adam(output_layer.parameters(), lr=args.learning_rate, betas=(args.beta1, args.beta2),
                                           weight_decay=args.weight_decay)

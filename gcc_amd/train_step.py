@@ -365,6 +365,120 @@ class FlatAdam:
         return dict(state=dict(step=self.steps, exp_avg=self.exp_avg, exp_avg_sq=self.exp_avg_sq),
                     param_groups=self.param_groups)
 
+    def ring_scalars(self, lr):
+        """(rate, betas) of the NEXT step's entry in the scalars ring (:meth:`_GraphedStep._run_step`)"""
+        return lr, self.param_groups[0]["betas"]
+
+
+OPT_RULES = {"sgd": 1, "adagrad": 2}        # GCC_OPT_SGD, GCC_OPT_ADAGRAD
+
+
+class FlatRuleState:
+    """What ``--optimizer sgd`` / ``adagrad`` (train.py:658-679) keep over one flat parameter buffer, whichever clip runs in
+    front: ``param_groups[0]`` in torch's shape (train.py sets ``["lr"]`` every step), ONE state tensor -- SGD's momentum buffer
+    or Adagrad's sum of squared gradients, both starting at 0: a zero buffer gives torch's first SGD step (buf = g) -- and the
+    host's step count.  Adagrad's rate of step t, clr = lr / (1 + (t - 1) lr_decay), is formed here in double, as torch forms it,
+    and handed to the kernel where Adam's lr goes."""
+
+    def __init__(self, rule, param, grad, lr, weight_decay, engine, momentum=0.0, lr_decay=0.0, eps=1e-10):
+        self.rule, self.param, self.grad, self.engine = rule, param, grad, engine
+        if rule == "sgd":                       # torch.optim.SGD(lr, momentum, weight_decay): dampening 0, no Nesterov
+            self.param_groups = [dict(lr=lr, momentum=momentum, weight_decay=weight_decay)]
+            self.state_key = "momentum_buffer"
+        elif rule == "adagrad":                 # torch.optim.Adagrad(lr, lr_decay, weight_decay): accumulator from 0
+            self.param_groups = [dict(lr=lr, lr_decay=lr_decay, eps=eps, weight_decay=weight_decay)]
+            self.state_key = "sum"
+        else:
+            raise ValueError(f"unknown update rule {rule!r} (sgd, adagrad)")
+        self.state = torch.zeros_like(param)
+        self.steps = 0
+
+    def rate(self, t):
+        """the effective learning rate of step ``t`` (1-based)"""
+        g = self.param_groups[0]
+        return g["lr"] if self.rule == "sgd" else g["lr"] / (1 + (t - 1) * g["lr_decay"])
+
+    def hyper(self):
+        g = self.param_groups[0]
+        return g["momentum"] if self.rule == "sgd" else g["eps"]
+
+    def ring_scalars(self, lr):
+        return self.rate(self.steps + 1), (0.0, 0.0)       # (lr is in param_groups already; no bias corrections)
+
+    def zero_grad(self):
+        pass                 # the backward kernels overwrite the flat gradient
+
+    def state_dict(self):
+        return dict(state={"step": self.steps, self.state_key: self.state}, param_groups=self.param_groups)
+
+
+class _FlatClipNorm(FlatRuleState):
+    """clip_grad_norm_ + the rule's update as two HIP launches (gcc_opt_step / gcc_opt_ema_step[_scalars]): :class:`FlatAdam`'s
+    ``step`` signature without the folded single-GPU tail (the sum of squares stays a launch, the enqueue too)."""
+
+    def __init__(self, rule, param, grad, lr, weight_decay, clip_norm, engine, **hyper):
+        super().__init__(rule, param, grad, lr, weight_decay, engine, **hyper)
+        self.clip_norm = clip_norm
+        self.grad_norm = torch.zeros(1, dtype=torch.float32, device=param.device)
+        self._scratch = torch.zeros(64, dtype=torch.float64, device=param.device)
+
+    def step(self, grad_scale=1.0, ema=None, ema_src=None, ema_m=0.0, meters=None, scalars=None):
+        self.steps += 1
+        self.engine.opt_step(OPT_RULES[self.rule], self.param, self.grad, self.state, self.rate(self.steps), self.hyper(),
+                             self.param_groups[0]["weight_decay"], self.clip_norm, self.grad_norm, self._scratch,
+                             stream=raw_stream(self.param), grad_scale=grad_scale, ema=ema, ema_src=ema_src, ema_m=ema_m,
+                             meters=meters, scalars=scalars)
+        return self.grad_norm
+
+
+class FlatSGD(_FlatClipNorm):
+    """clip_grad_norm_ + torch.optim.SGD(lr, momentum, weight_decay) (train.py:409,658-666) over one flat buffer"""
+
+    def __init__(self, param, grad, lr, momentum, weight_decay, clip_norm, engine):
+        super().__init__("sgd", param, grad, lr, weight_decay, clip_norm, engine, momentum=momentum)
+
+
+class FlatAdagrad(_FlatClipNorm):
+    """clip_grad_norm_ + torch.optim.Adagrad(lr, lr_decay, weight_decay) (train.py:409,673-679) over one flat buffer"""
+
+    def __init__(self, param, grad, lr, lr_decay, weight_decay, clip_norm, engine, eps=1e-10):
+        super().__init__("adagrad", param, grad, lr, weight_decay, clip_norm, engine, lr_decay=lr_decay, eps=eps)
+
+
+def flat_optimizer(name, param, grad, lr, betas, weight_decay, clip_norm, engine, momentum=0.9, lr_decay=0.0):
+    """the clip-by-norm flat optimizer of ``--optimizer name``"""
+    if name == "adam":
+        return FlatAdam(param, grad, lr, betas, weight_decay, clip_norm, engine)
+    if name == "sgd":
+        return FlatSGD(param, grad, lr, momentum, weight_decay, clip_norm, engine)
+    if name == "adagrad":
+        return FlatAdagrad(param, grad, lr, lr_decay, weight_decay, clip_norm, engine)
+    raise ValueError(f"unknown optimizer {name!r} (adam, sgd, adagrad)")
+
+
+def resolve_step_path(step_path, *, optimizer, gat, wide, moco, finetune=False, world=1):
+    """``train.py --step-path`` -> "fused" (MoCoTrainStep / E2ETrainStep / FinetuneTrainStep) or "api" (autograd, torch's clip
+    and torch.optim over the same kernels).  ``auto`` keeps every single-GPU command line on the route it had before the flag
+    existed -- Adam on the fused step where there is one, SGD / Adagrad on the API path -- and takes the fused step for every
+    optimizer on several ranks, where the API path does not run.  Refusals name the path that serves the request."""
+    if gat:
+        served, what = False, "--model gat"
+    elif finetune:
+        served, what = not wide, "--finetune with --hidden-size above 64"
+    else:
+        served, what = not wide or moco, "--hidden-size above 64 without --moco"
+    if step_path == "fused" and not served:
+        raise NotImplementedError(f"--step-path fused: there is no fused step for {what}; the API path serves it "
+                                  "(--step-path api, or the default auto)")
+    if step_path == "fused" or (step_path == "auto" and served and (optimizer == "adam" or world > 1)):
+        return "fused"
+    if step_path not in ("auto", "api"):
+        raise ValueError(f"unknown --step-path {step_path!r} (auto, fused, api)")
+    if world > 1:
+        raise NotImplementedError(f"the API path (--step-path api; {what if not served else 'forced here'}) runs on one GPU; the "
+                                  "data-parallel step is the fused MoCo step (--step-path fused, or auto)")
+    return "api"
+
 
 class _GraphedStep:
     """What MoCoTrainStep and E2ETrainStep share: the flat buffers, the producer lanes, the step's stream and its hand-offs,
@@ -490,9 +604,9 @@ class _GraphedStep:
             self._graphs_regrown = regrown
         try:
             if scalars is not None:
-                g0 = self.optimizer.param_groups[0]
+                rate, betas = self.optimizer.ring_scalars(lr)           # (Adagrad: the clr of the step about to run)
                 self._ring_guard()
-                self.nce.fill_scalars(self.ring, self.ring_count % self.ring_len, lr, g0["betas"], self.optimizer.steps + 1,
+                self.nce.fill_scalars(self.ring, self.ring_count % self.ring_len, rate, betas, self.optimizer.steps + 1,
                                       enqueue_index, seed or 0)
                 self.ring_count += 1
             if not graphed:
@@ -725,7 +839,8 @@ class MoCoTrainStep(_GraphedStep):
     def __init__(self, model: GraphEncoder, model_ema: GraphEncoder, contrast: MemoryMoCo, sampler, posemb,
                  learning_rate=0.005, betas=(0.9, 0.999), weight_decay=1e-5, clip_norm=1.0, alpha=0.999,
                  world_size=1, rank=0, prefetch=True, extra_lanes=(), depth=2, lanes=None, chunk=1, reserved_cus=0, cu_layout="interleaved",
-                 collectives=None, ahead=None, graph=None, flat_engine=None, fold=None, onepass_head=None):
+                 collectives=None, ahead=None, graph=None, flat_engine=None, fold=None, onepass_head=None,
+                 optimizer="adam", momentum=0.9, lr_decay=0.0):
         """``sampler``/``posemb``: producer lane 0; ``extra_lanes``: more (sampler, posemb) pairs with their own
         workspaces for multi-stream prefetch (see :class:`BatchProducer`).
         ``graph``: replay the step's ~45 launches as ONE captured hipGraph per ring slot (default: on with prefetch on a
@@ -737,7 +852,10 @@ class MoCoTrainStep(_GraphedStep):
         ``onepass_head``: the head as one pass over the queue (gcc_nce_forward_backward, two launches instead of four).  OFF
         unless asked for (``GCC_STEP_ONEPASS_HEAD=1``): it adds the same terms in another order, d loss / d q moves by ~1e-7
         relative, and Adam turns that into visibly different weights within a few steps -- a training run is no
-        longer the run the four launches give."""
+        longer the run the four launches give.
+        ``optimizer``: "adam", "sgd" (``momentum``) or "adagrad" (``lr_decay``), train.py:658-679.  SGD / Adagrad run the unfolded
+        tail -- a sum-of-squares launch, the update launch (clip, rule, EMA, meters), the enqueue: the tail the data-parallel Adam
+        step runs -- at both widths, on one or several ranks, eager or replayed."""
         self.ema, self.contrast = model_ema, contrast
         self.fold = (os.environ.get("GCC_STEP_FOLD", "1") != "0") if fold is None else bool(fold)
         self.onepass_head = (os.environ.get("GCC_STEP_ONEPASS_HEAD", "0") == "1") if onepass_head is None else bool(onepass_head)
@@ -766,8 +884,9 @@ class MoCoTrainStep(_GraphedStep):
         self.gin = model.wide_engine() if self.wide else model.engine()
         self.nce = contrast.engine()
         # Adam(lr, betas, weight_decay as L2) over exactly the parameters that get gradients, train.py:667-672
-        self.optimizer = FlatAdam(self.live, self.flat_grad, learning_rate, betas, weight_decay, clip_norm,
-                                  (flat_engine or NceEngine()) if self.wide else self.nce)      # (the flat-buffer kernels live in csrc/nce.hip; ``flat_engine``: tests)
+        self.optimizer = flat_optimizer(optimizer, self.live, self.flat_grad, learning_rate, betas, weight_decay, clip_norm,
+                                        (flat_engine or NceEngine()) if self.wide else self.nce,      # (the flat-buffer kernels live in csrc/nce.hip; ``flat_engine``: tests)
+                                        momentum=momentum, lr_decay=lr_decay)
         self.L = len(model.gnn.ginlayers)
         self.keys_all = torch.empty(self.B * world_size, contrast.inputSize if self.wide else H, device=self.dev) if self.collectives else None
         model.train()                                                    # train.py:357-365
@@ -875,7 +994,7 @@ class MoCoTrainStep(_GraphedStep):
                 dq = self.nce.backward(feat_q, feat_k, mem, c.T, 0, S["outs"], self.one, stream=st,
                                        prof=pr.get("nce_bwd"), defer_means=defer) # loss.backward(), train.py:408
             kw = {} if self.wide else dict(prof=pr.get("gin_bwd"))
-            if self.fold and scalars is not None and not self.collectives:
+            if self.fold and scalars is not None and not self.collectives and isinstance(self.optimizer, FlatAdam):
                 # nothing touches the gradient between the backward's last kernel and Adam: its sum of squares is taken there
                 _, n = self.gin.backward(enc, S["pq"], S["bufq"], dq, targets=self.grad_views, stream=st,
                                          sumsq=self.optimizer.sumsq_parts, **kw)
@@ -929,7 +1048,7 @@ class E2ETrainStep(_GraphedStep):
 
     def __init__(self, model: GraphEncoder, sampler, posemb, nce_t=0.07, learning_rate=0.005, betas=(0.9, 0.999),
                  weight_decay=1e-5, clip_norm=1.0, prefetch=True, depth=2, lanes=None, chunk=1, ahead=None, engine=None,
-                 graph=None):
+                 graph=None, optimizer="adam", momentum=0.9, lr_decay=0.0):
         self.T, self.clip_norm = nce_t, clip_norm
         self.world, self.rank = 1, 0
         # graph replay is available but OFF by default here: measured 1.241 vs 1.240 ms per step at bsz 256 and 0.872 vs
@@ -938,7 +1057,8 @@ class E2ETrainStep(_GraphedStep):
                          ahead, False if graph is None else graph)
         self.gin = model.engine()
         self.nce = engine if engine is not None else NceEngine()
-        self.optimizer = FlatAdam(self.live, self.flat_grad, learning_rate, betas, weight_decay, clip_norm, self.nce)
+        self.optimizer = flat_optimizer(optimizer, self.live, self.flat_grad, learning_rate, betas, weight_decay, clip_norm, self.nce,
+                                        momentum=momentum, lr_decay=lr_decay)
         model.train()
 
     def _first_id(self, step):

@@ -689,6 +689,33 @@ int32_t gcc_adam_ema_enqueue_step_scalars(float *param, float *grad, float *exp_
                                           const double *sumsq_parts, int32_t nparts, float *queue, int32_t K, const float *keys,
                                           int32_t nkeys, void *stream);
 
+/* --optimizer sgd / adagrad (train.py:658-679) on the same flat buffers, with torch.optim's float32 arithmetic:
+ *   GCC_OPT_SGD      torch.optim.SGD(lr, momentum, weight_decay), dampening 0, no Nesterov: g' = g_clipped + wd p;
+ *                    buf = momentum buf + g'; p -= lr buf.  state = buf, ZERO-initialised by the caller (which gives torch's
+ *                    first step, buf = g', without a step counter); hyper = momentum.
+ *   GCC_OPT_ADAGRAD  torch.optim.Adagrad(lr, lr_decay, weight_decay, eps): g' = g_clipped + wd p; sum += g' g';
+ *                    p -= clr g' / (sqrt(sum) + eps).  state = sum, zero-initialised; hyper = eps; `lr` is THIS STEP's
+ *                    clr = lr / (1 + (t - 1) lr_decay), which the caller forms in double as torch does.
+ * gcc_opt_step / gcc_opt_ema_step / gcc_opt_ema_step_scalars are gcc_adam_step / gcc_adam_ema_step / gcc_adam_ema_step_scalars
+ * with that update: the same clip (fixed-order double sum of squares, coef = min(1, max_norm / (norm + 1e-6)), grad_scale folded
+ * in, the clipped gradient stored back, grad_norm[0] written, max_norm <= 0 = no clip), the same scratch, the same optional EMA
+ * and meters inside the update launch; two launches.  With scalars, scalars->lr is the step's rate (Adagrad: its clr); the
+ * bias-correction fields are not read.  gcc_opt_clipvalue_step is gcc_adam_clipvalue_step's twin (one launch).
+ * An unknown rule, n < 1 and a NULL pointer are refused (rc < 0, gcc_last_error()). */
+#define GCC_OPT_SGD 1
+#define GCC_OPT_ADAGRAD 2
+int32_t gcc_opt_step(int32_t rule, float *param, float *grad, float *state, int64_t n, float lr, float hyper,
+                     float weight_decay, float max_norm, float grad_scale, float *grad_norm, double *scratch, void *stream);
+int32_t gcc_opt_ema_step(int32_t rule, float *param, float *grad, float *state, int64_t n, float lr, float hyper,
+                         float weight_decay, float max_norm, float grad_scale, float *grad_norm, double *scratch, float *ema,
+                         int64_t n_ema, float ema_m, const gcc_step_meters_args *meters, void *stream);
+int32_t gcc_opt_ema_step_scalars(int32_t rule, float *param, float *grad, float *state, int64_t n, float hyper,
+                                 float weight_decay, float max_norm, float grad_scale, float *grad_norm, double *scratch,
+                                 float *ema, int64_t n_ema, float ema_m, const gcc_step_meters_args *meters,
+                                 const gcc_step_scalars *scalars, void *stream);
+int32_t gcc_opt_clipvalue_step(int32_t rule, float *param, float *grad, float *state, int64_t n, float lr, float hyper,
+                               float weight_decay, float clip_value, float grad_scale, void *stream);
+
 /* ------------------------------------------------------- fine-tuning head ---
  * train.py --finetune (train_finetune / test_finetune of the reference, train.py:175-337): output_layer = nn.Linear(D, C),
  * CrossEntropyLoss (mean over the batch) and out.argmax(1), as ONE single-workgroup launch.  Rows whose label is < 0 are

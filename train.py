@@ -35,7 +35,8 @@ from gcc_amd.contrast import MemoryMoCo, NCESoftmaxLoss, NCESoftmaxLossNS, e2e_l
 from gcc_amd.encoder import GraphEncoder
 from gcc_amd.misc import AverageMeter, adjust_learning_rate, warmup_linear
 from gcc_amd.sampler import LoadBalanceGraphDataset
-from gcc_amd.train_step import E2ETrainStep, MoCoTrainStep, clip_grad_norm, flatten_parameters, moment_update, read_meters
+from gcc_amd.train_step import (E2ETrainStep, MoCoTrainStep, clip_grad_norm, flatten_parameters, moment_update, read_meters,
+                                resolve_step_path)
 
 GRAPH_CLASSIFICATION_DSETS = ["collab", "imdb-binary", "imdb-multi", "rdt-b", "rdt-5k"]
 
@@ -139,6 +140,7 @@ def parse_option(argv=None):
     parser.add_argument("--edge-multiplicity", type=int, default=0, help="copies of every edge in the reference's DGL graph (edge lists: detected)")
     parser.add_argument("--no-prefetch", action="store_true", help="--finetune: make each batch on the step's stream")
     parser.add_argument("--graph-batcher", choices=["auto", "host", "device"], default="auto", help="--finetune on graph-classification datasets: assemble batches on the device (gcc_pack_graphs; auto on a GPU) or with the host loop")
+    parser.add_argument("--step-path", choices=["auto", "fused", "api"], default="auto", help="the training step: fused = MoCoTrainStep / E2ETrainStep / FinetuneTrainStep (flat buffers, clip + update in two launches, graph replay, data parallel) for every --optimizer; api = autograd + torch.optim over the same kernels; auto = adam fused and sgd / adagrad api on one GPU (the routes before this flag), everything fused on several")
     parser.add_argument("--tu-parse", choices=["host", "device"], default="host", help="--finetune with --tudataset: parse the three TU files on the host (np.loadtxt) or on the device (gcc_text_ints_sep, gcc_tu_corpus)")
     # fmt: on
 
@@ -330,6 +332,10 @@ def main(args):
     if world > 1 and not args.moco:
         raise NotImplementedError("only the MoCo step is data parallel (seed batch sharded by rank, key all-gather, gradient "
                                   "all-reduce); the E2E / --nce-k 0 path would train N identical replicas: run it on one GPU")
+    args.step_path = getattr(args, "step_path", "auto")
+    if not args.resume:       # --step-path refusals before any device work (the route is taken from the built model below)
+        resolve_step_path(args.step_path, optimizer=args.optimizer, gat=args.model == "gat", wide=args.hidden_size > 64,
+                          moco=args.moco, world=world)
     checkpoint = None
     if args.resume:                                       # train.py:487-506
         if os.path.isfile(args.resume):
@@ -337,7 +343,8 @@ def main(args):
             checkpoint = torch.load(args.resume, map_location="cpu", weights_only=False)
             pretrain_args = checkpoint["opt"]
             for name in ("fold_idx", "gpu", "finetune", "resume", "cv", "dataset", "epochs", "num_workers",
-                         "batch_size", "dgl_file", "graph_dir", "graph_files", "graph_parse", "graph_npz", "synthetic", "max_steps", "producer_lanes", "producer_chunk"):
+                         "batch_size", "dgl_file", "graph_dir", "graph_files", "graph_parse", "graph_npz", "synthetic", "max_steps", "producer_lanes", "producer_chunk",
+                         "step_path"):
                 setattr(pretrain_args, name, getattr(args, name))
             args = pretrain_args
         else:
@@ -384,12 +391,12 @@ def main(args):
     trainer, optimizer = None, None
     wide = model.wide or contrast.wide    # above 64 channels (or a wider input): the any-width kernels (csrc/ginx.hip)
     gat = model.gnn_model == "gat"        # GAT (csrc/gat.hip): the API path below for every optimizer, MoCo and E2E
-    # --moco with Adam: the fused step at every width (MoCoTrainStep: producer lanes, flat buffers, clip + Adam + EMA as two launches,
-    # data parallel; above 64 channels on the any-width kernels, launch by launch).  E2E above 64 channels and SGD / Adagrad: the API
-    # path below (single GPU)
-    if wide and world > 1 and not (args.moco and args.optimizer == "adam"):
-        raise NotImplementedError("--hidden-size above 64 on several GPUs needs --moco with --optimizer adam (the data-parallel step)")
-    if args.optimizer == "adam" and (not wide or args.moco) and not gat:
+    # --moco: the fused step at every width (MoCoTrainStep: producer lanes, flat buffers, clip + update + EMA as two launches, data
+    # parallel; above 64 channels on the any-width kernels, launch by launch); E2E up to 64 channels: E2ETrainStep.  --step-path auto
+    # on one GPU keeps SGD / Adagrad on the API path below, where GAT and E2E above 64 channels always run (single GPU)
+    path = resolve_step_path(args.step_path, optimizer=args.optimizer, gat=gat, wide=wide, moco=args.moco,
+                             world=world)
+    if path == "fused":
         # data pipeline: `producer_lanes` streams, each preparing `producer_chunk` steps per turn (sampler calls + one
         # multi-view eigensolver call) -- the role of the reference's --num-workers DataLoader processes
         lanes, depth = [], 2
@@ -399,24 +406,23 @@ def main(args):
             lanes.append((smp, DevicePosEmb(args.batch_size, smp.node_cap, args.positional_embedding_size, device=dev,
                                             seed=args.seed, num_buffers=depth * args.producer_chunk,
                                             max_views=min(2 * args.producer_chunk, 32))))
+        rule = dict(optimizer=args.optimizer, momentum=args.momentum, lr_decay=args.lr_decay_rate)      # train.py:658-679
         if args.moco:
             trainer = MoCoTrainStep(model, model_ema, contrast, lanes[0][0], lanes[0][1],
                                     learning_rate=args.learning_rate, betas=(args.beta1, args.beta2),
                                     weight_decay=args.weight_decay, clip_norm=args.clip_norm, alpha=args.alpha,
-                                    world_size=world, rank=rank, lanes=lanes, depth=depth, chunk=args.producer_chunk)
+                                    world_size=world, rank=rank, lanes=lanes, depth=depth, chunk=args.producer_chunk, **rule)
         else:
             trainer = E2ETrainStep(model, lanes[0][0], lanes[0][1], nce_t=args.nce_t, learning_rate=args.learning_rate,
                                    betas=(args.beta1, args.beta2), weight_decay=args.weight_decay,
-                                   clip_norm=args.clip_norm, lanes=lanes, depth=depth, chunk=args.producer_chunk)
+                                   clip_norm=args.clip_norm, lanes=lanes, depth=depth, chunk=args.producer_chunk, **rule)
         optimizer = trainer.optimizer
         # the loop reads results only behind read_meters() (which joins the step's stream) and the epoch's device
         # synchronisation: no per-step stream hand-offs (gcc_amd/train_step.py: MoCoTrainStep.step)
         trainer.relaxed_streams = True
     else:
-        # train.py:658-679: SGD(momentum) / Adagrad through autograd and torch.optim -- the API path of the same kernels; also
-        # Adam for models wider than the fused step's 64 channels
-        if world > 1:
-            raise NotImplementedError("--optimizer sgd/adagrad runs the single-GPU API path; the data-parallel step is fused Adam")
+        # train.py:658-679: SGD(momentum) / Adagrad / Adam through autograd and torch.optim -- the API path of the same kernels
+        # (single GPU: resolve_step_path refuses it on several ranks)
         posemb = DevicePosEmb(args.batch_size, train_dataset.node_cap, args.positional_embedding_size,
                               device=dev, seed=args.seed)
         if args.optimizer == "adam":                      # (--hidden-size above 64, --model gat) train.py:667-672
