@@ -1013,8 +1013,13 @@ static int32_t gin_backward_launches(const gcc_gin_pass *pass, const float *dfea
     const int L = p.w.num_gin_layers, B = p.batch_size;
     const int kdim0 = p.w.pos_dim + p.w.deg_emb_dim + 1;
     const int emb_elems = (p.w.max_degree + 1) * p.w.deg_emb_dim;
-    if (!p.training || L < 1 || L > GCC_GIN_MAX_LAYERS || emb_elems > kEmbMaxElems) {
+    if (!p.training || L < 1 || L > GCC_GIN_MAX_LAYERS) {
         snprintf(g_err, kErrLen, "gcc_gin_backward: needs a training-mode pass (layers=%d)", L);
+        return -2;
+    }
+    if (emb_elems > kEmbMaxElems) {      // (the forward serves such a table: a key encoder's forward-only training pass stays possible)
+        snprintf(g_err, kErrLen, "gcc_gin_backward: (max_degree + 1) * degree_embedding_size = (%d + 1) * %d = %d floats, above the "
+                 "%d that the degree-embedding gradient keeps in LDS", p.w.max_degree, p.w.deg_emb_dim, emb_elems, kEmbMaxElems);
         return -2;
     }
     for (int l = 0; l < L; ++l)

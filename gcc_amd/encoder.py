@@ -99,6 +99,8 @@ def fill_weights(enc: "GraphEncoder", ptr) -> _cabi.GccGinWeights:
     w = _cabi.GccGinWeights()
     g = enc.gnn
     L = len(g.ginlayers)
+    if L < 1:
+        raise ValueError(f"num_layers={L + 1}: the fused GIN kernels need at least one GIN layer (num_layers >= 2)")
     w.num_gin_layers = L
     w.pos_dim = enc.positional_embedding_size
     w.deg_emb_dim = enc.degree_embedding_size
@@ -383,6 +385,9 @@ class GraphEncoder(nn.Module):
         # --hidden-size up to 64 runs on the fused 64-channel kernels, zero-padded and exact (ensure_padded); anything wider
         # (or a wider input) on the any-width kernels of csrc/ginx.hip (gcc_amd/encoder_wide.py): same arithmetic, unfused
         self.wide = node_hidden_dim > H or output_dim > H or node_input_dim > H
+        if num_layers < 2:
+            raise ValueError(f"num_layers={num_layers}: the GIN kernels need at least one GIN layer (num_layers - 1 of them "
+                             f"run), so num_layers must be 2..{_cabi.GIN_MAX_LAYERS + 1}")
         if num_layers - 1 > _cabi.GIN_MAX_LAYERS:
             raise NotImplementedError("too many GIN layers")
         self.gnn = _UnsupervisedGIN(num_layers, node_input_dim, node_hidden_dim, output_dim, final_dropout=0.5)

@@ -405,7 +405,9 @@ int64_t gcc_gin_backward_workspace_bytes(int64_t node_cap, int32_t batch_size, i
 
 /* Backward of one training-mode pass: dfeat [B, 64] -> grads (overwritten).
  * If `accumulate` != 0 the results are added to `grads` instead (E2E mode runs
- * two passes through the same weights, train.py:397-398). */
+ * two passes through the same weights, train.py:397-398).
+ * Refused (-2, gcc_last_error names the sizes) when (max_degree + 1) * deg_emb_dim exceeds 10,240 floats: the degree-embedding
+ * gradient keeps the table in LDS.  gcc_gin_forward serves such a table (a key encoder's forward-only training pass). */
 int32_t gcc_gin_backward(const gcc_gin_pass *pass, const float *dfeat, const gcc_gin_grads *grads,
                          int32_t accumulate, void *workspace, int64_t workspace_bytes, int64_t node_cap,
                          gcc_prof *prof, void *stream);

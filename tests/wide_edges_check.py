@@ -55,6 +55,18 @@ class Tier:
     def flat_engine(self):
         return NceEngine(**self._kw())
 
+    def gin_engine(self):
+        """the fused 64-channel GIN pass (csrc/encoder.hip, encoder_bwd.hip)"""
+        from gcc_amd.encoder import GinEngine
+
+        return GinEngine(**self._kw())
+
+    def head_engine(self):
+        """the fine-tuning head and clip-by-value Adam (csrc/cls_head.hip)"""
+        from gcc_amd.finetune import ClsHeadEngine
+
+        return ClsHeadEngine(**self._kw())
+
     def sync(self):
         if self.name == "gpu":
             torch.cuda.synchronize()
