@@ -257,10 +257,25 @@ __device__ __forceinline__ void fill_multigraph_by_entry(const Defl &d, const in
 // what the expansion needs of the tables, 8 bytes per node: quotient row | order inside the group | group size (0 = not
 // grouped; bit 15 = stalk member, bit 14 = the stalk's leaf) | contrast base of the group
 constexpr int kRecStalk = 0x8000, kRecStalkLeaf = 0x4000, kRecSize = 0x3FFF;
+// ---- isolated nodes.  A node i of degree 0 has (M u)_i = 0, so u_i = (M u)_i / lambda = 0 in every eigenvector whose
+// eigenvalue is not zero.  The solvers leave their rounding noise there (1e-15 .. 1e-18 after an inverse iteration), and the row
+// normalisation would make a unit row of it that depends on the start vector and on the solver class.  Every expansion step
+// writes such an entry as 0 (isolated_zero); entries of null-space columns stay, there the node's row is part of a basis.
+// "Not zero" is judged on the kernel's own eigenvalue of the column: the threshold has to clear the solvers' eigenvalue error
+// (at most 6e-7 against float64 in every class, dense, block and Krylov, on the disconnected items of
+// tests/posemb_width_check.py at widths 5, 6 and 32; kZeroEig = 1e-5 is what the ranking already trusts) and stay under the
+// smallest eigenvalue a column is guaranteed to have where the rule is asserted (0.1): 1e-2 is a factor 10 from the one
+// and more than 10,000 from the other.  An isolated node is never grouped, so its record's order field is free.
+constexpr float kIsolatedEigMin = 1e-2f;
+constexpr int kRecIsolated = 0xFFFF;     // order field of a degree-0 node's record
+// (per column, once: src = the column's code, lam = the eigenvalues the codes >= 0 index; a contrast column, src < 0, is 0 at an
+//  ungrouped node anyway.  Per entry: o = the order field of the node's record)
+__device__ __forceinline__ bool column_not_null(int src, const float *lam) { return src >= 0 && fabsf(lam[src]) > kIsolatedEigMin; }
+__device__ __forceinline__ bool isolated_zero(int o, bool not_null) { return o == kRecIsolated && not_null; }
 __device__ __forceinline__ void defl_record(const Defl &d, int v, const int32_t *rp, const int32_t *col, int n0, uint16_t *rec)
 {
     const int pv = d.par[v];
-    int rsrc = d.ridx[v], o = 0, g = 0, cb = 0;
+    int rsrc = d.ridx[v], o = rp[v + 1] == rp[v] ? kRecIsolated : 0, g = 0, cb = 0;
     if (pv != (int)kNone && d.tcnt[pv] >= 2) {
         rsrc = d.ridx[d.rep[pv]]; o = d.ord[v]; g = d.tcnt[pv]; cb = d.cbase[pv] & 0xFFFF;
     } else {
@@ -1978,9 +1993,10 @@ __global__ __launch_bounds__(kT, kPair ? GCC_POSEMB_QUAD_OCC : 1) void posemb_di
         }
     }
     // ---- expand to the n original nodes; x = normalize(u, "l2") row-wise, zero padded (data_util.py:260-262)
+    const bool not_null = lane < k && column_not_null(colsrc[lane], es.lamv);
     for (int v = wv; v < n; v += kNW) {
         const int rsrc = xrec[4 * v], o = xrec[4 * v + 1], g = xrec[4 * v + 2], cb = xrec[4 * v + 3];
-        const float val = lane < k ? defl_expand(rsrc, o, g, cb, colsrc[lane], w.Y, kYld) : 0.f;
+        const float val = lane < k && !isolated_zero(o, not_null) ? defl_expand(rsrc, o, g, cb, colsrc[lane], w.Y, kYld) : 0.f;
         const float s2 = wave_sum(val * val);
         const float inv = s2 > 0.f ? 1.0f / sqrtf(s2) : 1.0f;
         if (lane < a.hidden) {
@@ -2156,13 +2172,14 @@ __global__ __launch_bounds__(kWaveTeams * 64, kNMax <= 48 ? GCC_POSEMB_W48_OCC :
         // 'expand' 12.7 against 10.7 us (n' <= 48) / 19.5 against 15.9 us (<= 64) per item: profiles/HISTORY.md.)
         const int c16 = lane & 15, nv = lane >> 4;
         const int src0 = c16 < k ? colsrc[c16] : 0, src1 = c16 + 16 < k ? colsrc[c16 + 16] : 0;
+        const bool nn0 = column_not_null(src0, es.lamv), nn1 = column_not_null(src1, es.lamv);
         for (int v0 = 0; v0 < n; v0 += 4) {
             const int v = v0 + nv;
             const bool valid = v < n;
             const int vv = valid ? v : 0;
             const int rsrc = xinfo[4 * vv + 0], o = xinfo[4 * vv + 1], g = xinfo[4 * vv + 2], cb = xinfo[4 * vv + 3];
-            const float val0 = valid && c16 < k ? defl_expand(rsrc, o, g, cb, src0, w.Y, kYld) : 0.f;
-            const float val1 = valid && c16 + 16 < k ? defl_expand(rsrc, o, g, cb, src1, w.Y, kYld) : 0.f;
+            const float val0 = valid && c16 < k && !isolated_zero(o, nn0) ? defl_expand(rsrc, o, g, cb, src0, w.Y, kYld) : 0.f;
+            const float val1 = valid && c16 + 16 < k && !isolated_zero(o, nn1) ? defl_expand(rsrc, o, g, cb, src1, w.Y, kYld) : 0.f;
             const float s2 = wave_shfl(row16_sum_last(fmaf(val0, val0, val1 * val1)), lane | 15);
             const float inv = s2 > 0.f ? 1.0f / sqrtf(s2) : 1.0f;
             if (valid) {
@@ -2530,8 +2547,11 @@ __global__ __launch_bounds__(kKThreads) void posemb_krylov_kernel(KryArgs ka)
         }
         __syncthreads();
         for (int r = tid; r < n; r += kKThreads) {
-            const float *ro = rawout + (int64_t)(n0 + r) * a.hidden;
+            float *ro = rawout + (int64_t)(n0 + r) * a.hidden;
             float *po = a.pos + (int64_t)(n0 + r) * a.hidden;
+            if (a.row_ptr[n0 + r + 1] == a.row_ptr[n0 + r])             // an isolated node (kIsolatedEigMin)
+                for (int c = 0; c < k; ++c)
+                    if (fabsf(theta[colsrc[c]]) > kIsolatedEigMin) ro[c] = 0.f;
             float s2 = 0.f;
             for (int c = 0; c < k; ++c) s2 = fmaf(ro[c], ro[c], s2);
             const float inv = s2 > 0.f ? 1.0f / sqrtf(s2) : 1.0f;
@@ -3672,9 +3692,11 @@ __global__ __launch_bounds__(kChThreads) GCC_CHEB_REG_CAP void posemb_cheb_kerne
     {
         const int hl = lane & 31, hv = lane >> 5;
         const int src = hl < k ? colsrc[hl] : 0;
+        const bool not_null = column_not_null(src, theta);
         auto node_value = [&](int v) -> float {
             if (v >= n || hl >= k) return 0.f;
             const int rsrc = xrec[4 * v], o = xrec[4 * v + 1], g = xrec[4 * v + 2], cb = xrec[4 * v + 3];
+            if (isolated_zero(o, not_null)) return 0.f;
             return defl_expand(rsrc, o, g, cb, src, XA, P);
         };
         auto node_store = [&](int v, float val, float s2) {
