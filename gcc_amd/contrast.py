@@ -23,7 +23,8 @@ D = 64
 
 
 class NceEngine:
-    """C-ABI calls of the head.  ``lib``/``ptr`` are injectable for the emulator tests only."""
+    """C-ABI calls of the head (csrc/nce.hip) and of the step tail (csrc/step_tail.hip).  ``lib``/``ptr`` are injectable for the
+    emulator tests only."""
 
     def __init__(self, lib=None, ptr=None, dtype="f32"):
         self.lib = lib if lib is not None else _cabi.load()
@@ -129,12 +130,42 @@ class NceEngine:
                    self.ptr(saved) if saved is not None else None, stream)
         return saved
 
+    def _tail(self, who, rule, param, grad, states, lr, hyper, weight_decay, step, max_norm, grad_norm, scratch, stream,
+              grad_scale, ema=None, ema_src=None, ema_m=0.0, meters=None, scalars=None, sumsq_parts=None, enqueue=None, plain=False):
+        """One clip-by-norm step tail (the kernels of gcc_amd/csrc/step_tail.hip) for any ``rule``: None = Adam (``states`` =
+        (exp_avg, exp_avg_sq), ``hyper`` = (beta1, beta2, eps), ``step`` its count), 1 = SGD / 2 = Adagrad (one state tensor,
+        ``hyper`` = (momentum,) / (eps,)).  The entry point follows from (rule, scalars, fold); ``plain``: the one without the
+        EMA / meters arguments."""
+        ptr, fold = self.ptr, sumsq_parts is not None or enqueue is not None
+        if ema is not None and (ema_src is None or ema_src.data_ptr() != param.data_ptr() or ema.numel() != ema_src.numel()):
+            raise ValueError(f"{who}: param must be a prefix of ema_src, and ema the same size as ema_src")
+        if fold and (scalars is None or rule is not None):
+            raise ValueError(f"{who}: sumsq_parts / enqueue are the device-resident-scalars Adam step's")
+        name = ("gcc_adam" if rule is None else "gcc_opt") + ("_step" if plain else "_ema_enqueue_step_scalars" if fold else
+                                                      "_ema_step_scalars" if scalars is not None else "_ema_step")
+        args = ([] if rule is None else [int(rule)]) + [ptr(param), ptr(grad), *(ptr(s) for s in states), param.numel()]
+        args += ([] if scalars is not None else [float(lr)]) + [float(h) for h in hyper] + [float(weight_decay)]
+        args += ([int(step)] if rule is None and scalars is None else []) + [float(max_norm), float(grad_scale), ptr(grad_norm),
+                                                                             ptr(scratch)]
+        if not plain:
+            ma = None
+            if meters is not None:
+                acc, mx, loss, prob, q, k = meters
+                ma = _cabi.GccStepMetersArgs(ptr(acc), ptr(mx), ptr(loss), ptr(prob), ptr(q.node_off), ptr(q.edge_off),
+                                             ptr(k.node_off), int(q.batch_size))
+            args += [ptr(ema) if ema is not None else None, ema.numel() if ema is not None else 0, float(ema_m),
+                     ctypes.byref(ma) if ma is not None else None] + ([ptr(scalars)] if scalars is not None else [])
+        if fold:
+            (parts, nparts), (queue, keys) = sumsq_parts or (None, 0), enqueue or (None, None)
+            args += [ptr(parts) if parts is not None else None, int(nparts), ptr(queue) if queue is not None else None,
+                     queue.shape[0] if queue is not None else 0, ptr(keys) if keys is not None else None,
+                     keys.shape[0] if keys is not None else 0]
+        _cabi.call(self.lib, name, *args, stream)
+
     def adam(self, param, grad, exp_avg, exp_avg_sq, lr, betas, eps, weight_decay, step, max_norm, grad_norm,
              scratch, stream=None, grad_scale=1.0):
-        _cabi.call(self.lib, "gcc_adam_step", self.ptr(param), self.ptr(grad), self.ptr(exp_avg), self.ptr(exp_avg_sq),
-                   param.numel(), float(lr), float(betas[0]), float(betas[1]), float(eps),
-                   float(weight_decay), int(step), float(max_norm), float(grad_scale), self.ptr(grad_norm),
-                   self.ptr(scratch), stream)
+        self._tail("adam", None, param, grad, (exp_avg, exp_avg_sq), lr, (*betas, eps), weight_decay, step, max_norm, grad_norm,
+                   scratch, stream, grad_scale, plain=True)
 
     def adam_ema(self, param, grad, exp_avg, exp_avg_sq, lr, betas, eps, weight_decay, step, max_norm, grad_norm,
                  scratch, stream=None, grad_scale=1.0, ema=None, ema_src=None, ema_m=0.0, meters=None, scalars=None,
@@ -144,65 +175,15 @@ class NceEngine:
         With ``scalars``: ``sumsq_parts`` = (float64 tensor, count) of :meth:`GinEngine.backward`'s ``sumsq`` replaces the
         sum-of-squares launch, ``enqueue`` = (queue, keys) puts the queue's enqueue into the Adam launch
         (gcc_adam_ema_enqueue_step_scalars)."""
-        ma = None
-        if meters is not None:
-            acc, mx, loss, prob, q, k = meters
-            ma = _cabi.GccStepMetersArgs(self.ptr(acc), self.ptr(mx), self.ptr(loss), self.ptr(prob), self.ptr(q.node_off),
-                                         self.ptr(q.edge_off), self.ptr(k.node_off), int(q.batch_size))
-        if ema is not None and (ema_src is None or ema_src.data_ptr() != param.data_ptr() or ema.numel() != ema_src.numel()):
-            raise ValueError("adam_ema: param must be a prefix of ema_src, and ema the same size as ema_src")
-        if (sumsq_parts is not None or enqueue is not None) and scalars is None:
-            raise ValueError("adam_ema: sumsq_parts / enqueue are the device-resident-scalars step's")
-        if sumsq_parts is not None or enqueue is not None:
-            parts, nparts = sumsq_parts if sumsq_parts is not None else (None, 0)
-            queue, keys = enqueue if enqueue is not None else (None, None)
-            _cabi.call(
-                self.lib, "gcc_adam_ema_enqueue_step_scalars",
-                self.ptr(param), self.ptr(grad), self.ptr(exp_avg), self.ptr(exp_avg_sq), param.numel(), float(betas[0]),
-                float(betas[1]), float(eps), float(weight_decay), float(max_norm), float(grad_scale), self.ptr(grad_norm),
-                self.ptr(scratch), self.ptr(ema) if ema is not None else None, ema.numel() if ema is not None else 0,
-                float(ema_m), ctypes.byref(ma) if ma is not None else None, self.ptr(scalars),
-                self.ptr(parts) if parts is not None else None, int(nparts),
-                self.ptr(queue) if queue is not None else None, queue.shape[0] if queue is not None else 0,
-                self.ptr(keys) if keys is not None else None, keys.shape[0] if keys is not None else 0, stream)
-            return
-        if scalars is not None:                      # lr / bias corrections from the device struct (replayed step)
-            _cabi.call(
-                self.lib, "gcc_adam_ema_step_scalars",
-                self.ptr(param), self.ptr(grad), self.ptr(exp_avg), self.ptr(exp_avg_sq), param.numel(), float(betas[0]),
-                float(betas[1]), float(eps), float(weight_decay), float(max_norm), float(grad_scale), self.ptr(grad_norm),
-                self.ptr(scratch), self.ptr(ema) if ema is not None else None, ema.numel() if ema is not None else 0,
-                float(ema_m), ctypes.byref(ma) if ma is not None else None, self.ptr(scalars), stream)
-            return
-        _cabi.call(self.lib, "gcc_adam_ema_step", self.ptr(param), self.ptr(grad), self.ptr(exp_avg), self.ptr(exp_avg_sq),
-                   param.numel(), float(lr), float(betas[0]), float(betas[1]), float(eps),
-                   float(weight_decay), int(step), float(max_norm), float(grad_scale),
-                   self.ptr(grad_norm), self.ptr(scratch),
-                   self.ptr(ema) if ema is not None else None, ema.numel() if ema is not None else 0,
-                   float(ema_m), ctypes.byref(ma) if ma is not None else None, stream)
+        self._tail("adam_ema", None, param, grad, (exp_avg, exp_avg_sq), lr, (*betas, eps), weight_decay, step, max_norm, grad_norm,
+                   scratch, stream, grad_scale, ema, ema_src, ema_m, meters, scalars, sumsq_parts, enqueue)
 
     def opt_step(self, rule, param, grad, state, lr, hyper, weight_decay, max_norm, grad_norm, scratch, stream=None,
                  grad_scale=1.0, ema=None, ema_src=None, ema_m=0.0, meters=None, scalars=None):
         """gcc_opt_step / gcc_opt_ema_step[_scalars]: :meth:`adam` / :meth:`adam_ema` with SGD's (``rule`` 1: ``state`` the
         momentum buffer, ``hyper`` the momentum) or Adagrad's (2: the sum of squares, eps; ``lr`` = the step's clr) update."""
-        head = (int(rule), self.ptr(param), self.ptr(grad), self.ptr(state), param.numel())
-        mid = (float(hyper), float(weight_decay), float(max_norm), float(grad_scale), self.ptr(grad_norm), self.ptr(scratch))
-        if ema is None and meters is None and scalars is None:
-            _cabi.call(self.lib, "gcc_opt_step", *head, float(lr), *mid, stream)
-            return
-        ma = None
-        if meters is not None:
-            acc, mx, loss, prob, q, k = meters
-            ma = _cabi.GccStepMetersArgs(self.ptr(acc), self.ptr(mx), self.ptr(loss), self.ptr(prob), self.ptr(q.node_off),
-                                         self.ptr(q.edge_off), self.ptr(k.node_off), int(q.batch_size))
-        if ema is not None and (ema_src is None or ema_src.data_ptr() != param.data_ptr() or ema.numel() != ema_src.numel()):
-            raise ValueError("opt_step: param must be a prefix of ema_src, and ema the same size as ema_src")
-        tail = (self.ptr(ema) if ema is not None else None, ema.numel() if ema is not None else 0, float(ema_m),
-                ctypes.byref(ma) if ma is not None else None)
-        if scalars is not None:                      # the rate from the device struct (replayed step)
-            _cabi.call(self.lib, "gcc_opt_ema_step_scalars", *head, *mid, *tail, self.ptr(scalars), stream)
-        else:
-            _cabi.call(self.lib, "gcc_opt_ema_step", *head, float(lr), *mid, *tail, stream)
+        self._tail("opt_step", int(rule), param, grad, (state,), lr, (hyper,), weight_decay, 0, max_norm, grad_norm, scratch,
+                   stream, grad_scale, ema, ema_src, ema_m, meters, scalars, plain=ema is None and meters is None and scalars is None)
 
     def meters(self, acc, mx, loss, prob, grad_norm, q, k, stream=None):
         _cabi.call(self.lib, "gcc_step_meters", self.ptr(acc), self.ptr(mx), self.ptr(loss), self.ptr(prob), self.ptr(grad_norm),

@@ -5,7 +5,7 @@
 //   loss = CrossEntropyLoss()(out, y)     mean over the batch
 //   loss.backward()                       d out, d W, d b, d feat_q (fed to the encoder's backward)
 //   preds = out.argmax(1); f1_score(..., average="micro") = correct / rows
-// and clip_grad_value_(params, v) + Adam.step() over one flat buffer.
+// (clip_grad_value_(params, v) + Adam.step() over the flat buffers: step_tail.hip).
 //
 //   cls_head_kernel<train>  ONE workgroup of 1024 threads (the problem is B <= 1024 rows x C <= 64 classes x D <= 256 features,
 //       latency-bound).  W [C][D] and b sit in LDS.  Phase 1: every wave takes groups of R = 64 / C rows, one lane per
@@ -15,7 +15,6 @@
 //       a workgroup barrier): dW / db as sums over rows 0..B-1 in order, one thread per element.  Loss and correct count: per
 //       lane over its rows in order, then a fixed wave tree and the 16 waves in order -- no float atomics anywhere, two runs
 //       are bit-identical.
-//   adam_clipvalue_kernel   clamp(g * grad_scale, -v, v) then gcc_adam_step's update; one launch (no norm pass).
 #include "host_common.h"
 
 #include <math.h>
@@ -189,27 +188,6 @@ __global__ __launch_bounds__(kThreads) void cls_head_kernel(HeadDev a)
     }
 }
 
-__global__ __launch_bounds__(256) void adam_clipvalue_kernel(float *p, float *g, float *m, float *v, int64_t n, float lr,
-                                                            float b1, float b2, float eps, float wd, float bc1, float bc2_sqrt,
-                                                            float clip, float grad_scale)
-{
-    TRAIN_STEP_WAVE_PRIORITY();
-    const int64_t stride = (int64_t)gridDim.x * 256;
-    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += stride) {
-        float gc = g[i] * grad_scale;
-        if (clip > 0.f) gc = gc < -clip ? -clip : (gc > clip ? clip : gc);   // clip_grad_value_ (NaN passes, as clamp_)
-        g[i] = gc;                                           // the clipped gradient stays visible, as in torch
-        const float p0 = p[i];
-        const float gi = fmaf(wd, p0, gc);                   // weight_decay: grad = grad + wd * param
-        const float mi = fmaf(b1, m[i], (1.f - b1) * gi);
-        const float vi = fmaf(b2, v[i], (1.f - b2) * gi * gi);
-        m[i] = mi;
-        v[i] = vi;
-        const float denom = sqrtf(vi) / bc2_sqrt + eps;
-        p[i] = p0 - (lr / bc1) * (mi / denom);
-    }
-}
-
 size_t head_lds_bytes(int C, int D)
 {
     return sizeof(float) * ((size_t)C * D + kMaxC + 2 * kWaves * 64) + sizeof(int) * kWaves * 64 + sizeof(double) * kWaves +
@@ -278,23 +256,6 @@ int32_t gcc_cls_head_train(const gcc_cls_head_args *args, void *stream)
 int32_t gcc_cls_head_eval(const gcc_cls_head_args *args, void *stream)
 {
     return launch_head<false>("gcc_cls_head_eval", args, stream);
-}
-
-int32_t gcc_adam_clipvalue_step(float *param, float *grad, float *exp_avg, float *exp_avg_sq, int64_t n, float lr,
-                                float beta1, float beta2, float eps, float weight_decay, int32_t step, float clip_value,
-                                float grad_scale, void *stream)
-{
-    if (!param || !grad || !exp_avg || !exp_avg_sq || n < 1 || step < 1 || !(grad_scale > 0.f)) {
-        snprintf(g_err, kErrLen, "gcc_adam_clipvalue_step: bad argument");
-        return -1;
-    }
-    const float bc1 = 1.0f - powf(beta1, (float)step);            // exactly gcc_adam_step's host arithmetic
-    const float bc2_sqrt = sqrtf(1.0f - powf(beta2, (float)step));
-    int blocks = (int)((n + 255) / 256);
-    if (blocks > 512) blocks = 512;
-    hipLaunchKernelGGL(adam_clipvalue_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, param, grad, exp_avg,
-                       exp_avg_sq, n, lr, beta1, beta2, eps, weight_decay, bc1, bc2_sqrt, clip_value, grad_scale);
-    return hipGetLastError() == hipSuccess ? 0 : -10;
 }
 
 }  // extern "C"

@@ -1,8 +1,8 @@
-// gcc_amd/csrc/nce.hip -- MoCo / InfoNCE head, queue enqueue, EMA (gfx950).
+// gcc_amd/csrc/nce.hip -- MoCo / InfoNCE head (gfx950).
 //
-// Replaces MemoryMoCo.forward (gcc/contrastive/memory_moco.py:26-63: bmm/mm/cat/div/
-// clone/index_copy_), NCESoftmaxLoss / NCESoftmaxLossNS (gcc/contrastive/criterions.py:5-33:
-// CrossEntropyLoss over [B, K+1]) and moment_update (train.py:169-172).
+// Replaces MemoryMoCo.forward (gcc/contrastive/memory_moco.py:26-63: bmm/mm/cat/div/clone) and
+// NCESoftmaxLoss / NCESoftmaxLossNS (gcc/contrastive/criterions.py:5-33: CrossEntropyLoss over
+// [B, K+1]).  The queue's enqueue (index_copy_) and moment_update are step_tail.hip's.
 //
 //   (dtype GCC_NCE_BF16: the same kernels with q / k / queue rounded to bf16 on load -- the forward logits then run on
 //   v_mfma_f32_16x16x32_bf16, 2 instructions per 16 x 16 tile instead of 16; accumulation and softmax stay fp32)
@@ -539,283 +539,6 @@ __global__ __launch_bounds__(kThreads) void nce_dq_kernel(NceDev a)
     st4(a.dq + (int64_t)b * D + c4, o);
 }
 
-__global__ __launch_bounds__(kThreads) void queue_enqueue_kernel(float *mem, int K, const float *keys, int nkeys,
-                                                                 int index, float *saved, const gcc_step_scalars *sc)
-{
-    TRAIN_STEP_WAVE_PRIORITY();
-    if (sc) index = sc->enqueue_index % K;                    // replayed step: the ring pointer lives on the device
-    const int gid = (int)blockIdx.x * kThreads + (int)threadIdx.x;
-    const int i = gid >> 4, c4 = (gid & 15) * 4;
-    if (i >= nkeys) return;
-    const int row = (index + i) % K;                          // torch.fmod(out_ids + index, queueSize)
-    if (saved) st4(saved + (int64_t)i * D + c4, ld4(mem + (int64_t)row * D + c4));
-    st4(mem + (int64_t)row * D + c4, ld4(keys + (int64_t)i * D + c4));
-}
-
-__global__ __launch_bounds__(kThreads) void ema_kernel(float *ema, const float *p, int64_t n, float m)
-{
-    TRAIN_STEP_WAVE_PRIORITY();
-    const int64_t stride = (int64_t)gridDim.x * kThreads;
-    for (int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x; i < n; i += stride)
-        ema[i] = ema[i] * m + (1.f - m) * p[i];               // p2.mul_(m).add_(1 - m, p1)
-}
-
-// ---- clip_grad_norm_ + Adam over one flat buffer (train.py:409,417)
-constexpr int kNormBlocks = 32;
-// sum of squares of the flat gradient: kNormBlocks partial sums; the workgroup that arrives last adds them up in index
-// order (deterministic).  scratch: [0] = result, [1] = ticket (as int), [2 .. 2 + kNormBlocks) = partials.
-__global__ __launch_bounds__(kThreads) void gradnorm_kernel(const float *g, int64_t n, double *scratch)
-{
-    TRAIN_STEP_WAVE_PRIORITY();
-    static_assert(kNormBlocks <= 64, "the last workgroup adds the partials up with one wave");
-    __shared__ double red[kThreads / 64];
-    __shared__ int last;
-    const int tid = (int)threadIdx.x;
-    double s = 0.0;
-    // 8 independent loads per round (clamped address, masked afterwards): one element per round was a dependent round
-    // trip per element, ~12 in a row for the 100 k parameters of the GIN encoder
-    const int64_t stride = (int64_t)gridDim.x * kThreads;
-    for (int64_t base = (int64_t)blockIdx.x * kThreads + tid; base < n; base += 8 * stride) {
-        float x[8];
-#pragma unroll
-        for (int u = 0; u < 8; ++u) { const int64_t i = base + u * stride; x[u] = g[i < n ? i : n - 1]; }
-#pragma unroll
-        for (int u = 0; u < 8; ++u) if (base + u * stride < n) s += (double)x[u] * (double)x[u];
-    }
-    s = wave_sum(s);
-    if ((tid & 63) == 0) red[tid >> 6] = s;
-    __syncthreads();
-    if (tid == 0) {
-        double t = 0.0;
-        for (int i = 0; i < kThreads / 64; ++i) t += red[i];
-        scratch[2 + blockIdx.x] = t;
-        device_fence();
-        last = atomicAdd((int *)(scratch + 1), 1) == (int)gridDim.x - 1;
-    }
-    __syncthreads();
-    if (last && tid < 64) {                                  // block-uniform; one wave: the partials in one round trip, fixed tree
-        device_fence();
-        const double v = tid < (int)gridDim.x ? load_fresh_f64(scratch + 2 + tid) : 0.0;
-        const double tot = wave_sum(v);
-        if (tid == 0) {
-            scratch[0] = tot;
-            *(int *)(scratch + 1) = 0;
-        }
-    }
-}
-
-// optional extras of the Adam launch (gcc_adam_ema_step): the EMA copy of the parameters and the per-step meters
-struct AdamExtras {
-    float *ema; int64_t n_ema; float ema_m;
-    const gcc_step_scalars *sc;      // replayed step: lr and the bias corrections come from here
-    double *acc; int32_t *mx; const float *loss, *prob; const int32_t *node_off_q, *edge_off_q, *node_off_k; int32_t B;
-    // gcc_adam_ema_enqueue_step_scalars: the sum of squares as per-workgroup partials of gin_grad_final_kernel (instead of
-    // sumsq[0] of a gradnorm_kernel launch), and the queue's enqueue as workgroups >= adam_blocks of this launch
-    const double *parts; int32_t nparts;
-    float *q_mem; const float *q_keys; int32_t q_K, q_nkeys, adam_blocks;
-};
-
-__global__ __launch_bounds__(kThreads) void adam_kernel(float *p, float *g, float *m, float *v, int64_t n, float lr,
-                                                        float b1, float b2, float eps, float wd, float bc1,
-                                                        float bc2_sqrt, float max_norm, float grad_scale,
-                                                        const double *sumsq, float *grad_norm, AdamExtras x)
-{
-    TRAIN_STEP_WAVE_PRIORITY();
-    const int nblk = x.q_mem ? x.adam_blocks : (int)gridDim.x;
-    if ((int)blockIdx.x >= nblk) {                             // (block-uniform) queue_enqueue_kernel's rows, ring pointer from the device
-        const int gid = ((int)blockIdx.x - nblk) * kThreads + (int)threadIdx.x;
-        const int i = gid >> 4, c4 = (gid & 15) * 4;
-        if (i >= x.q_nkeys) return;
-        const int row = (x.sc->enqueue_index % x.q_K + i) % x.q_K;                 // torch.fmod(out_ids + index, queueSize)
-        st4(x.q_mem + (int64_t)row * D + c4, ld4(x.q_keys + (int64_t)i * D + c4));
-        return;
-    }
-    // grad_scale: the 1 / world of a summed (all-reduced) gradient, folded in here instead of a launch of its own
-    double ss = 0.0;
-    double pv[4] = {0.0, 0.0, 0.0, 0.0};
-    if (x.parts) {                                             // (uniform) the partials: one round trip, with the first element's
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            const int idx = (int)threadIdx.x + kThreads * u;
-            pv[u] = x.parts[idx < x.nparts ? idx : x.nparts - 1];
-        }
-    } else {
-        ss = sumsq[0];
-    }
-    if (x.sc) { lr = x.sc->lr; bc1 = x.sc->bias_corr1; bc2_sqrt = x.sc->bias_corr2_sqrt; }   // (uniform: one scalar load, in flight with the rest)
-    // this thread's first element rides in the same round trip as the norm
-    const int64_t stride = (int64_t)nblk * kThreads, i0 = (int64_t)blockIdx.x * kThreads + threadIdx.x;
-    const int64_t ic = i0 < n ? i0 : n - 1;
-    float g0 = g[ic], p0 = p[ic], m0 = m[ic], v0 = v[ic];
-    const float e0 = x.ema ? x.ema[i0 < x.n_ema ? i0 : x.n_ema - 1] : 0.f;      // (block-uniform branch)
-    if (x.parts) {
-        // every workgroup adds ALL partials up in the same fixed order (thread t: partials t, t + 256, ..; wave tree; waves 0..3):
-        // the same bits in every workgroup, no ticket and no last-arrival pass
-        __shared__ double red[kThreads / 64];
-        double t = 0.0;
-#pragma unroll
-        for (int u = 0; u < 4; ++u) if ((int)threadIdx.x + kThreads * u < x.nparts) t += pv[u];
-        for (int idx = (int)threadIdx.x + 4 * kThreads; idx < x.nparts; idx += kThreads) t += x.parts[idx];
-        t = wave_sum(t);
-        if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = t;
-        __syncthreads();
-        ss = (red[0] + red[1]) + (red[2] + red[3]);
-    }
-    const float norm = grad_scale * (float)sqrt(ss);
-    float coef = 1.f;
-    if (max_norm > 0.f) {                                      // torch.nn.utils.clip_grad_norm_
-        coef = max_norm / (norm + 1e-6f);
-        coef = coef > 1.f ? 1.f : coef;
-    }
-    if (blockIdx.x == 0 && threadIdx.x == 0) {
-        grad_norm[0] = norm;
-        if (x.acc) {                                           // train.py:418-428's meters (gcc_step_meters)
-            const int32_t nq = x.node_off_q[x.B], nk = x.node_off_k[x.B], eq = x.edge_off_q[x.B];
-            x.acc[0] += (double)x.loss[0];
-            x.acc[1] += (double)x.prob[0];
-            x.acc[2] += (double)norm;
-            x.acc[3] += (double)nq + (double)nk;
-            x.acc[4] += 1.0;
-            x.mx[0] = nq > x.mx[0] ? nq : x.mx[0];
-            x.mx[1] = eq > x.mx[1] ? eq : x.mx[1];
-        }
-    }
-    coef *= grad_scale;
-    const int64_t nmax = x.ema && x.n_ema > n ? x.n_ema : n;
-    for (int64_t i = i0; i < nmax; i += stride) {
-        float pi, ei = 0.f;
-        if (i != i0) {
-            const int64_t j = i < n ? i : n - 1;
-            g0 = g[j]; p0 = p[j]; m0 = m[j]; v0 = v[j];
-            if (x.ema) ei = x.ema[i < x.n_ema ? i : x.n_ema - 1];
-        } else {
-            ei = e0;
-        }
-        if (i < n) {
-            const float gc = g0 * coef;
-            g[i] = gc;                                         // the clipped gradient stays visible, as in torch
-            const float gi = fmaf(wd, p0, gc);                 // weight_decay: grad = grad + wd * param
-            const float mi = fmaf(b1, m0, (1.f - b1) * gi);
-            const float vi = fmaf(b2, v0, (1.f - b2) * gi * gi);
-            m[i] = mi;
-            v[i] = vi;
-            const float denom = sqrtf(vi) / bc2_sqrt + eps;
-            pi = p0 - (lr / bc1) * (mi / denom);
-            p[i] = pi;
-        } else {
-            pi = p[i];                                         // parameters past the live prefix: only averaged
-        }
-        if (x.ema && i < x.n_ema) x.ema[i] = ei * x.ema_m + (1.f - x.ema_m) * pi;   // p2.mul_(m).add_(1 - m, p1), train.py:169-172
-    }
-}
-
-// ---- --optimizer sgd / adagrad (train.py:658-679) over the same flat buffers: adam_kernel's unfolded tail (the sum of squares
-// from a gradnorm_kernel launch; the enqueue stays a launch of its own) with torch.optim.SGD's / torch.optim.Adagrad's update.
-// ``s``: the momentum buffer / the sum of squared gradients; ``hyper``: the momentum / eps; ``lr``: Adagrad's clr of this step
-// (lr / (1 + (t - 1) lr_decay), formed by the host in double as torch forms it).  x.parts / x.q_mem are not used here.
-template <int kRule>
-__device__ __forceinline__ float opt_update(float p0, float gc, float s0, float lr, float hyper, float wd, float &s1)
-{
-    const float gi = fmaf(wd, p0, gc);                         // weight_decay: grad = grad + wd * param (after the clip, as torch)
-    if (kRule == GCC_OPT_SGD) {
-        s1 = fmaf(hyper, s0, gi);                              // buf.mul_(momentum).add_(grad); buf = 0 gives torch's first step
-        return fmaf(-lr, s1, p0);                              // param.add_(buf, alpha=-lr)
-    }
-    s1 = fmaf(gi, gi, s0);                                     // state_sum.addcmul_(grad, grad)
-    return p0 - lr * gi / (sqrtf(s1) + hyper);                 // param.addcdiv_(grad, sqrt(sum) + eps, value=-clr): 0 / eps = 0
-}
-
-template <int kRule>
-__global__ __launch_bounds__(kThreads) void opt_kernel(float *p, float *g, float *s, int64_t n, float lr, float hyper, float wd,
-                                                       float max_norm, float grad_scale, const double *sumsq, float *grad_norm,
-                                                       AdamExtras x)
-{
-    TRAIN_STEP_WAVE_PRIORITY();
-    const double ss = sumsq[0];
-    if (x.sc) lr = x.sc->lr;                                   // (uniform: one scalar load, in flight with the rest)
-    // this thread's first element rides in the same round trip as the norm
-    const int64_t stride = (int64_t)gridDim.x * kThreads, i0 = (int64_t)blockIdx.x * kThreads + threadIdx.x;
-    const int64_t ic = i0 < n ? i0 : n - 1;
-    float g0 = g[ic], p0 = p[ic], s0 = s[ic];
-    const float e0 = x.ema ? x.ema[i0 < x.n_ema ? i0 : x.n_ema - 1] : 0.f;      // (block-uniform branch)
-    const float norm = grad_scale * (float)sqrt(ss);
-    float coef = 1.f;
-    if (max_norm > 0.f) {                                      // torch.nn.utils.clip_grad_norm_
-        coef = max_norm / (norm + 1e-6f);
-        coef = coef > 1.f ? 1.f : coef;
-    }
-    if (blockIdx.x == 0 && threadIdx.x == 0) {
-        grad_norm[0] = norm;
-        if (x.acc) {                                           // train.py:418-428's meters (gcc_step_meters)
-            const int32_t nq = x.node_off_q[x.B], nk = x.node_off_k[x.B], eq = x.edge_off_q[x.B];
-            x.acc[0] += (double)x.loss[0];
-            x.acc[1] += (double)x.prob[0];
-            x.acc[2] += (double)norm;
-            x.acc[3] += (double)nq + (double)nk;
-            x.acc[4] += 1.0;
-            x.mx[0] = nq > x.mx[0] ? nq : x.mx[0];
-            x.mx[1] = eq > x.mx[1] ? eq : x.mx[1];
-        }
-    }
-    coef *= grad_scale;
-    const int64_t nmax = x.ema && x.n_ema > n ? x.n_ema : n;
-    for (int64_t i = i0; i < nmax; i += stride) {
-        float pi, ei = 0.f;
-        if (i != i0) {
-            const int64_t j = i < n ? i : n - 1;
-            g0 = g[j]; p0 = p[j]; s0 = s[j];
-            if (x.ema) ei = x.ema[i < x.n_ema ? i : x.n_ema - 1];
-        } else {
-            ei = e0;
-        }
-        if (i < n) {
-            const float gc = g0 * coef;
-            g[i] = gc;                                         // the clipped gradient stays visible, as in torch
-            float si;
-            pi = opt_update<kRule>(p0, gc, s0, lr, hyper, wd, si);
-            s[i] = si;
-            p[i] = pi;
-        } else {
-            pi = p[i];                                         // parameters past the live prefix: only averaged
-        }
-        if (x.ema && i < x.n_ema) x.ema[i] = ei * x.ema_m + (1.f - x.ema_m) * pi;   // p2.mul_(m).add_(1 - m, p1), train.py:169-172
-    }
-}
-
-// clip_grad_value_ + the same two rules: the fine-tuning tail (gcc_adam_clipvalue_step's twin), one launch, no norm pass
-template <int kRule>
-__global__ __launch_bounds__(kThreads) void opt_clipvalue_kernel(float *p, float *g, float *s, int64_t n, float lr, float hyper,
-                                                                 float wd, float clip, float grad_scale)
-{
-    TRAIN_STEP_WAVE_PRIORITY();
-    const int64_t stride = (int64_t)gridDim.x * kThreads;
-    for (int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x; i < n; i += stride) {
-        float gc = g[i] * grad_scale;
-        if (clip > 0.f) gc = gc < -clip ? -clip : (gc > clip ? clip : gc);   // clip_grad_value_ (NaN passes, as clamp_)
-        g[i] = gc;                                           // the clipped gradient stays visible, as in torch
-        float si;
-        p[i] = opt_update<kRule>(p[i], gc, s[i], lr, hyper, wd, si);
-        s[i] = si;
-    }
-}
-
-// ---- per-step meters of train.py:418-428 (loss / prob / gnorm / graph sizes) accumulated on the device: one thread
-__global__ void step_meters_kernel(double *acc, int32_t *mx, const float *loss, const float *prob, const float *gnorm,
-                                   const int32_t *node_off_q, const int32_t *edge_off_q, const int32_t *node_off_k,
-                                   int32_t B)
-{
-    TRAIN_STEP_WAVE_PRIORITY();
-    if (threadIdx.x != 0 || blockIdx.x != 0) return;
-    const int32_t nq = node_off_q[B], nk = node_off_k[B], eq = edge_off_q[B];
-    acc[0] += (double)loss[0];
-    acc[1] += (double)prob[0];
-    acc[2] += (double)gnorm[0];
-    acc[3] += (double)nq + (double)nk;
-    acc[4] += 1.0;
-    mx[0] = nq > mx[0] ? nq : mx[0];
-    mx[1] = eq > mx[1] ? eq : mx[1];
-}
-
 inline int fill_dev(const gcc_nce_args *a, void *workspace, int64_t workspace_bytes, NceDev &d, Plan &pl)
 {
     if (!a || !a->q || !a->mem || a->B < 1 || a->K < 1 || (a->pos_mode != 1 && !a->k) ||
@@ -917,307 +640,6 @@ int32_t gcc_nce_forward_backward(const gcc_nce_args *a, const float *dloss, floa
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) { snprintf(g_err, kErrLen, "gcc_nce_forward_backward: %s", hipGetErrorString(e)); return -10; }
     return 0;
-}
-
-int32_t gcc_queue_enqueue(float *mem, int32_t K, const float *keys, int32_t nkeys, int32_t index, float *saved,
-                          void *stream)
-{
-    if (!mem || !keys || K < 1 || nkeys < 1 || nkeys > K || index < 0 || index >= K) {
-        snprintf(g_err, kErrLen, "gcc_queue_enqueue: bad argument (K=%d n=%d index=%d)", K, nkeys, index);
-        return -1;
-    }
-    hipLaunchKernelGGL(queue_enqueue_kernel, dim3((nkeys * 16 + kThreads - 1) / kThreads), dim3(kThreads), 0,
-                       (hipStream_t)stream, mem, K, keys, nkeys, index, saved, (const gcc_step_scalars *)nullptr);
-    return hipGetLastError() == hipSuccess ? 0 : -10;
-}
-
-int32_t gcc_queue_enqueue_scalars(float *mem, int32_t K, const float *keys, int32_t nkeys, const gcc_step_scalars *scalars,
-                                  void *stream)
-{
-    if (!mem || !keys || !scalars || K < 1 || nkeys < 1 || nkeys > K) {
-        snprintf(g_err, kErrLen, "gcc_queue_enqueue_scalars: bad argument (K=%d n=%d)", K, nkeys);
-        return -1;
-    }
-    hipLaunchKernelGGL(queue_enqueue_kernel, dim3((nkeys * 16 + kThreads - 1) / kThreads), dim3(kThreads), 0,
-                       (hipStream_t)stream, mem, K, keys, nkeys, 0, (float *)nullptr, scalars);
-    return hipGetLastError() == hipSuccess ? 0 : -10;
-}
-
-__global__ void step_scalars_kernel(gcc_step_scalars *dev, gcc_step_scalars v) { *dev = v; }
-
-// one thread: ring entry (*counter mod ring_len) of the host-pinned ring -> the device struct; the entry was written by plain
-// host stores before this launch was submitted, and is read word by word with system-scope loads (the ring's lines are
-// reused every ring_len steps: nothing may be served from a stale cache line)
-__global__ void step_scalars_fetch_kernel(gcc_step_scalars *dev, const gcc_step_scalars *ring, int ring_len,
-                                          unsigned long long *counter)
-{
-    const unsigned long long n = *counter;
-    const uint32_t *src = (const uint32_t *)(ring + (n % (unsigned long long)ring_len));
-    uint32_t *dst = (uint32_t *)dev;
-#pragma unroll
-    for (int i = 0; i < (int)(sizeof(gcc_step_scalars) / 4); ++i) dst[i] = load_system_u32(src + i);
-    *counter = n + 1;
-}
-
-static void fill_scalars(gcc_step_scalars &v, float lr, float beta1, float beta2, int32_t adam_step, int32_t enqueue_index,
-                         uint64_t dropout_seed)
-{
-    v.lr = lr;
-    v.bias_corr1 = 1.0f - powf(beta1, (float)adam_step);          // exactly gcc_adam_step's host arithmetic
-    v.bias_corr2_sqrt = sqrtf(1.0f - powf(beta2, (float)adam_step));
-    v.enqueue_index = enqueue_index;
-    v.dropout_seed = dropout_seed;
-}
-
-void gcc_step_scalars_fill(gcc_step_scalars *host_entry, float lr, float beta1, float beta2, int32_t adam_step,
-                           int32_t enqueue_index, uint64_t dropout_seed)
-{
-    gcc_step_scalars v;
-    fill_scalars(v, lr, beta1, beta2, adam_step, enqueue_index, dropout_seed);
-    memcpy(host_entry, &v, sizeof(v));
-    __atomic_thread_fence(__ATOMIC_RELEASE);                      // visible before the launch that follows is submitted
-}
-
-int32_t gcc_step_scalars_fetch(gcc_step_scalars *dev, const gcc_step_scalars *ring, int32_t ring_len,
-                               unsigned long long *counter, void *stream)
-{
-    if (!dev || !ring || !counter || ring_len < 1) {
-        snprintf(g_err, kErrLen, "gcc_step_scalars_fetch: bad argument");
-        return -1;
-    }
-    hipLaunchKernelGGL(step_scalars_fetch_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, dev, ring, (int)ring_len, counter);
-    return hipGetLastError() == hipSuccess ? 0 : -10;
-}
-
-int32_t gcc_step_scalars_set(gcc_step_scalars *dev, float lr, float beta1, float beta2, int32_t adam_step,
-                             int32_t enqueue_index, uint64_t dropout_seed, void *stream)
-{
-    if (!dev || adam_step < 1 || enqueue_index < 0) {
-        snprintf(g_err, kErrLen, "gcc_step_scalars_set: bad argument");
-        return -1;
-    }
-    gcc_step_scalars v;
-    fill_scalars(v, lr, beta1, beta2, adam_step, enqueue_index, dropout_seed);
-    hipLaunchKernelGGL(step_scalars_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, dev, v);
-    return hipGetLastError() == hipSuccess ? 0 : -10;
-}
-
-int32_t gcc_adam_step(float *param, float *grad, float *exp_avg, float *exp_avg_sq, int64_t n, float lr,
-                      float beta1, float beta2, float eps, float weight_decay, int32_t step, float max_norm,
-                      float grad_scale, float *grad_norm, double *scratch, void *stream)
-{
-    if (!param || !grad || !exp_avg || !exp_avg_sq || !grad_norm || !scratch || n < 1 || step < 1 || !(grad_scale > 0.f)) {
-        snprintf(g_err, kErrLen, "gcc_adam_step: bad argument");
-        return -1;
-    }
-    hipStream_t s = (hipStream_t)stream;
-    const float bc1 = 1.0f - powf(beta1, (float)step);
-    const float bc2_sqrt = sqrtf(1.0f - powf(beta2, (float)step));
-    hipLaunchKernelGGL(gradnorm_kernel, dim3(kNormBlocks), dim3(kThreads), 0, s, (const float *)grad, n, scratch);
-    int blocks = (int)((n + kThreads - 1) / kThreads);
-    if (blocks > 512) blocks = 512;
-    const AdamExtras none = {};
-    hipLaunchKernelGGL(adam_kernel, dim3(blocks), dim3(kThreads), 0, s, param, grad, exp_avg, exp_avg_sq, n, lr, beta1,
-                       beta2, eps, weight_decay, bc1, bc2_sqrt, max_norm, grad_scale, (const double *)scratch, grad_norm, none);
-    return hipGetLastError() == hipSuccess ? 0 : -10;
-}
-
-struct AdamFold {            // gcc_adam_ema_enqueue_step_scalars
-    const double *parts; int32_t nparts;
-    float *q_mem; const float *q_keys; int32_t q_K, q_nkeys;
-};
-
-static int32_t adam_ema_launch(const char *who, float *param, float *grad, float *exp_avg, float *exp_avg_sq, int64_t n, float lr,
-                               float beta1, float beta2, float eps, float weight_decay, int32_t step, float max_norm,
-                               float grad_scale, float *grad_norm, double *scratch, float *ema, int64_t n_ema, float ema_m,
-                               const gcc_step_meters_args *meters, const gcc_step_scalars *scalars, void *stream,
-                               const AdamFold *fold = nullptr)
-{
-    if (!param || !grad || !exp_avg || !exp_avg_sq || !grad_norm || !scratch || n < 1 || (!scalars && step < 1) || !(grad_scale > 0.f) ||
-        (ema && n_ema < n) ||
-        (meters && (!meters->acc || !meters->mx || !meters->loss || !meters->prob || !meters->node_off_q ||
-                    !meters->edge_off_q || !meters->node_off_k || meters->batch_size < 1))) {
-        snprintf(g_err, kErrLen, "%s: bad argument", who);
-        return -1;
-    }
-    hipStream_t s = (hipStream_t)stream;
-    const float bc1 = scalars ? 1.f : 1.0f - powf(beta1, (float)step);
-    const float bc2_sqrt = scalars ? 1.f : sqrtf(1.0f - powf(beta2, (float)step));
-    if (!fold || !fold->parts)
-        hipLaunchKernelGGL(gradnorm_kernel, dim3(kNormBlocks), dim3(kThreads), 0, s, (const float *)grad, n, scratch);
-    AdamExtras x = {};
-    x.sc = scalars;
-    if (ema) { x.ema = ema; x.n_ema = n_ema; x.ema_m = ema_m; }
-    if (meters) {
-        x.acc = meters->acc; x.mx = meters->mx; x.loss = meters->loss; x.prob = meters->prob;
-        x.node_off_q = meters->node_off_q; x.edge_off_q = meters->edge_off_q; x.node_off_k = meters->node_off_k;
-        x.B = meters->batch_size;
-    }
-    const int64_t nmax = ema ? n_ema : n;
-    int blocks = (int)((nmax + kThreads - 1) / kThreads);
-    if (blocks > 512) blocks = 512;
-    int extra = 0;
-    if (fold) {
-        x.parts = fold->parts; x.nparts = fold->nparts;
-        if (fold->q_mem) {
-            x.q_mem = fold->q_mem; x.q_keys = fold->q_keys; x.q_K = fold->q_K; x.q_nkeys = fold->q_nkeys; x.adam_blocks = blocks;
-            extra = (fold->q_nkeys * 16 + kThreads - 1) / kThreads;
-        }
-    }
-    hipLaunchKernelGGL(adam_kernel, dim3(blocks + extra), dim3(kThreads), 0, s, param, grad, exp_avg, exp_avg_sq, n, lr, beta1,
-                       beta2, eps, weight_decay, bc1, bc2_sqrt, max_norm, grad_scale, (const double *)scratch, grad_norm, x);
-    return hipGetLastError() == hipSuccess ? 0 : -10;
-}
-
-int32_t gcc_adam_ema_step(float *param, float *grad, float *exp_avg, float *exp_avg_sq, int64_t n, float lr,
-                          float beta1, float beta2, float eps, float weight_decay, int32_t step, float max_norm,
-                          float grad_scale, float *grad_norm, double *scratch, float *ema, int64_t n_ema, float ema_m,
-                          const gcc_step_meters_args *meters, void *stream)
-{
-    return adam_ema_launch("gcc_adam_ema_step", param, grad, exp_avg, exp_avg_sq, n, lr, beta1, beta2, eps, weight_decay, step,
-                           max_norm, grad_scale, grad_norm, scratch, ema, n_ema, ema_m, meters, nullptr, stream);
-}
-
-int32_t gcc_adam_ema_step_scalars(float *param, float *grad, float *exp_avg, float *exp_avg_sq, int64_t n,
-                                  float beta1, float beta2, float eps, float weight_decay, float max_norm,
-                                  float grad_scale, float *grad_norm, double *scratch, float *ema, int64_t n_ema, float ema_m,
-                                  const gcc_step_meters_args *meters, const gcc_step_scalars *scalars, void *stream)
-{
-    if (!scalars) { snprintf(g_err, kErrLen, "gcc_adam_ema_step_scalars: scalars is NULL"); return -1; }
-    return adam_ema_launch("gcc_adam_ema_step_scalars", param, grad, exp_avg, exp_avg_sq, n, 0.f, beta1, beta2, eps, weight_decay,
-                           0, max_norm, grad_scale, grad_norm, scratch, ema, n_ema, ema_m, meters, scalars, stream);
-}
-
-int32_t gcc_adam_ema_enqueue_step_scalars(float *param, float *grad, float *exp_avg, float *exp_avg_sq, int64_t n,
-                                          float beta1, float beta2, float eps, float weight_decay, float max_norm,
-                                          float grad_scale, float *grad_norm, double *scratch, float *ema, int64_t n_ema, float ema_m,
-                                          const gcc_step_meters_args *meters, const gcc_step_scalars *scalars,
-                                          const double *sumsq_parts, int32_t nparts, float *queue, int32_t K, const float *keys,
-                                          int32_t nkeys, void *stream)
-{
-    const char *who = "gcc_adam_ema_enqueue_step_scalars";
-    if (!scalars) { snprintf(g_err, kErrLen, "%s: scalars is NULL", who); return -1; }
-    if ((sumsq_parts && nparts < 1) || (!sumsq_parts && nparts != 0) || (queue && (!keys || K < 1 || nkeys < 1 || nkeys > K)) ||
-        (!sumsq_parts && !queue)) {
-        snprintf(g_err, kErrLen, "%s: bad argument (nparts=%d K=%d n=%d)", who, nparts, K, nkeys);
-        return -1;
-    }
-    const AdamFold fold = {sumsq_parts, nparts, queue, keys, K, nkeys};
-    return adam_ema_launch(who, param, grad, exp_avg, exp_avg_sq, n, 0.f, beta1, beta2, eps, weight_decay, 0, max_norm, grad_scale,
-                           grad_norm, scratch, ema, n_ema, ema_m, meters, scalars, stream, &fold);
-}
-
-static int32_t opt_check(const char *who, int32_t rule, const float *param, const float *grad, const float *state, int64_t n,
-                         float grad_scale)
-{
-    if (rule != GCC_OPT_SGD && rule != GCC_OPT_ADAGRAD) {
-        snprintf(g_err, kErrLen, "%s: unknown rule %d (GCC_OPT_SGD = 1, GCC_OPT_ADAGRAD = 2)", who, rule);
-        return -2;
-    }
-    if (n < 1) { snprintf(g_err, kErrLen, "%s: n = %lld, at least one element is needed", who, (long long)n); return -1; }
-    if (!param || !grad || !state) {
-        snprintf(g_err, kErrLen, "%s: %s is NULL", who, !param ? "param" : !grad ? "grad" : "state");
-        return -1;
-    }
-    if (!(grad_scale > 0.f)) { snprintf(g_err, kErrLen, "%s: grad_scale must be positive", who); return -1; }
-    return 0;
-}
-
-static int32_t opt_launch(const char *who, int32_t rule, float *param, float *grad, float *state, int64_t n, float lr, float hyper,
-                          float weight_decay, float max_norm, float grad_scale, float *grad_norm, double *scratch, float *ema,
-                          int64_t n_ema, float ema_m, const gcc_step_meters_args *meters, const gcc_step_scalars *scalars,
-                          void *stream)
-{
-    const int32_t rc = opt_check(who, rule, param, grad, state, n, grad_scale);
-    if (rc) return rc;
-    if (!grad_norm || !scratch || (ema && n_ema < n) ||
-        (meters && (!meters->acc || !meters->mx || !meters->loss || !meters->prob || !meters->node_off_q ||
-                    !meters->edge_off_q || !meters->node_off_k || meters->batch_size < 1))) {
-        snprintf(g_err, kErrLen, "%s: bad argument (grad_norm / scratch NULL, n_ema < n, or an incomplete meters struct)", who);
-        return -1;
-    }
-    hipStream_t s = (hipStream_t)stream;
-    hipLaunchKernelGGL(gradnorm_kernel, dim3(kNormBlocks), dim3(kThreads), 0, s, (const float *)grad, n, scratch);
-    AdamExtras x = {};
-    x.sc = scalars;
-    if (ema) { x.ema = ema; x.n_ema = n_ema; x.ema_m = ema_m; }
-    if (meters) {
-        x.acc = meters->acc; x.mx = meters->mx; x.loss = meters->loss; x.prob = meters->prob;
-        x.node_off_q = meters->node_off_q; x.edge_off_q = meters->edge_off_q; x.node_off_k = meters->node_off_k;
-        x.B = meters->batch_size;
-    }
-    const int64_t nmax = ema ? n_ema : n;
-    int blocks = (int)((nmax + kThreads - 1) / kThreads);
-    if (blocks > 512) blocks = 512;
-    if (rule == GCC_OPT_SGD)
-        hipLaunchKernelGGL(opt_kernel<GCC_OPT_SGD>, dim3(blocks), dim3(kThreads), 0, s, param, grad, state, n, lr, hyper, weight_decay,
-                           max_norm, grad_scale, (const double *)scratch, grad_norm, x);
-    else
-        hipLaunchKernelGGL(opt_kernel<GCC_OPT_ADAGRAD>, dim3(blocks), dim3(kThreads), 0, s, param, grad, state, n, lr, hyper,
-                           weight_decay, max_norm, grad_scale, (const double *)scratch, grad_norm, x);
-    return hipGetLastError() == hipSuccess ? 0 : -10;
-}
-
-int32_t gcc_opt_step(int32_t rule, float *param, float *grad, float *state, int64_t n, float lr, float hyper, float weight_decay,
-                     float max_norm, float grad_scale, float *grad_norm, double *scratch, void *stream)
-{
-    return opt_launch("gcc_opt_step", rule, param, grad, state, n, lr, hyper, weight_decay, max_norm, grad_scale, grad_norm, scratch,
-                      nullptr, 0, 0.f, nullptr, nullptr, stream);
-}
-
-int32_t gcc_opt_ema_step(int32_t rule, float *param, float *grad, float *state, int64_t n, float lr, float hyper, float weight_decay,
-                         float max_norm, float grad_scale, float *grad_norm, double *scratch, float *ema, int64_t n_ema, float ema_m,
-                         const gcc_step_meters_args *meters, void *stream)
-{
-    return opt_launch("gcc_opt_ema_step", rule, param, grad, state, n, lr, hyper, weight_decay, max_norm, grad_scale, grad_norm,
-                      scratch, ema, n_ema, ema_m, meters, nullptr, stream);
-}
-
-int32_t gcc_opt_ema_step_scalars(int32_t rule, float *param, float *grad, float *state, int64_t n, float hyper, float weight_decay,
-                                 float max_norm, float grad_scale, float *grad_norm, double *scratch, float *ema, int64_t n_ema,
-                                 float ema_m, const gcc_step_meters_args *meters, const gcc_step_scalars *scalars, void *stream)
-{
-    if (!scalars) { snprintf(g_err, kErrLen, "gcc_opt_ema_step_scalars: scalars is NULL"); return -1; }
-    return opt_launch("gcc_opt_ema_step_scalars", rule, param, grad, state, n, 0.f, hyper, weight_decay, max_norm, grad_scale,
-                      grad_norm, scratch, ema, n_ema, ema_m, meters, scalars, stream);
-}
-
-int32_t gcc_opt_clipvalue_step(int32_t rule, float *param, float *grad, float *state, int64_t n, float lr, float hyper,
-                               float weight_decay, float clip_value, float grad_scale, void *stream)
-{
-    const int32_t rc = opt_check("gcc_opt_clipvalue_step", rule, param, grad, state, n, grad_scale);
-    if (rc) return rc;
-    int blocks = (int)((n + kThreads - 1) / kThreads);
-    if (blocks > 512) blocks = 512;
-    if (rule == GCC_OPT_SGD)
-        hipLaunchKernelGGL(opt_clipvalue_kernel<GCC_OPT_SGD>, dim3(blocks), dim3(kThreads), 0, (hipStream_t)stream, param, grad, state,
-                           n, lr, hyper, weight_decay, clip_value, grad_scale);
-    else
-        hipLaunchKernelGGL(opt_clipvalue_kernel<GCC_OPT_ADAGRAD>, dim3(blocks), dim3(kThreads), 0, (hipStream_t)stream, param, grad,
-                           state, n, lr, hyper, weight_decay, clip_value, grad_scale);
-    return hipGetLastError() == hipSuccess ? 0 : -10;
-}
-
-int32_t gcc_step_meters(double *acc, int32_t *mx, const float *loss, const float *prob, const float *grad_norm,
-                        const int32_t *node_off_q, const int32_t *edge_off_q, const int32_t *node_off_k,
-                        int32_t batch_size, void *stream)
-{
-    if (!acc || !mx || !loss || !prob || !grad_norm || !node_off_q || !edge_off_q || !node_off_k || batch_size < 1) {
-        snprintf(g_err, kErrLen, "gcc_step_meters: bad argument");
-        return -1;
-    }
-    hipLaunchKernelGGL(step_meters_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, acc, mx, loss, prob, grad_norm,
-                       node_off_q, edge_off_q, node_off_k, batch_size);
-    return hipGetLastError() == hipSuccess ? 0 : -10;
-}
-
-int32_t gcc_ema_update(float *ema, const float *p, int64_t n, float m, void *stream)
-{
-    if (!ema || !p || n < 1) { snprintf(g_err, kErrLen, "gcc_ema_update: bad argument"); return -1; }
-    int blocks = (int)((n + kThreads - 1) / kThreads);
-    if (blocks > 1024) blocks = 1024;
-    hipLaunchKernelGGL(ema_kernel, dim3(blocks), dim3(kThreads), 0, (hipStream_t)stream, ema, p, n, m);
-    return hipGetLastError() == hipSuccess ? 0 : -10;
 }
 
 }  // extern "C"

@@ -25,7 +25,8 @@ from .train_step import OPT_RULES, FlatRuleState, flat_grad_views, flatten_param
 
 
 class ClsHeadEngine:
-    """C-ABI calls of the head and of clip-by-value Adam.  ``lib``/``ptr`` are injectable for the emulator tests only."""
+    """C-ABI calls of the head (csrc/cls_head.hip) and of the clip-by-value tail (csrc/step_tail.hip).  ``lib``/``ptr`` are
+    injectable for the emulator tests only."""
 
     def __init__(self, lib=None, ptr=None):
         self.lib = lib if lib is not None else _cabi.load()
@@ -68,56 +69,48 @@ class ClsHeadEngine:
         a.eval_loss_sum, a.eval_counts = self.ptr(loss_sum), self.ptr(counts)
         _cabi.call(self.lib, "gcc_cls_head_eval", ctypes.byref(a), stream)
 
+    def _clipvalue(self, rule, param, grad, states, lr, hyper, weight_decay, step, clip_value, grad_scale, stream):
+        """one clip-by-value tail (csrc/step_tail.hip): ``rule`` None = Adam (``states`` = (exp_avg, exp_avg_sq), ``hyper`` =
+        (beta1, beta2, eps), its ``step`` count), 1 = SGD (the momentum buffer; the momentum), 2 = Adagrad (the sum; eps)"""
+        ptr = self.ptr
+        _cabi.call(self.lib, "gcc_adam_clipvalue_step" if rule is None else "gcc_opt_clipvalue_step",
+                   *([] if rule is None else [int(rule)]), ptr(param), ptr(grad), *(ptr(s) for s in states), param.numel(), lr, *hyper,
+                   weight_decay, *([int(step)] if rule is None else []), clip_value, grad_scale, stream)
+
     def adam_clipvalue(self, param, grad, exp_avg, exp_avg_sq, lr, betas, eps, weight_decay, step, clip_value,
                        grad_scale=1.0, stream=None):
-        _cabi.call(self.lib, "gcc_adam_clipvalue_step", self.ptr(param), self.ptr(grad), self.ptr(exp_avg), self.ptr(exp_avg_sq),
-                   param.numel(), lr, betas[0], betas[1], eps, weight_decay, int(step),
-                   clip_value, grad_scale, stream)
+        self._clipvalue(None, param, grad, (exp_avg, exp_avg_sq), lr, (*betas, eps), weight_decay, step, clip_value, grad_scale, stream)
 
     def opt_clipvalue(self, rule, param, grad, state, lr, hyper, weight_decay, clip_value, grad_scale=1.0, stream=None):
         """gcc_opt_clipvalue_step: ``rule`` 1 = SGD (``state`` the momentum buffer, ``hyper`` the momentum), 2 = Adagrad (the sum
         of squares, eps; ``lr`` = the step's clr)"""
-        _cabi.call(self.lib, "gcc_opt_clipvalue_step", int(rule), self.ptr(param), self.ptr(grad), self.ptr(state), param.numel(),
-                   lr, hyper, weight_decay, clip_value, grad_scale, stream)
-
-
-class FlatAdamClipValue:
-    """clip_grad_value_(params, clip_value) + torch.optim.Adam(lr, betas, eps=1e-8, weight_decay) over one flat buffer
-    (train.py:232-246 of the reference), one launch.  ``param_groups`` / ``state_dict`` keep the shape train.py uses."""
-
-    def __init__(self, param, grad, lr, betas, weight_decay, clip_value, engine, eps=1e-8):
-        self.param, self.grad, self.engine = param, grad, engine
-        self.param_groups = [dict(lr=lr, betas=tuple(betas), eps=eps, weight_decay=weight_decay)]
-        self.clip_value = clip_value
-        self.exp_avg = torch.zeros_like(param)
-        self.exp_avg_sq = torch.zeros_like(param)
-        self.steps = 0
-
-    def step(self, stream=None):
-        g = self.param_groups[0]
-        self.steps += 1
-        self.engine.adam_clipvalue(self.param, self.grad, self.exp_avg, self.exp_avg_sq, g["lr"], g["betas"], g["eps"],
-                                   g["weight_decay"], self.steps, self.clip_value, stream=stream)
-
-    def zero_grad(self):
-        pass                 # the kernels overwrite the flat gradients
-
-    def state_dict(self):
-        return dict(state=dict(step=self.steps, exp_avg=self.exp_avg, exp_avg_sq=self.exp_avg_sq),
-                    param_groups=self.param_groups)
+        self._clipvalue(int(rule), param, grad, (state,), lr, (hyper,), weight_decay, 0, clip_value, grad_scale, stream)
 
 
 class _FlatClipValue(FlatRuleState):
-    """clip_grad_value_(params, clip_value) + the rule's update over one flat buffer, one launch (gcc_opt_clipvalue_step)"""
+    """clip_grad_value_(params, clip_value) + the rule's update over one flat buffer (train.py:232-246 of the reference), one
+    launch: gcc_adam_clipvalue_step / gcc_opt_clipvalue_step"""
 
     def __init__(self, rule, param, grad, lr, weight_decay, clip_value, engine, **hyper):
         super().__init__(rule, param, grad, lr, weight_decay, engine, **hyper)
         self.clip_value = clip_value
 
     def step(self, stream=None):
+        g = self.param_groups[0]
         self.steps += 1
-        self.engine.opt_clipvalue(OPT_RULES[self.rule], self.param, self.grad, self.state, self.rate(self.steps), self.hyper(),
-                                  self.param_groups[0]["weight_decay"], self.clip_value, stream=stream)
+        if self.rule == "adam":
+            self.engine.adam_clipvalue(self.param, self.grad, *self.states, g["lr"], g["betas"], g["eps"], g["weight_decay"],
+                                       self.steps, self.clip_value, stream=stream)
+        else:
+            self.engine.opt_clipvalue(OPT_RULES[self.rule], self.param, self.grad, self.state, self.rate(self.steps), self.hyper(),
+                                      g["weight_decay"], self.clip_value, stream=stream)
+
+
+class FlatAdamClipValue(_FlatClipValue):
+    """clip_grad_value_ + torch.optim.Adam(lr, betas, eps=1e-8, weight_decay) (train.py:232-246,667-672 of the reference)"""
+
+    def __init__(self, param, grad, lr, betas, weight_decay, clip_value, engine, eps=1e-8):
+        super().__init__("adam", param, grad, lr, weight_decay, clip_value, engine, betas=betas, eps=eps)
 
 
 class FlatSGDClipValue(_FlatClipValue):

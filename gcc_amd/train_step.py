@@ -321,114 +321,98 @@ def read_meters(trainer):
     return a, m
 
 
-class FlatAdam:
-    """clip_grad_norm_ + torch.optim.Adam(lr, betas, eps=1e-8, weight_decay) (train.py:409,667-672) over one flat
-    parameter buffer, as two HIP launches (gcc_adam_step).  ``param_groups`` / ``state_dict`` keep the shape
-    train.py expects (it sets ``param_group["lr"]`` every step and checkpoints ``optimizer.state_dict()``)."""
-
-    def __init__(self, param, grad, lr, betas, weight_decay, clip_norm, engine, eps=1e-8):
-        self.param, self.grad, self.engine = param, grad, engine
-        self.param_groups = [dict(lr=lr, betas=tuple(betas), eps=eps, weight_decay=weight_decay)]
-        self.clip_norm = clip_norm
-        self.exp_avg = torch.zeros_like(param)
-        self.exp_avg_sq = torch.zeros_like(param)
-        self.steps = 0
-        self.grad_norm = torch.zeros(1, dtype=torch.float32, device=param.device)
-        self._scratch = torch.zeros(64, dtype=torch.float64, device=param.device)
-        self.sumsq_parts = torch.zeros(4096, dtype=torch.float64, device=param.device)     # gin_grad_final's partials (folded step)
-
-    def step(self, grad_scale=1.0, ema=None, ema_src=None, ema_m=0.0, meters=None, scalars=None, sumsq_parts=None, enqueue=None):
-        """``sumsq_parts`` = (partials, count) left by the backward's last kernel instead of a sum-of-squares launch, ``enqueue`` =
-        (queue, keys) copied by extra workgroups of the Adam launch: both with ``scalars`` only (the single-GPU MoCo step).
-        ``grad_scale``: 1 / world when ``grad`` holds the SUM over ranks (folded into the two launches).
-        ``ema`` / ``ema_src`` / ``ema_m``: moment_update of the flat EMA buffer from the flat parameter buffer
-        (``param`` is its live prefix); ``meters`` = (acc, mx, loss, prob, graph_q, graph_k): one step of the
-        device-side meters -- both inside the Adam launch (gcc_adam_ema_step) instead of launches of their own."""
-        g = self.param_groups[0]
-        self.steps += 1
-        st = raw_stream(self.param)
-        if ema is None and meters is None and scalars is None:
-            self.engine.adam(self.param, self.grad, self.exp_avg, self.exp_avg_sq, g["lr"], g["betas"], g["eps"],
-                             g["weight_decay"], self.steps, self.clip_norm, self.grad_norm, self._scratch, stream=st,
-                             grad_scale=grad_scale)
-        else:
-            self.engine.adam_ema(self.param, self.grad, self.exp_avg, self.exp_avg_sq, g["lr"], g["betas"], g["eps"],
-                                 g["weight_decay"], self.steps, self.clip_norm, self.grad_norm, self._scratch, stream=st,
-                                 grad_scale=grad_scale, ema=ema, ema_src=ema_src, ema_m=ema_m, meters=meters, scalars=scalars,
-                                 **(dict(sumsq_parts=sumsq_parts, enqueue=enqueue) if sumsq_parts is not None or enqueue is not None else {}))
-        return self.grad_norm
-
-    def zero_grad(self):
-        pass                 # the backward kernels overwrite the flat gradient
-
-    def state_dict(self):
-        return dict(state=dict(step=self.steps, exp_avg=self.exp_avg, exp_avg_sq=self.exp_avg_sq),
-                    param_groups=self.param_groups)
-
-    def ring_scalars(self, lr):
-        """(rate, betas) of the NEXT step's entry in the scalars ring (:meth:`_GraphedStep._run_step`)"""
-        return lr, self.param_groups[0]["betas"]
-
-
-OPT_RULES = {"sgd": 1, "adagrad": 2}        # GCC_OPT_SGD, GCC_OPT_ADAGRAD
+OPT_RULES = {"sgd": 1, "adagrad": 2}        # GCC_OPT_SGD, GCC_OPT_ADAGRAD ("adam": the gcc_adam_* entry points)
 
 
 class FlatRuleState:
-    """What ``--optimizer sgd`` / ``adagrad`` (train.py:658-679) keep over one flat parameter buffer, whichever clip runs in
-    front: ``param_groups[0]`` in torch's shape (train.py sets ``["lr"]`` every step), ONE state tensor -- SGD's momentum buffer
-    or Adagrad's sum of squared gradients, both starting at 0: a zero buffer gives torch's first SGD step (buf = g) -- and the
-    host's step count.  Adagrad's rate of step t, clr = lr / (1 + (t - 1) lr_decay), is formed here in double, as torch forms it,
-    and handed to the kernel where Adam's lr goes."""
+    """What ``--optimizer adam`` / ``sgd`` / ``adagrad`` (train.py:658-679) keep over one flat parameter buffer, whichever clip
+    runs in front: ``param_groups[0]`` in torch's shape (train.py sets ``["lr"]`` every step and checkpoints ``state_dict()``),
+    the state tensors -- Adam's exp_avg / exp_avg_sq, SGD's momentum buffer or Adagrad's sum of squared gradients, all starting
+    at 0: a zero buffer gives torch's first SGD step (buf = g) -- and the host's step count.  Adagrad's rate of step t,
+    clr = lr / (1 + (t - 1) lr_decay), is formed here in double, as torch forms it, and handed to the kernel where Adam's lr goes."""
 
-    def __init__(self, rule, param, grad, lr, weight_decay, engine, momentum=0.0, lr_decay=0.0, eps=1e-10):
+    STATE_KEYS = dict(adam=("exp_avg", "exp_avg_sq"), sgd=("momentum_buffer",), adagrad=("sum",))
+
+    def __init__(self, rule, param, grad, lr, weight_decay, engine, betas=(0.9, 0.999), momentum=0.0, lr_decay=0.0, eps=1e-10):
         self.rule, self.param, self.grad, self.engine = rule, param, grad, engine
-        if rule == "sgd":                       # torch.optim.SGD(lr, momentum, weight_decay): dampening 0, no Nesterov
+        if rule == "adam":                      # torch.optim.Adam(lr, betas, eps, weight_decay)
+            self.param_groups = [dict(lr=lr, betas=tuple(betas), eps=eps, weight_decay=weight_decay)]
+        elif rule == "sgd":                     # torch.optim.SGD(lr, momentum, weight_decay): dampening 0, no Nesterov
             self.param_groups = [dict(lr=lr, momentum=momentum, weight_decay=weight_decay)]
-            self.state_key = "momentum_buffer"
         elif rule == "adagrad":                 # torch.optim.Adagrad(lr, lr_decay, weight_decay): accumulator from 0
             self.param_groups = [dict(lr=lr, lr_decay=lr_decay, eps=eps, weight_decay=weight_decay)]
-            self.state_key = "sum"
         else:
-            raise ValueError(f"unknown update rule {rule!r} (sgd, adagrad)")
-        self.state = torch.zeros_like(param)
+            raise ValueError(f"unknown update rule {rule!r} (adam, sgd, adagrad)")
+        self.states = tuple(torch.zeros_like(param) for _ in self.STATE_KEYS[rule])
+        self.state = self.states[0]
+        if rule == "adam":
+            self.exp_avg, self.exp_avg_sq = self.states
         self.steps = 0
 
     def rate(self, t):
         """the effective learning rate of step ``t`` (1-based)"""
         g = self.param_groups[0]
-        return g["lr"] if self.rule == "sgd" else g["lr"] / (1 + (t - 1) * g["lr_decay"])
+        return g["lr"] / (1 + (t - 1) * g["lr_decay"]) if self.rule == "adagrad" else g["lr"]
 
     def hyper(self):
         g = self.param_groups[0]
         return g["momentum"] if self.rule == "sgd" else g["eps"]
 
     def ring_scalars(self, lr):
+        """(rate, betas) of the NEXT step's entry in the scalars ring (:meth:`_GraphedStep._run_step`)"""
+        if self.rule == "adam":
+            return lr, self.param_groups[0]["betas"]
         return self.rate(self.steps + 1), (0.0, 0.0)       # (lr is in param_groups already; no bias corrections)
 
     def zero_grad(self):
         pass                 # the backward kernels overwrite the flat gradient
 
     def state_dict(self):
-        return dict(state={"step": self.steps, self.state_key: self.state}, param_groups=self.param_groups)
+        return dict(state=dict(step=self.steps, **dict(zip(self.STATE_KEYS[self.rule], self.states))), param_groups=self.param_groups)
 
 
 class _FlatClipNorm(FlatRuleState):
-    """clip_grad_norm_ + the rule's update as two HIP launches (gcc_opt_step / gcc_opt_ema_step[_scalars]): :class:`FlatAdam`'s
-    ``step`` signature without the folded single-GPU tail (the sum of squares stays a launch, the enqueue too)."""
+    """clip_grad_norm_ + the rule's update (train.py:409,417) as two HIP launches: gcc_adam_step / gcc_adam_ema_step[_scalars],
+    gcc_opt_step / gcc_opt_ema_step[_scalars]."""
 
     def __init__(self, rule, param, grad, lr, weight_decay, clip_norm, engine, **hyper):
         super().__init__(rule, param, grad, lr, weight_decay, engine, **hyper)
         self.clip_norm = clip_norm
         self.grad_norm = torch.zeros(1, dtype=torch.float32, device=param.device)
         self._scratch = torch.zeros(64, dtype=torch.float64, device=param.device)
+        if rule == "adam":
+            self.sumsq_parts = torch.zeros(4096, dtype=torch.float64, device=param.device)     # gin_grad_final's partials (folded step)
 
-    def step(self, grad_scale=1.0, ema=None, ema_src=None, ema_m=0.0, meters=None, scalars=None):
+    def step(self, grad_scale=1.0, ema=None, ema_src=None, ema_m=0.0, meters=None, scalars=None, sumsq_parts=None, enqueue=None):
+        """``sumsq_parts`` = (partials, count) left by the backward's last kernel instead of a sum-of-squares launch, ``enqueue`` =
+        (queue, keys) copied by extra workgroups of the update launch: both with ``scalars`` and Adam only (the single-GPU MoCo
+        step).  ``grad_scale``: 1 / world when ``grad`` holds the SUM over ranks (folded into the two launches).
+        ``ema`` / ``ema_src`` / ``ema_m``: moment_update of the flat EMA buffer from the flat parameter buffer
+        (``param`` is its live prefix); ``meters`` = (acc, mx, loss, prob, graph_q, graph_k): one step of the
+        device-side meters -- both inside the update launch instead of launches of their own."""
+        g, fold = self.param_groups[0], sumsq_parts is not None or enqueue is not None
         self.steps += 1
-        self.engine.opt_step(OPT_RULES[self.rule], self.param, self.grad, self.state, self.rate(self.steps), self.hyper(),
-                             self.param_groups[0]["weight_decay"], self.clip_norm, self.grad_norm, self._scratch,
-                             stream=raw_stream(self.param), grad_scale=grad_scale, ema=ema, ema_src=ema_src, ema_m=ema_m,
-                             meters=meters, scalars=scalars)
+        tail = (g["weight_decay"], self.clip_norm, self.grad_norm, self._scratch)
+        kw = dict(stream=raw_stream(self.param), grad_scale=grad_scale)
+        extras = dict(ema=ema, ema_src=ema_src, ema_m=ema_m, meters=meters, scalars=scalars)
+        if self.rule != "adam":
+            if fold:
+                raise ValueError("sumsq_parts / enqueue: the folded tail is Adam's")
+            self.engine.opt_step(OPT_RULES[self.rule], self.param, self.grad, self.state, self.rate(self.steps), self.hyper(),
+                                 *tail, **kw, **extras)
+        elif ema is None and meters is None and scalars is None:
+            self.engine.adam(self.param, self.grad, *self.states, g["lr"], g["betas"], g["eps"], tail[0], self.steps, *tail[1:], **kw)
+        else:
+            self.engine.adam_ema(self.param, self.grad, *self.states, g["lr"], g["betas"], g["eps"], tail[0], self.steps, *tail[1:],
+                                 **kw, **extras, **(dict(sumsq_parts=sumsq_parts, enqueue=enqueue) if fold else {}))
         return self.grad_norm
+
+
+class FlatAdam(_FlatClipNorm):
+    """clip_grad_norm_ + torch.optim.Adam(lr, betas, eps=1e-8, weight_decay) (train.py:409,667-672) over one flat buffer"""
+
+    def __init__(self, param, grad, lr, betas, weight_decay, clip_norm, engine, eps=1e-8):
+        super().__init__("adam", param, grad, lr, weight_decay, clip_norm, engine, betas=betas, eps=eps)
 
 
 class FlatSGD(_FlatClipNorm):
@@ -885,7 +869,7 @@ class MoCoTrainStep(_GraphedStep):
         self.nce = contrast.engine()
         # Adam(lr, betas, weight_decay as L2) over exactly the parameters that get gradients, train.py:667-672
         self.optimizer = flat_optimizer(optimizer, self.live, self.flat_grad, learning_rate, betas, weight_decay, clip_norm,
-                                        (flat_engine or NceEngine()) if self.wide else self.nce,      # (the flat-buffer kernels live in csrc/nce.hip; ``flat_engine``: tests)
+                                        (flat_engine or NceEngine()) if self.wide else self.nce,      # (the flat-buffer kernels live in csrc/step_tail.hip; ``flat_engine``: tests)
                                         momentum=momentum, lr_decay=lr_decay)
         self.L = len(model.gnn.ginlayers)
         self.keys_all = torch.empty(self.B * world_size, contrast.inputSize if self.wide else H, device=self.dev) if self.collectives else None
@@ -994,7 +978,7 @@ class MoCoTrainStep(_GraphedStep):
                 dq = self.nce.backward(feat_q, feat_k, mem, c.T, 0, S["outs"], self.one, stream=st,
                                        prof=pr.get("nce_bwd"), defer_means=defer) # loss.backward(), train.py:408
             kw = {} if self.wide else dict(prof=pr.get("gin_bwd"))
-            if self.fold and scalars is not None and not self.collectives and isinstance(self.optimizer, FlatAdam):
+            if self.fold and scalars is not None and not self.collectives and self.optimizer.rule == "adam":
                 # nothing touches the gradient between the backward's last kernel and Adam: its sum of squares is taken there
                 _, n = self.gin.backward(enc, S["pq"], S["bufq"], dq, targets=self.grad_views, stream=st,
                                          sumsq=self.optimizer.sumsq_parts, **kw)

@@ -1,5 +1,5 @@
 """Shared by tests/test_cls_head_edges_emu.py and tests/test_cls_head_edges_gpu.py: the fine-tuning head and clip-by-value Adam
-(csrc/cls_head.hip) at their shape edges against float64 torch (``F.cross_entropy`` on ``feat @ W.T + b``; ``clip_grad_value_`` +
+(csrc/cls_head.hip, csrc/step_tail.hip) at their shape edges against float64 torch (``F.cross_entropy`` on ``feat @ W.T + b``; ``clip_grad_value_`` +
 ``torch.optim.Adam``).  TEST INFRASTRUCTURE ONLY.
 
 Inputs are generated on the CPU from fixed seeds and then moved (tests/wide_edges_check.py::Tier): both tiers run the same numbers.

@@ -1,4 +1,5 @@
-"""The MoCo / InfoNCE head, the queue enqueue, the EMA update, the gradient norm and Adam (gcc_amd/csrc/nce.hip) against the
+"""The MoCo / InfoNCE head (gcc_amd/csrc/nce.hip), the queue enqueue, the EMA update, the gradient norm and Adam
+(gcc_amd/csrc/step_tail.hip) against the
 reference-generated golden vectors, the oracle and float64 restatements in torch, shared by the emulator tier
 (tests/test_nce_emu.py, tests/test_nce_onepass_emu.py) and the GPU tier (tests/test_nce_gpu.py): the same cases and checks; only
 the library, the pointer function and the device differ.
@@ -592,7 +593,7 @@ def _scratch_ticket(scratch):
 
 
 def check_adam(S, n, tail=None):
-    """gcc_adam_step (``tail`` None: gradnorm_kernel + adam_kernel) or gcc_adam_ema_step with n_ema = n + tail (the EMA copy
+    """gcc_adam_step (``tail`` None: gradnorm_kernel + tail_norm_kernel<0>) or gcc_adam_ema_step with n_ema = n + tail (the EMA copy
     covers ``tail`` elements past the live prefix) over two steps, the first with the gradient norm above max_norm 1.0, the
     second below it, against a float64 restatement of clip_grad_norm_ + torch.optim.Adam (L2 weight decay) + moment_update
     (train.py:169-172,409,417).  The restatement takes lr, the betas, eps, the weight decay and the EMA momentum at the float

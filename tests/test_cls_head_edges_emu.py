@@ -1,4 +1,4 @@
-"""The fine-tuning head and clip-by-value Adam (csrc/cls_head.hip) at their shape edges on the emulator build, against float64
+"""The fine-tuning head and clip-by-value Adam (csrc/cls_head.hip, csrc/step_tail.hip) at their shape edges on the emulator build, against float64
 torch.  The cases, inputs and bars are tests/cls_head_check.py's; the device tier is tests/test_cls_head_edges_gpu.py."""
 import pytest
 

@@ -1,4 +1,4 @@
-"""The fine-tuning head and clip-by-value Adam (csrc/cls_head.hip) at their shape edges on a real MI355X, against float64
+"""The fine-tuning head and clip-by-value Adam (csrc/cls_head.hip, csrc/step_tail.hip) at their shape edges on a real MI355X, against float64
 torch.  The cases, inputs and bars are tests/cls_head_check.py's; the emulator tier is tests/test_cls_head_edges_emu.py.
 
 Measured on an MI355X (worst error of loss, logits, dW, db, dfeat and dlogits against float64, as a share of the tensor's largest

@@ -1,4 +1,4 @@
-"""The fine-tuning head (gcc_amd/csrc/cls_head.hip), clip-by-value Adam and FinetuneTrainStep on the emulator build, against
+"""The fine-tuning head (gcc_amd/csrc/cls_head.hip), clip-by-value Adam (csrc/step_tail.hip) and FinetuneTrainStep on the emulator build, against
 float64 torch and against tests/golden/finetune_golden.pt (the reference's own encoder inside its train_finetune)."""
 import pytest
 import torch

@@ -1,4 +1,4 @@
-"""The MoCo / InfoNCE head, the enqueue, the EMA update, the gradient norm and Adam (gcc_amd/csrc/nce.hip) on a real MI355X:
+"""The MoCo / InfoNCE head, the enqueue, the EMA update, the gradient norm and Adam (gcc_amd/csrc/nce.hip, step_tail.hip) on a real MI355X:
 every check of tests/test_nce_emu.py and tests/test_nce_onepass_emu.py (tests/nce_check.py) at the smallest shapes that still
 reach each path -- a last slice shorter than a chunk, a last slice of one row, B = 63 / 65, more than 64 slices, patch rows
 that wrap, several query blocks of the E2E head.

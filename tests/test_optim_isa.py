@@ -14,10 +14,10 @@ from tests.test_solver_footprint import _metadata  # noqa: E402
 pytestmark = pytest.mark.skipif(not os.path.exists(isa_chains.HIPCC) or shutil.which("make") is None,
                                 reason="hipcc not installed")
 
-SRC = isa_chains.ROOT / "gcc_amd" / "csrc" / "nce.hip"
+SRC = isa_chains.ROOT / "gcc_amd" / "csrc" / "step_tail.hip"
 
 
-@pytest.mark.parametrize("kernel", ["opt_kernelILi1E", "opt_kernelILi2E", "opt_clipvalue_kernelILi1E", "opt_clipvalue_kernelILi2E"])
+@pytest.mark.parametrize("kernel", ["tail_norm_kernelILi1E", "tail_norm_kernelILi2E", "tail_value_kernelILi1E", "tail_value_kernelILi2E"])
 def test_sgd_and_adagrad_tails_have_no_scratch(kernel):
     md = _metadata(isa_chains.isa_of(SRC), kernel)
     assert md["private_segment_fixed_size"] == 0, md

@@ -18,7 +18,7 @@ pytestmark = pytest.mark.skipif(not os.path.exists(isa_chains.HIPCC) or shutil.w
 CSRC = isa_chains.ROOT / "gcc_amd" / "csrc"
 
 
-@pytest.mark.parametrize("src,kernel", [("nce.hip", "nce_onepass_kernel"), ("nce.hip", "nce_merge_kernel"), ("nce.hip", "adam_kernel"),
+@pytest.mark.parametrize("src,kernel", [("nce.hip", "nce_onepass_kernel"), ("nce.hip", "nce_merge_kernel"), ("step_tail.hip", "tail_norm_kernelILi0E"),
                                         ("encoder_bwd.hip", "gin_grad_final_kernel"), ("encoder.hip", "gin_feat_kernel")])
 def test_no_scratch(src, kernel):
     md = _metadata(isa_chains.isa_of(CSRC / src), kernel)

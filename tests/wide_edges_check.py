@@ -62,7 +62,7 @@ class Tier:
         return GinEngine(**self._kw())
 
     def head_engine(self):
-        """the fine-tuning head and clip-by-value Adam (csrc/cls_head.hip)"""
+        """the fine-tuning head and clip-by-value Adam (csrc/cls_head.hip, csrc/step_tail.hip)"""
         from gcc_amd.finetune import ClsHeadEngine
 
         return ClsHeadEngine(**self._kw())

@@ -15,7 +15,7 @@ import numpy as np
 root = sys.argv[1]
 path = glob.glob(os.path.join(root, "**", "*kernel_trace.csv"), recursive=True)[0]
 rows = list(csv.DictReader(open(path)))
-TRAIN = ("gin_", "nce_", "adam_kernel", "gradnorm_kernel", "queue_enqueue_kernel", "step_scalars")
+TRAIN = ("gin_", "nce_", "tail_norm_kernel", "tail_value_kernel", "gradnorm_kernel", "queue_enqueue_kernel", "step_scalars")
 ev = sorted(((int(r["Start_Timestamp"]), int(r["End_Timestamp"]), r["Kernel_Name"]) for r in rows
              if any(t in r["Kernel_Name"] for t in TRAIN)), key=lambda e: e[0])
 first = [i for i, e in enumerate(ev) if "gin_feat_kernel" in e[2]]
